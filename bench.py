@@ -10,7 +10,7 @@ computed" (on every rank, when there are several). Inputs are uploaded to HBM be
 
 N=1 workload: BASELINE.json configs[2], the largest single-GPU configuration — S. cerevisiae-size 12 Mb genome,
 Nanopore-like 25x long reads + PAF against short-read contigs, synthetic (tools/hxsim, seed 0x4841534c + 2;
-there is no network for real reads). configs[1] (E. coli-size 4.6 Mb, PacBio-like 25x) is measured too and
+there is no network for real reads). With --full, configs[1] (E. coli-size 4.6 Mb, PacBio-like 25x) is measured too and
 reported under "configs1" (`--workload ecoli` makes it the main line instead); configs[3]'s 140 Mb data set is run on
 the one GPU as well and reported under "configs3" (the many-edge regime: throughput, not one edge's chain).
 N>1: reads sharded by id range, ONE all-gather of edge records (RCCL), edges sharded by estimated DP cost for
@@ -20,11 +20,16 @@ chromosome's worth (280 Mb; 1.12 Gb = the shape of configs[4] at 0.36 x its size
 (`config.workload` says which). Launched WITHOUT torch.distributed.run, `--gpus N` runs the product binary's own multi-GPU path instead: N ranks
 inside this process (hx_group_create, one RCCL all-gather in hx_edge_merge, hxh_runs_all_sharded - what `haslr_assemble --gpus N` runs). After the timed steps every rank stitches the
 assembly, the ranks' assemblies must be identical, and rank 0 repeats the pass on its GPU alone and requires the
-same assembly (`assembly.matches_single_gpu`).
+same assembly (`assembly.matches_single_gpu`; under a launcher with --full).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` (one
+timed step) and the figures read off the timed passes themselves (`roofline`, `stage_ms`, `kernel_ms`). `--full` adds what takes work of its own:
+`one_shot`, `assembly`, `gfa`, `cpu_baseline`, `configs1`, `configs3` (the --no-* options leave single ones out again).
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) - the inputs are the same from run to run for the same arguments.
 
 Extra objects on the JSON line: `roofline` for the dominant kernel (K6 POA; HBM bound named by the north
 star, algorithmic bytes per SURVEY.md 8d) with GCUPS against the VALU issue bound (256 CU x 4 SIMD-32 x 2.4 GHz),
-the SQ-counter figures of the committed profile, the critical path and the POA workspace; `gfa` +
+the SQ-counter figures of the committed profile, the critical path and the POA workspace; with --full, `gfa` +
 `gfa_equals_cpu_baseline` (the metric's "GFA match": six files, byte for byte); and `cpu_baseline` (the
 CPU oracle = a port of the reference path with AVX2 row kernels, timed on this box's host cores on the SAME
 data set, 64 threads and all cores; its consensus must equal the GPU's).
@@ -96,6 +101,43 @@ def gfa_digest(out_dir):
     """sha256 of each of the six backbone.0x.*.gfa files of a run directory (the metric's "GFA match")"""
     files = sorted(glob.glob(os.path.join(out_dir, "backbone.0[1-6].*.gfa")))
     return {os.path.basename(f): hashlib.sha256(open(f, "rb").read()).hexdigest() for f in files}
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(run, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives from a pass - chain_out, edges_out, coords_out and the consensus sequences - as
+    out_dir/<stage>.<array>.npy. Integer arrays are written as float64 (exact: every value is below 2^53; a packed directed edge key, from << 32 | to,
+    is written as its two halves `<array>_from` / `<array>_to`), the consensus as character codes in float32 (`consensus.bases`) beside the
+    sequences' offsets (`consensus.offsets`). Above `limit` bytes in all, every array is cut to the same fraction by a fixed, seeded choice of
+    positions (in order), so that two builds given the same arguments are compared position for position."""
+    import zlib
+
+    import numpy as np
+    arrays = {}
+    for stage, d in (("chain", run.chain_out()), ("edges", run.edges_out()), ("coords", run.coords_out())):
+        for k, a in d.items():
+            if k in ("key", "edge_key"):
+                arrays[f"{stage}.{k}_from"] = (a >> np.uint64(32)).astype(np.float64)
+                arrays[f"{stage}.{k}_to"] = (a & np.uint64(0xFFFFFFFF)).astype(np.float64)
+            else:
+                if a.size and int(a.max()) >= 1 << 53:
+                    raise SystemExit(f"--dump-outputs: {stage}.{k} holds values float64 cannot represent exactly")
+                arrays[f"{stage}.{k}"] = a.astype(np.float64)
+    cns = run.cns_out()
+    arrays["consensus.bases"] = np.frombuffer("".join(cns).encode(), np.uint8).astype(np.float32)
+    arrays["consensus.offsets"] = np.cumsum([0] + [len(c) for c in cns], dtype=np.int64).astype(np.float64)
+    header = 128                                       # bytes of an .npy header for a 1-D array
+    total = sum(a.nbytes + header for a in arrays.values())
+    frac = 1.0 if total <= limit else (limit - header * len(arrays)) / sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if frac < 1.0:
+            m = int(a.size * frac)
+            a = a[np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, m, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": len(arrays), "sampled_fraction": min(1.0, frac)}
 
 
 def bench_dir():
@@ -324,7 +366,7 @@ def run_group(args):
     # afterwards, when the group has given its memory back (a reference for the assembly and a rough N = 1 figure).
     solo_first = n == 1
     if solo_first:
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(max(1, args.warmup)), "--no-cpu-baseline", "--no-configs1", "--no-configs3", "--no-one-shot"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(max(1, args.warmup)), "--full", "--no-cpu-baseline", "--no-configs1", "--no-configs3", "--no-one-shot"]
         if args.workload:
             cmd += ["--workload", args.workload]
         if args.genome_len:
@@ -446,11 +488,18 @@ def main():
                     help="default: yeast (BASELINE configs[2]; x N for N = 2, 8), fly (configs[3] as BASELINE names it: 140 Mb on 4 GPUs) at N = 4")
     ap.add_argument("--genome-len", type=int, default=0, help="override the per-run genome length (testing)")
     ap.add_argument("--poa-block", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the CPU baseline, the one-shot figures, the assembly and GFA checks, "
+                         "configs1 and configs3 (each of these can be left out again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (single-process N = 1 line)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs1", action="store_true", help="skip the extra E. coli-size (configs[1]) measurement")
     ap.add_argument("--no-one-shot", action="store_true", help="skip the one-shot figures (haslr_assemble end to end in a process of its own, the cold first pass of a fresh context)")
     ap.add_argument("--no-configs3", action="store_true", help="skip the extra D. melanogaster-size (configs[3], 140 Mb on this one GPU: the many-edge regime) measurement")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps (and the dump) - the extras are --full's
+        args.no_cpu_baseline = args.no_configs1 = args.no_configs3 = args.no_one_shot = True
 
     import torch
     import torch.distributed as dist
@@ -462,7 +511,10 @@ def main():
     # HASLR_BENCH_FORCE_DIST=1 (testing): the N>1 code path - process group, record all-gather, results exchange - with whatever world size the launcher
     # gave, also 1: a one-GPU box then executes the RCCL collectives of the multi-GPU path for real
     dist_on = world > 1 or os.environ.get("HASLR_BENCH_FORCE_DIST") == "1"
-    if world == 1 and (args.gpus > 1 or os.environ.get("HASLR_BENCH_FORCE_GROUP") == "1"):
+    grouped = world == 1 and (args.gpus > 1 or os.environ.get("HASLR_BENCH_FORCE_GROUP") == "1")
+    if args.dump_outputs and (dist_on or grouped):
+        raise SystemExit("--dump-outputs: the single-process N = 1 line only (a sharded pass leaves each rank a share of the outputs)")
+    if grouped:
         return run_group(args)                     # no launcher: the ranks live inside this process, like haslr_assemble --gpus N (HASLR_BENCH_FORCE_GROUP=1: also for one rank)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device: the product path has no CPU fallback")
@@ -534,6 +586,7 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=comm_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = dump_outputs(last, args.dump_outputs) if args.dump_outputs else None
 
     # per-launch figures of the dominant kernel (K6 POA), hipEvent-timed inside the library on its stream
     tim = ctx.timing()
@@ -554,40 +607,42 @@ def main():
     poa_host = ctx.poa_host_times()   # of the last step's consensus call
     kernel_ms = {k: v["ms"] / max(1, v["launches"]) for k, v in tim.items()}
 
-    # ---- the assembly (outside the timed region): every rank stitches; N>1: identical on all ranks and equal to a single-GPU pass
-    last.assemble()
-    fasta = last.assembly_fasta()
-    sha = hashlib.sha256(fasta.encode()).hexdigest()
-    assembly = {"sha256": sha, "contigs": fasta.count(">"), "bases": sum(len(x) for x in fasta.split("\n") if x and x[0] != ">")}
-    if dist_on:
-        h = torch.frombuffer(bytearray(bytes.fromhex(sha)), dtype=torch.uint8).to(comm_device)
-        hs = [torch.zeros(32, dtype=torch.uint8, device=comm_device) for _ in range(world)]
-        dist.all_gather(hs, h)
-        assembly["same_on_all_ranks"] = all(bool(torch.equal(hs[0], x)) for x in hs)
-        assembly["results_gathered_bytes"] = gathered[0]
-        assembly["edge_record_exchange_bytes"] = backend.exchange_bytes
-        assembly["edge_record_exchange_ms"] = backend.exchange_ms      # wall time of the record all-gather of the last step on this rank (over xGMI with RCCL; SURVEY 8e expects 10-15 ms at CHM1 scale)
-        if backend_name == "gloo" and dist.get_world_size() > 1:
-            # rehearsal mode (all ranks on one device): the single-GPU pass needs the memory the other ranks' workspaces hold
-            last.close()
-            ctx.close()
-            torch.cuda.empty_cache()
-            dist.barrier()
+    # ---- the assembly (--full; outside the timed region): every rank stitches; N>1: identical on all ranks and equal to a single-GPU pass
+    assembly = None
+    if args.full:
+        last.assemble()
+        fasta = last.assembly_fasta()
+        sha = hashlib.sha256(fasta.encode()).hexdigest()
+        assembly = {"sha256": sha, "contigs": fasta.count(">"), "bases": sum(len(x) for x in fasta.split("\n") if x and x[0] != ">")}
+        if dist_on:
+            h = torch.frombuffer(bytearray(bytes.fromhex(sha)), dtype=torch.uint8).to(comm_device)
+            hs = [torch.zeros(32, dtype=torch.uint8, device=comm_device) for _ in range(world)]
+            dist.all_gather(hs, h)
+            assembly["same_on_all_ranks"] = all(bool(torch.equal(hs[0], x)) for x in hs)
+            assembly["results_gathered_bytes"] = gathered[0]
+            assembly["edge_record_exchange_bytes"] = backend.exchange_bytes
+            assembly["edge_record_exchange_ms"] = backend.exchange_ms      # wall time of the record all-gather of the last step on this rank (over xGMI with RCCL; SURVEY 8e expects 10-15 ms at CHM1 scale)
+            if backend_name == "gloo" and dist.get_world_size() > 1:
+                # rehearsal mode (all ranks on one device): the single-GPU pass needs the memory the other ranks' workspaces hold
+                last.close()
+                ctx.close()
+                torch.cuda.empty_cache()
+                dist.barrier()
+                if rank == 0:
+                    ctx = hip.HipContext(dev_index)
+                    ctx.upload(ds)
             if rank == 0:
-                ctx = hip.HipContext(dev_index)
-                ctx.upload(ds)
-        if rank == 0:
-            last.close()
-            ctx.set_read_shard(0, ds.reads.n)
-            t0 = time.perf_counter()
-            solo = host.Run(ds, prm, ctx.backend(), None)
-            solo.all()
-            assembly["single_gpu_pass_s"] = time.perf_counter() - t0
-            assembly["matches_single_gpu"] = hashlib.sha256(solo.assembly_fasta().encode()).hexdigest() == sha
-            last = solo
-        dist.barrier()
-        if not assembly["same_on_all_ranks"] or (rank == 0 and not assembly["matches_single_gpu"]):
-            raise SystemExit(f"[rank {rank}] multi-GPU assembly differs: {assembly}")
+                last.close()
+                ctx.set_read_shard(0, ds.reads.n)
+                t0 = time.perf_counter()
+                solo = host.Run(ds, prm, ctx.backend(), None)
+                solo.all()
+                assembly["single_gpu_pass_s"] = time.perf_counter() - t0
+                assembly["matches_single_gpu"] = hashlib.sha256(solo.assembly_fasta().encode()).hexdigest() == sha
+                last = solo
+            dist.barrier()
+            if not assembly["same_on_all_ranks"] or (rank == 0 and not assembly["matches_single_gpu"]):
+                raise SystemExit(f"[rank {rank}] multi-GPU assembly differs: {assembly}")
 
     # HBM traffic of the POA launch group: measured offline with rocprofv3 PMC passes for exactly this workload (profiles/*_traffic.json)
     traffic, traffic_src = None, None
@@ -626,7 +681,7 @@ def main():
                       "wait_share": sq["SQ_WAIT_ANY"] / sq["SQ_WAVE_CYCLES"] if sq.get("SQ_WAVE_CYCLES") else None,
                       "sq_counters_source": sq_src}
         gfa_gpu = None
-        if world == 1:   # the metric's "GFA match": the six backbone.0x.*.gfa snapshots of a GPU pass (untimed) against the CPU leg's, byte for byte
+        if world == 1 and args.full:   # the metric's "GFA match": the six backbone.0x.*.gfa snapshots of a GPU pass (untimed) against the CPU leg's, byte for byte
             work_dir = os.path.join(os.environ.get("HASLR_BENCH_DIR", "/tmp/haslr_bench"), "gfa_%s" % args.workload)
             r2 = host.Run(ds, prm, ctx.backend(), os.path.join(work_dir, "gpu_gfa"))
             r2.chain(); r2.graph(); r2.close()
@@ -648,12 +703,16 @@ def main():
                          "note": "POA is an O(L^2) integer DP over O(L) bytes: HBM fraction is low by construction (SURVEY.md 8d); GCUPS against the VALU issue bound "
                                  "(256 CU x 4 SIMD-32 x 2.4 GHz lane-ops/s / 10 lane-ops per cell) is the figure of merit; valu_lane_ops_per_cell / valu_issue_util / wait_share are "
                                  "what the SQ counters of the committed profile say the kernel really issues; critical_path_ms = the slowest edge's serial chain (its lane-0 cycle counters / 2.4 GHz)"},
-            "stage_ms": stage_ms, "kernel_ms": kernel_ms, "consensus_host_ms": {**poa_host, "stage_minus_launch_group_ms": stage_ms.get("consensus", 0) - poa_ms}, "poa_phase_cycles": {"edges": phase["edges"], "slowest_edge": phase["slowest_edge"]}, "assembly": assembly, "gfa": gfa_gpu,
+            "stage_ms": stage_ms, "kernel_ms": kernel_ms, "consensus_host_ms": {**poa_host, "stage_minus_launch_group_ms": stage_ms.get("consensus", 0) - poa_ms}, "poa_phase_cycles": {"edges": phase["edges"], "slowest_edge": phase["slowest_edge"]},
             # outside the timed region (the metric starts with parsed, resident inputs): text ingest and the PCIe upload
             "ingest": {"seconds": t_parse, "input_mb": in_bytes / 1e6, "mb_per_s": in_bytes / 1e6 / t_parse, "threads": os.environ.get("HASLR_IO_THREADS", "auto (<= 16)"), "upload_seconds": t_upload},
         }
+        if args.full:
+            line.update({"assembly": assembly, "gfa": gfa_gpu})
+        if dumped:
+            line["outputs_dumped"] = dumped
         if world > 1:
-            line["config"].update({"edge_record_exchange_ms": assembly.get("edge_record_exchange_ms"), "edge_record_exchange_bytes": assembly.get("edge_record_exchange_bytes"),
+            line["config"].update({"edge_record_exchange_ms": backend.exchange_ms, "edge_record_exchange_bytes": backend.exchange_bytes,
                                    "rccl_ranks": dist.get_world_size() if backend_name == "nccl" else 0})
             if not args.no_cpu_baseline:
                 try:

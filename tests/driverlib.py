@@ -36,11 +36,11 @@ def make_data(data):
 
 
 def make_bin(bindir, driver, real=()):
-    """a bin/ like the reference's: haslr.py + the five tools. `driver` is copied unless it is a path under /root/reference (then it is
+    """a bin/ like the reference's: haslr.py + the five tools. `driver` is copied unless it is the reference's, staged under oracle/_ref/ (then it is
     linked: the reference may be run in place, never copied). Tools in `real` = {name: path} are linked, the others are stand-ins."""
     os.makedirs(bindir, exist_ok=True)
     dst = os.path.join(bindir, "haslr.py")
-    if driver.startswith("/root/reference/"):
+    if driver.startswith(os.path.join(ROOT, "oracle", "_ref") + os.sep):
         os.symlink(driver, dst)
     else:
         shutil.copy(driver, dst)

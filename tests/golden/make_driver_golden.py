@@ -1,8 +1,8 @@
-"""Regenerates tests/golden/driver/*.json: what the REFERENCE's pipeline driver (bin/haslr.py, run in place from /root/reference through a
-link, never copied) does in each scenario of tests/driverlib.py when all five tools are recording stand-ins (tests/stub_tool.py) except
+"""Regenerates tests/golden/driver/*.json: what the REFERENCE's pipeline driver (bin/haslr.py as build() stages it under oracle/_ref/, run there
+through a link, never copied) does in each scenario of tests/driverlib.py when all five tools are recording stand-ins (tests/stub_tool.py) except
 minia_nooverlap, which is this build's tool (itself pinned to the compiled reference tool by tests/test_nooverlap.py). Stored per scenario
 and per run: exit status, stdout with time stamps and temporary paths masked, the tools' command lines, the output tree.
-    python tests/golden/make_driver_golden.py        (in the build container; needs /root/reference and a built haslr_amd/bin)"""
+    python tests/golden/make_driver_golden.py        (after build() with the reference sources present: oracle/_ref/haslr.py, haslr_amd/bin)"""
 import json
 import os
 import sys
@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import driverlib  # noqa: E402
 
-REF = "/root/reference/bin/haslr.py"
+REF = os.path.join(driverlib.ROOT, "oracle", "_ref", "haslr.py")
 
 
 def main():

@@ -51,8 +51,9 @@ def main():
                 if len(seq) >= m:
                     sys.stdout.write(">%s\n%s\n" % (name, seq))
     elif tool == "minia":
-        print("minia stand-in: stdout")
-        print("minia stand-in: stderr", file=sys.stderr)
+        # both streams go to one log: written in a fixed order, whether or not Python buffers stdout (PYTHONUNBUFFERED)
+        print("minia stand-in: stderr", file=sys.stderr, flush=True)
+        print("minia stand-in: stdout", flush=True)
         if fail == "minia":
             return 3
         prefix = opt(argv, "-out")

@@ -13,9 +13,9 @@ for step in "$@"; do
     ab140dbg) HX_DEBUG=1 AB_PASSES=2 timeout 1500 python tools/dev_r05_ab.py ${AB_SPECS:-"-"} 2>&1 | grep "RESULT\|pruning\|class .: .* workgroups\|POA batch:\|top edge" | cut -c1-420 | tee $O/ab140dbg.txt ;;
     edgedump) HX_DEBUG=2 AB_PASSES=2 timeout 1500 python tools/dev_r05_ab.py ${AB_SPECS:-"-"} 2> $O/edgedump.err | tee $O/edgedump.txt; grep -c "hx-edge" $O/edgedump.err ;;
     ab12) AB_WORKLOAD=yeast timeout 900 python tools/dev_r05_ab.py ${AB12_SPECS:-"-" "poa_prune=95"} 2> $O/ab12.err | tee $O/ab12.txt ;;
-    benchq) timeout 1500 python bench.py --no-cpu-baseline --steps ${BENCH_STEPS:-6} --warmup 2 > $O/benchq.json 2> $O/benchq.err; python -c "
+    benchq) timeout 1500 python bench.py --full --no-cpu-baseline --steps ${BENCH_STEPS:-6} --warmup 2 > $O/benchq.json 2> $O/benchq.err; python -c "
 import json;d=json.load(open('$O/benchq.json'));print('ms/step',d['ms_per_step'],'gcups',d['roofline']['gcups'],'slowest',d['poa_phase_cycles']['slowest_edge'],'config',d['config'])" ;;
-    bench) timeout 1800 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 2500 $O/bench.json ;;
+    bench) timeout 1800 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 2500 $O/bench.json ;;
     alltests) timeout 3000 python -m pytest tests -m gpu -q 2>&1 | grep -v "^       removed" | tail -30 | cut -c1-400 | tee $O/alltests.txt ;;
     *) echo "unknown step $step" ;;
   esac

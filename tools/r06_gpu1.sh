@@ -6,7 +6,7 @@ O=gpurun_out/r06_1
 mkdir -p $O
 export HASLR_BENCH_DIR=/tmp/haslr_bench
 { nproc; free -g; df -h /tmp / /dev/shm; rocm-smi --showmeminfo vram 2>/dev/null | head -8; } > $O/probe.txt 2>&1
-timeout 900 python bench.py --steps 6 --warmup 2 > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full --steps 6 --warmup 2 > $O/bench.json 2> $O/bench.err
 FLY=/tmp/haslr_bench/gpu_pacbio_g140000000_s4841534f
 YST=/tmp/haslr_bench/gpu_nanopore_g12000000_s4841534e
 ls -la /tmp/haslr_bench > $O/files.txt
@@ -37,10 +37,10 @@ for th in (16, 32, 64, 128, 16):
     ds.close()
 PY
 for v in "A=1" "HX_POA_PRUNE=95 HX_POA_PASS_LANES=0" "HX_POA_PRUNE=95 HX_POA_PASS_LANES=0 HX_POA_PRUNE_LANES=512"; do
-  echo "== $v"; env $v timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-configs1 --no-configs3 --no-one-shot 2>&1 | grep -E "step |^\{" | cut -c1-400
+  echo "== $v"; env $v timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-configs1 --no-configs3 --no-one-shot 2>&1 | grep -E "step |^\{" | cut -c1-400
 done > $O/prune_few_edges.txt 2>&1
 for v in "A=1" "HX_POA_WORKSPACE_GB=257" "HX_POA_WORKSPACE_GB=100"; do
-  echo "== $v"; env $v timeout 300 python bench.py --workload fly --steps 3 --warmup 1 --no-cpu-baseline --no-configs1 --no-configs3 --no-one-shot 2>&1 | grep -E "step |^\{" | cut -c1-600
+  echo "== $v"; env $v timeout 300 python bench.py --full --workload fly --steps 3 --warmup 1 --no-cpu-baseline --no-configs1 --no-configs3 --no-one-shot 2>&1 | grep -E "step |^\{" | cut -c1-600
 done > $O/workspace_ab.txt 2>&1
 timeout 1500 python -m pytest tests -m gpu -x -q --durations=45 > $O/gpu_tests.log 2>&1
 tail -5 $O/gpu_tests.log

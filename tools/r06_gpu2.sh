@@ -7,7 +7,7 @@ mkdir -p $O
 export HASLR_BENCH_DIR=/tmp/haslr_bench
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -o /tmp/allocbench tools/dev_allocbench.hip -lpthread 2> $O/allocbench_build.err
 timeout 600 /tmp/allocbench 208 > $O/allocbench.txt 2>&1
-timeout 900 python bench.py --workload fly --steps 3 --warmup 1 --no-cpu-baseline --no-configs1 > $O/bench_fly.json 2> $O/bench_fly.err
+timeout 900 python bench.py --full --workload fly --steps 3 --warmup 1 --no-cpu-baseline --no-configs1 > $O/bench_fly.json 2> $O/bench_fly.err
 cp /tmp/haslr_bench/cli_fly.stderr.txt $O/ 2>/dev/null
 FLY=/tmp/haslr_bench/gpu_pacbio_g140000000_s4841534f
 cli() { # tag prefix env...

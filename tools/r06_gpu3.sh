@@ -4,7 +4,7 @@ set -u
 O=gpurun_out/r06_3
 mkdir -p $O
 export HASLR_BENCH_DIR=/tmp/haslr_bench
-timeout 900 python bench.py --workload fly --steps 3 --warmup 1 --no-cpu-baseline --no-configs1 > $O/bench_fly.json 2> $O/bench_fly.err
+timeout 900 python bench.py --full --workload fly --steps 3 --warmup 1 --no-cpu-baseline --no-configs1 > $O/bench_fly.json 2> $O/bench_fly.err
 cp /tmp/haslr_bench/cli_fly.stderr.txt $O/ 2>/dev/null
 FLY=/tmp/haslr_bench/gpu_pacbio_g140000000_s4841534f
 cli() { # tag prefix env...

@@ -23,5 +23,5 @@ cat $O/top_edges.txt
 rm -f $O/edgedump.err
 HASLR_BENCH_FORCE_GROUP=1 HASLR_GROUP_TRANSPORT=host timeout 600 python bench.py --gpus 1 --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_group1.json 2> $O/bench_group1.err
 grep "step " $O/bench_group1.err | cut -c1-100
-HASLR_GROUP_TRANSPORT=host timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 > $O/bench_group2_host.json 2> $O/bench_group2_host.err
+HASLR_GROUP_TRANSPORT=host timeout 900 python bench.py --full --gpus 2 --steps 2 --warmup 1 > $O/bench_group2_host.json 2> $O/bench_group2_host.err
 tail -3 $O/bench_group2_host.err | cut -c1-300
