@@ -21,6 +21,7 @@
 #include "../../include/haslr_hip.h"
 #include "host/haslr_host.h"
 #include "kernels/kernels.h"
+#include "kernels/poa_modes.h"
 
 namespace {
 
@@ -167,6 +168,8 @@ struct HxOptions {
     int poa_prune_lazy = 1;        // ... a wave that skipped a whole batch of rows polls for the next one rarely (0: like any wave)
     int poa_prune_lanes = 128;     // ... in launches of workgroups of at least this many lanes (a one-wave workgroup has no block to skip)
     int coords_lds_supp = -1;      // supports per edge the coordinate kernel sorts in LDS (testing: 0 sends every edge through the global scratch)
+    int poa_general = 0;           // hx_poa_sequences_mode with HX_POA_NW runs the general path (kernels/poa_modes.hip) instead of the tuned one: the cross-check of what the modes share with kNW
+    int poa_modes_slot_kb = 0;     // the general path's first round of slots holds at most this many KB (testing: forces the overflow and the rerun in a larger slot; 0 no cap)
 };
 struct OptDesc { const char* name; int HxOptions::*ip; double HxOptions::*dp; };
 const OptDesc kOptions[] = {
@@ -180,6 +183,7 @@ const OptDesc kOptions[] = {
     {"poa_slots", &HxOptions::poa_slots, nullptr}, {"poa_batches", &HxOptions::poa_batches, nullptr}, {"poa_force_cm", &HxOptions::poa_force_cm, nullptr},
     {"poa_no_xcd_map", &HxOptions::poa_no_xcd_map, nullptr}, {"poa_streams", &HxOptions::poa_streams, nullptr}, {"poa_wide_delay_us", &HxOptions::poa_wide_delay_us, nullptr},
     {"poa_prune", &HxOptions::poa_prune, nullptr}, {"poa_prune_lanes", &HxOptions::poa_prune_lanes, nullptr}, {"poa_prune_lazy", &HxOptions::poa_prune_lazy, nullptr}, {"poa_prune_shared", &HxOptions::poa_prune_shared, nullptr}, {"poa_pass_lanes", &HxOptions::poa_pass_lanes, nullptr}, {"poa_chain_ms", &HxOptions::poa_chain_ms, nullptr}, {"poa_chain_pct", &HxOptions::poa_chain_pct, nullptr}, {"poa_scratch_warm", &HxOptions::poa_scratch_warm, nullptr}, {"poa_big_first", &HxOptions::poa_big_first, nullptr}, {"poa_order_by_cells", &HxOptions::poa_order_by_cells, nullptr}, {"poa_slots_by_work", &HxOptions::poa_slots_by_work, nullptr}, {"poa_resident_first", &HxOptions::poa_resident_first, nullptr}, {"poa_own_bucket_first", &HxOptions::poa_own_bucket_first, nullptr}, {"poa_bucket_half_octaves", &HxOptions::poa_bucket_half_octaves, nullptr}, {"coords_lds_supp", &HxOptions::coords_lds_supp, nullptr},
+    {"poa_general", &HxOptions::poa_general, nullptr}, {"poa_modes_slot_kb", &HxOptions::poa_modes_slot_kb, nullptr},
 };
 }  // namespace
 
@@ -244,6 +248,7 @@ struct hx_ctx {
     // POA workspace lives as long as the context: allocating tens of GB per call costs more than the kernel
     PoaPoolBufs poa_pools;
     PoaArena poa_arena;
+    hxk::PoaModesWs poa_modes_ws;       // workspace of the general path (hx_poa_sequences_mode: kSW / kOV, and kNW under option poa_general)
     std::mutex poa_arena_mu;            // hx_poa_reserve may run on a thread of its own beside the upload and the first stages
     double poa_host_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // host wall time of the last consensus call: plan, workspace, enqueue, device wait, collect, finish, (unused), total
     uint64_t poa_budget = 0;
@@ -1682,6 +1687,28 @@ extern "C" int hx_poa_sequences(hx_ctx* c, uint32_t n_sets, const uint64_t* set_
     return rc;
 }
 
+extern "C" int hx_poa_sequences_mode(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_mode_params* mp, hx_cns_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!mp) return fail("hx_poa_sequences_mode: no parameters");
+    if (mp->gap >= 0) return fail("hx_poa_sequences_mode: the gap score must be negative (linear gap penalty), not " + std::to_string(mp->gap));
+    if (mp->type != HX_POA_SW && mp->type != HX_POA_NW && mp->type != HX_POA_OV) return fail("hx_poa_sequences_mode: unknown alignment type " + std::to_string(mp->type) + " (HX_POA_SW 0, HX_POA_NW 1, HX_POA_OV 2)");
+    if (set_off[n_sets] >= 0x7fffffffULL) return fail("hx_poa_sequences_mode: too many sequences");
+    const hx_poa_params pp{mp->match, mp->mismatch, mp->gap};
+    if (mp->type == HX_POA_NW && !c->opt.poa_general) return hx_poa_sequences(c, n_sets, set_off, seq_off, bases, &pp, out);   // the tuned global path
+    HIPCHK(hipSetDevice(c->device));
+    const hxk::PoaModesArgs a{n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap, mp->type, (uint32_t)std::max(0, c->opt.poa_modes_slot_kb), c->opt.poa_workspace_gb, c->opt.debug};
+    hxk::PoaModesOut o;
+    std::string err;
+    if (hxk::poa_modes_run(c->stream, c->poa_modes_ws, a, o, err)) return fail(err);
+    c->tm.ms[3] += o.kernel_ms; c->tm.launches[3] += o.launches;
+    out->n_edge = n_sets;
+    out->cns_off = (uint64_t*)malloc(((size_t)n_sets + 1) * 8); memcpy(out->cns_off, o.cns_off.data(), ((size_t)n_sets + 1) * 8);
+    out->cns = (char*)malloc(std::max<size_t>(1, o.cns.size())); memcpy(out->cns, o.cns.data(), o.cns.size());
+    out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
+    if (c->opt.debug) fprintf(stderr, "[hx] POA modes call: %u sets, %.3g cells, kernels %.2f ms, %u sets rerun in a larger slot\n", n_sets, (double)o.cells, o.kernel_ms, o.retried);
+    return 0;
+}
+
 extern "C" void hx_free_cns(hx_ctx*, hx_cns_out* o) { free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }
 
 // ================================================================================================ misc
@@ -1803,6 +1830,7 @@ extern "C" int hx_poa_release_workspace(hx_ctx* c) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     { std::lock_guard<std::mutex> lk(c->poa_arena_mu); c->poa_arena.release(); }
+    c->poa_modes_ws.release();
     c->poa_budget = 0;   // taken again, from what is free then, by the next consensus call
     return 0;
 }

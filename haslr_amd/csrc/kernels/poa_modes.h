@@ -1,0 +1,42 @@
+// poa_modes.h — host side of the general POA path (kernels/poa_modes.hip): spoa's linear-gap engine in its three alignment modes
+// (kSW local, kNW global, kOV overlap) for caller-given sequence sets, one workgroup per set. DESIGN.md "General POA path".
+#ifndef HX_POA_MODES_H
+#define HX_POA_MODES_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+namespace hxk {
+
+struct PoaModesWs {   // the path's workspace: one device allocation, grows to the largest call, lives as long as its owner (the context)
+    void* p = nullptr;
+    size_t cap = 0;
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    ~PoaModesWs() { release(); }
+};
+
+struct PoaModesArgs {
+    uint32_t n_sets;
+    const uint64_t *set_off, *seq_off;   // hx_poa_sequences' layout
+    const char* bases;
+    int32_t match, mismatch, gap, type;  // type: 0 kSW, 1 kNW, 2 kOV (spoa::AlignmentType)
+    uint32_t slot_kb_cap;                // first round only: workspace slots of at most this many KB (0: no cap); sets that overflow are rerun in larger slots
+    double workspace_gb;                 // cap of the workspace (0: 40 % of the free device memory)
+    int debug;
+};
+
+struct PoaModesOut {
+    std::vector<uint64_t> cns_off;       // n_sets + 1
+    std::string cns;
+    uint64_t cells = 0, seq_bases = 0, n_aligned = 0;
+    double kernel_ms = 0;                // hipEvents around the launches
+    uint32_t launches = 0, retried = 0;  // kernel launches, sets rerun in a larger slot
+};
+
+// 0 = ok, else -1 with the reason in err
+int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModesOut& o, std::string& err);
+
+}  // namespace hxk
+#endif

@@ -1,0 +1,462 @@
+// poa_modes.hip — the general POA path: spoa's linear-gap engine in its three alignment modes (kSW local, kNW global, kOV overlap) for
+// caller-given sequence sets (hx_poa_sequences_mode; DESIGN.md "General POA path" has the semantics and the mapping).
+//
+// It is a kernel family of its own beside the tuned global-only k_poa (kernels/poa.hip), which depends on kNW throughout (de-ramped keys
+// with tie bits, score-bound pruning, sink lists, end-node ties decided on closures, multi-member pipelines). What the modes share with
+// kNW - spoa's add_alignment, its topological sort, the heaviest bundle with branch completion - is poa_graph.inl, included here as it is.
+//
+// Mapping: one workgroup per set; persistent workgroups pull set indices off a device counter; each owns one slot of the workspace (graph
+// pools sized for the set's total length, then the int32 score matrix H). For every sequence, in order:
+//   * DP, one row per node in spoa's rank order: a lane owns CPL contiguous columns in registers; the predecessor rows' diagonal and vertical
+//     candidates are folded in in-edge order; the horizontal recurrence is a prefix maximum of H[j] - j g (in-lane, then a DPP wave scan and
+//     a scan of the wave totals); kSW clamps at 0 after the scan (exact: a clamped 0 only ever propagates g < 0). The end cell is the first
+//     maximum in row-major order over the mode's candidate cells (per-lane first maxima, then the smallest (row, column) among the best).
+//   * traceback: spoa's literal compare walk over H (first matching predecessor: diagonal, then vertical, then horizontal), thread 0
+//   * graph update (add_alignment), spoa's topological sort (thread 0), rank-ordered predecessor rows (all lanes)
+// and at the end the heaviest bundle with branch completion by the first wavefront. A set whose next alignment needs more of H than its slot
+// holds stops with a status; the host reruns it in a larger slot.
+#include <algorithm>
+#include <chrono>
+#include <numeric>
+
+#include "kernels.h"
+#include "poa_modes.h"
+
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "kernels/poa_modes.hip is written for gfx950 (CDNA4)"
+#endif
+
+namespace hxk {
+
+namespace {
+
+#include "poa_graph.inl"    // the graph of a set, spoa's topological order, heaviest bundle
+
+enum { MT_SW = 0, MT_NW = 1, MT_OV = 2 };
+enum { MS_OK = 0, MS_H_OVERFLOW = 1, MS_GRAPH_OVERFLOW = 2 };
+constexpr uint32_t MAX_SET_BASES = (1u << 21) - 2;   // node ids are packed in 21 bits (+1) in the node records of poa_graph.inl
+
+struct MSet { uint64_t seq_begin, sum_len, cns_off; uint32_t nseq, lmax; };
+
+struct MArgs {
+    const MSet* sets; const uint32_t* order; uint32_t n_items; uint32_t* counter;
+    const uint8_t* codes; const uint64_t* soff;
+    uint8_t* ws; uint64_t slot_bytes;
+    int32_t m, n, g, type;
+    char* cns; uint32_t *cns_len, *status, *vseen; unsigned long long* cells;
+};
+
+__host__ __device__ inline uint64_t al256(uint64_t x) { return (x + 255) & ~255ull; }
+
+// the graph pools of a set at the start of its slot: at most one node per base (vcap = total length), one edge per base and sequence.
+// Returns their bytes; fills g / path / colref when base is not null. The host sizes slots with the same function.
+__host__ __device__ inline uint64_t carve_pools(uint8_t* base, uint64_t T, uint32_t nseq, uint32_t lmax, G* g, uint32_t** path, uint32_t** colref) {
+    const uint64_t vc = T + 1, ec = T + nseq + 1, ac = T + lmax + 2, sc = 4 * vc + ec + 64;
+    uint64_t off = 0;
+    auto take = [&](uint64_t bytes) -> uint8_t* { uint8_t* p = base ? base + off : nullptr; off += al256(bytes); return p; };
+    G t{};
+    t.code = take(vc); t.n_aligned = take(vc); t.mark = take(vc); t.check = take(vc);
+    t.aligned = (uint32_t*)take(12 * vc);
+    t.in_head = (uint32_t*)take(4 * vc); t.in_tail = (uint32_t*)take(4 * vc); t.out_head = (uint32_t*)take(4 * vc); t.out_tail = (uint32_t*)take(4 * vc);
+    t.rank2node = (uint32_t*)take(4 * vc); t.node2rank = (uint32_t*)take(4 * vc); t.stack = (uint32_t*)take(4 * sc);
+    t.score = (int32_t*)take(4 * vc); t.pred = (int32_t*)take(4 * vc);
+    t.row_meta = (uint32_t*)take(4 * vc); t.row_pred_off = (uint32_t*)take(4 * vc + 4);
+    t.pred_rank = (uint32_t*)take(4 * ec); t.pred_w = (int32_t*)take(4 * ec);
+    t.nrec = (uint4*)take(16 * vc); t.nrec2 = (uint4*)take(16 * vc);
+    t.e_from = (uint32_t*)take(4 * ec); t.e_to = (uint32_t*)take(4 * ec); t.e_next_in = (uint32_t*)take(4 * ec); t.e_next_out = (uint32_t*)take(4 * ec);
+    t.e_w = (int32_t*)take(4 * ec);
+    t.aln_node = (int32_t*)take(4 * ac); t.aln_pos = (int32_t*)take(4 * ac);
+    uint32_t* p = (uint32_t*)take(4 * (uint64_t)(lmax + 1));
+    uint32_t* c = (uint32_t*)take(4 * (uint64_t)(lmax + 1));
+    t.vcap = (uint32_t)T; t.ecap = (uint32_t)(T + nseq);
+    if (g) { *g = t; *path = p; *colref = c; }
+    return off;
+}
+
+// block-wide exclusive sum of v (every thread calls it; s_scan holds NT / 64 words); returns the prefix, *total the sum
+template <int NT>
+__device__ __forceinline__ uint32_t block_excl_sum(uint32_t v, uint32_t* s_scan, uint32_t* total) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint32_t incl = wave_scan_add(v);
+    if (lane == 63) s_scan[w] = incl;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+    for (uint32_t q = 0; q < NT / 64; q++) { const uint32_t x = s_scan[q]; pre += q < w ? x : 0u; tot += x; }
+    __syncthreads();
+    *total = tot;
+    return pre + incl - v;
+}
+
+// spoa's rank order after an add (serial DFS, thread 0) and the rows the DP and the heaviest bundle read: per rank the node's base, sink
+// bit and in-degree (row_meta), the ranks and weights of its in-edge sources in in-edge order (row_pred_off / pred_rank / pred_w)
+template <int NT>
+__device__ void order_rows(G& g, const uint32_t V, uint32_t* s_scan) {
+    const uint32_t t = threadIdx.x;
+    for (uint32_t i = t; i < V; i += NT) { g.mark[i] = 0; g.check[i] = 1; }
+    __syncthreads();
+    if (t == 0) toposort(g, V, g.rank2node);
+    __syncthreads();
+    for (uint32_t r = t; r < V; r += NT) g.node2rank[g.rank2node[r]] = r;
+    __syncthreads();
+    uint32_t carry = 0;
+    for (uint32_t b = 0; b < V; b += NT) {
+        const uint32_t r = b + t;
+        uint32_t np = 0;
+        if (r < V) {
+            const uint32_t n = g.rank2node[r];
+            for (uint32_t e = g.in_head[n]; e != NONE; e = g.e_next_in[e]) np++;
+            g.row_meta[r] = (uint32_t)g.code[n] | (g.out_head[n] == NONE ? 4u : 0u) | (np << META_NP);
+        }
+        uint32_t tot;
+        const uint32_t pre = block_excl_sum<NT>(np, s_scan, &tot);
+        if (r < V) {
+            uint32_t o = carry + pre;
+            g.row_pred_off[r] = o;
+            for (uint32_t e = g.in_head[g.rank2node[r]]; e != NONE; e = g.e_next_in[e], o++) { g.pred_rank[o] = g.node2rank[g.e_from[e]]; g.pred_w[o] = g.e_w[e]; }
+        }
+        carry += tot;
+    }
+    if (t == 0) g.row_pred_off[V] = carry;
+    __syncthreads();
+}
+
+struct Shared { uint32_t item, V, E, fail; int best; unsigned long long key; };
+
+// DP of sequence s[0, L) against the V rows; returns through *bi / *bj the end cell (bi = 0: none - kSW without a cell above 0)
+template <int NT, int CPL>
+__device__ void dp_rows(const G& g, int32_t* H, const uint32_t V, const uint8_t* s, const uint32_t L, const MArgs& a, Shared& sh, int* s_wtot,
+                        uint32_t* bi_out, uint32_t* bj_out) {
+    constexpr int NEG2 = -(1 << 30);   // identity of the scans (below every real and every NEG-derived value)
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    const uint32_t W = L + 1, j0 = t * CPL;
+    const int32_t m = a.m, n = a.n, gp = a.g;
+    const int type = a.type;
+    uint32_t sq[(CPL + 15) / 16];   // s[j - 1] of the lane's columns, 2 bits each
+#pragma unroll
+    for (int q = 0; q < (CPL + 15) / 16; q++) sq[q] = 0;
+#pragma unroll
+    for (int k = 0; k < CPL; k++) { const uint32_t j = j0 + k; if (j >= 1 && j <= L) sq[k >> 4] |= (uint32_t)s[j - 1] << (2 * (k & 15)); }
+#pragma unroll
+    for (int k = 0; k < CPL; k++) { const uint32_t j = j0 + k; if (j <= L) H[j] = type == MT_NW ? (int32_t)j * gp : 0; }
+    __syncthreads();
+    int32_t bv = type == MT_SW ? 0 : NEG;
+    uint32_t bi = 0, bj = 0;
+    uint32_t meta = g.row_meta[0], off = g.row_pred_off[0];
+    for (uint32_t i = 1; i <= V; i++) {
+        const uint32_t cmeta = meta, coff = off;
+        if (i < V) { meta = g.row_meta[i]; off = g.row_pred_off[i]; }   // the next row's record, while this one runs
+        const uint32_t np = cmeta >> META_NP, code = cmeta & 3u;
+        const bool sink = (cmeta & 4u) != 0;
+        int32_t x[CPL];
+#pragma unroll
+        for (int k = 0; k < CPL; k++) x[k] = NEG;
+        const uint32_t npp = np ? np : 1u;
+        for (uint32_t p = 0; p < npp; p++) {
+            const uint32_t prow = np ? g.pred_rank[coff + p] + 1u : 0u;
+            const int32_t* hp = H + (size_t)prow * W;
+            int32_t left = j0 >= 1 && j0 <= W ? hp[j0 - 1] : NEG;
+#pragma unroll
+            for (int k = 0; k < CPL; k++) {
+                const uint32_t j = j0 + k;
+                if (j <= L) {
+                    const int32_t v = hp[j];
+                    const int32_t sg = ((sq[k >> 4] >> (2 * (k & 15))) & 3u) == code ? m : n;
+                    x[k] = max(x[k], max(left + sg, v + gp));
+                    left = v;
+                }
+            }
+        }
+        if (type != MT_NW && j0 == 0) x[0] = 0;   // H[r][0] of kSW / kOV (kNW: max over P(r) of H[p][0] + g, which the fold above gave)
+        // horizontal: H[j] = j g + max over k <= j of (x[k] - k g)
+#pragma unroll
+        for (int k = 0; k < CPL; k++) { x[k] -= (int32_t)(j0 + k) * gp; if (k) x[k] = max(x[k], x[k - 1]); }
+        const int incl = wave_scan_max(x[CPL - 1]);
+        int carry = wave_shift_up1(incl, NEG2);
+        if (NT > 64) {
+            if (lane == 63) s_wtot[w] = incl;
+            __syncthreads();
+            for (uint32_t q = 0; q < w; q++) carry = max(carry, s_wtot[q]);
+        }
+        int32_t* row = H + (size_t)i * W;
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            const uint32_t j = j0 + k;
+            int32_t h = max(x[k], carry) + (int32_t)j * gp;
+            if (type == MT_SW) h = max(h, 0);
+            if (j <= L) {
+                row[j] = h;
+                const bool cand = j >= 1 && (type == MT_SW || (type == MT_NW ? sink && j == L : sink || j == L));
+                if (cand && h > bv) { bv = h; bi = i; bj = j; }
+            }
+        }
+        __syncthreads();   // the row is visible to every lane before a later row reads it (and s_wtot is free again)
+    }
+    if (t == 0) { sh.best = type == MT_SW ? 0 : NEG; sh.key = ~0ull; }
+    __syncthreads();
+    if (bi) atomicMax(&sh.best, bv);
+    __syncthreads();
+    if (bi && bv == sh.best) atomicMin(&sh.key, ((unsigned long long)bi << 32) | bj);
+    __syncthreads();
+    const unsigned long long key = sh.key;
+    *bi_out = key == ~0ull ? 0u : (uint32_t)(key >> 32);
+    *bj_out = key == ~0ull ? 0u : (uint32_t)key;
+    __syncthreads();
+}
+
+// spoa's traceback from (i, j); thread 0. Leaves the pairs REVERSED in aln_node / aln_pos (add_alignment's layout) and returns their number,
+// 0 when no pair holds a sequence position (the alignment counts as empty).
+__device__ uint32_t traceback(G& g, const int32_t* H, const uint8_t* s, const uint32_t L, uint32_t i, uint32_t j, const MArgs& a) {
+    const uint32_t W = L + 1;
+    uint32_t na = 0;
+    bool anypos = false;
+    for (;;) {
+        const int32_t h = H[(size_t)i * W + j];
+        if (a.type == MT_SW ? h == 0 : a.type == MT_NW ? (i == 0 && j == 0) : (i == 0 || j == 0)) break;
+        uint32_t pi = i, pj = j, np = 0, off = 0, code = 0;
+        bool ok = false;
+        if (i != 0) { const uint32_t meta = g.row_meta[i - 1]; np = meta >> META_NP; off = g.row_pred_off[i - 1]; code = meta & 3u; }
+        const uint32_t npp = np ? np : 1u;
+        if (i != 0 && j != 0) {
+            const int32_t sg = s[j - 1] == code ? a.m : a.n;
+            for (uint32_t p = 0; p < npp && !ok; p++) {
+                const uint32_t prow = np ? g.pred_rank[off + p] + 1u : 0u;
+                if (h == H[(size_t)prow * W + j - 1] + sg) { pi = prow; pj = j - 1; ok = true; }
+            }
+        }
+        if (!ok && i != 0)
+            for (uint32_t p = 0; p < npp && !ok; p++) {
+                const uint32_t prow = np ? g.pred_rank[off + p] + 1u : 0u;
+                if (h == H[(size_t)prow * W + j] + a.g) { pi = prow; pj = j; ok = true; }
+            }
+        if (!ok) { if (j == 0) break; pj = j - 1; }   // horizontal (j = 0 cannot happen on a consistent matrix)
+        g.aln_node[na] = pi != i ? (int32_t)g.rank2node[i - 1] : -1;
+        g.aln_pos[na] = pj != j ? (int32_t)(j - 1) : -1;
+        anypos = anypos || pj != j;
+        na++;
+        i = pi; j = pj;
+    }
+    return anypos ? na : 0u;
+}
+
+template <int NT, int CPL>
+__device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Shared& sh, int* s_wtot, uint32_t* s_scan) {
+    const uint32_t t = threadIdx.x;
+    const MSet S = a.sets[set];
+    G g; uint32_t *path, *colref;
+    const uint64_t pools = carve_pools(slot, S.sum_len, S.nseq, S.lmax, &g, &path, &colref);
+    if (pools > a.slot_bytes) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
+    int32_t* H = (int32_t*)(slot + pools);
+    const uint64_t hcap = (a.slot_bytes - pools) / 4;
+    uint32_t V = 0, E = 0, non_empty = 0;
+    unsigned long long cells = 0;
+    for (uint32_t k = 0; k < S.nseq; k++) {
+        const uint64_t b = a.soff[S.seq_begin + k];
+        const uint32_t L = (uint32_t)(a.soff[S.seq_begin + k + 1] - b);
+        if (L == 0) continue;
+        const uint8_t* s = a.codes + b;
+        non_empty++;
+        uint32_t na = 0;
+        if (V) {
+            if ((uint64_t)(V + 1) * (L + 1) > hcap) { if (t == 0) { a.status[set] = MS_H_OVERFLOW; a.vseen[set] = V; } return; }
+            cells += (unsigned long long)V * L;
+            uint32_t bi, bj;
+            dp_rows<NT, CPL>(g, H, V, s, L, a, sh, s_wtot, &bi, &bj);
+            if (t == 0 && bi) na = traceback(g, H, s, L, bi, bj, a);
+        }
+        if (t == 0) {
+            uint32_t v = V, e = E;
+            const bool ok = add_alignment(g, v, e, na, s, L, path, colref);
+            sh.V = v; sh.E = e; sh.fail = !ok;
+        }
+        __syncthreads();
+        V = sh.V; E = sh.E;
+        if (sh.fail) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
+        order_rows<NT>(g, V, s_scan);
+    }
+    if (t < 64) {
+        const uint32_t len = non_empty ? consensus_wave(g, V, a.cns + S.cns_off) : 0u;
+        if (t == 0) { a.cns_len[set] = len; a.cells[set] = cells; a.status[set] = MS_OK; }
+    }
+    __syncthreads();   // the slot is free for the next set
+}
+
+template <int NT, int CPL>
+__global__ __launch_bounds__(NT) void k_poa_modes(MArgs a) {
+    __shared__ Shared sh;
+    __shared__ int s_wtot[NT / 64];
+    __shared__ uint32_t s_scan[NT / 64];
+    uint8_t* slot = a.ws + (size_t)blockIdx.x * a.slot_bytes;
+    for (;;) {
+        if (threadIdx.x == 0) sh.item = atomicAdd(a.counter, 1u);
+        __syncthreads();
+        const uint32_t q = sh.item;
+        __syncthreads();
+        if (q >= a.n_items) return;
+        run_set<NT, CPL>(a, a.order[q], slot, sh, s_wtot, s_scan);
+    }
+}
+
+// the instances: workgroup lanes x columns per lane; a set goes to the first whose NT x CPL columns hold its longest sequence + 1
+struct Inst { int nt, cpl; const void* fn; };
+const Inst kInst[] = {
+    {64, 16, (const void*)k_poa_modes<64, 16>},
+    {256, 16, (const void*)k_poa_modes<256, 16>},
+    {256, 32, (const void*)k_poa_modes<256, 32>},
+    {1024, 32, (const void*)k_poa_modes<1024, 32>},
+};
+constexpr int N_INST = sizeof(kInst) / sizeof(kInst[0]);
+constexpr uint32_t MAX_LEN = 1024 * 32 - 1;
+
+void launch(int inst, uint32_t blocks, const MArgs& a, hipStream_t s) {
+    switch (inst) {
+        case 0: k_poa_modes<64, 16><<<blocks, 64, 0, s>>>(a); break;
+        case 1: k_poa_modes<256, 16><<<blocks, 256, 0, s>>>(a); break;
+        case 2: k_poa_modes<256, 32><<<blocks, 256, 0, s>>>(a); break;
+        default: k_poa_modes<1024, 32><<<blocks, 1024, 0, s>>>(a); break;
+    }
+}
+
+template <class T> struct Buf {   // device buffer of one call
+    T* p = nullptr;
+    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)); }
+    ~Buf() { if (p) (void)hipFree(p); }
+};
+
+}  // namespace
+
+#define MCHK(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(e_); return -1; } } while (0)
+
+int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModesOut& o, std::string& err) {
+    const uint32_t ns = a.n_sets;
+    const uint64_t nseq = a.set_off[ns], nb = a.seq_off[nseq];
+    std::vector<MSet> sets(ns);
+    std::vector<uint64_t> cns_off((size_t)ns + 1, 0);
+    o = PoaModesOut();
+    for (uint32_t i = 0; i < ns; i++) {
+        MSet& S = sets[i];
+        S.seq_begin = a.set_off[i]; S.nseq = (uint32_t)(a.set_off[i + 1] - a.set_off[i]); S.sum_len = 0; S.lmax = 0;
+        for (uint64_t k = a.set_off[i]; k < a.set_off[i + 1]; k++) {
+            const uint64_t L = a.seq_off[k + 1] - a.seq_off[k];
+            if (L > MAX_LEN) { err = "hx_poa_sequences_mode: set " + std::to_string(i) + " holds a sequence of " + std::to_string(L) + " bases, longer than " + std::to_string(MAX_LEN) + " (the longest the general POA path takes)"; return -1; }
+            S.sum_len += L; S.lmax = std::max(S.lmax, (uint32_t)L);
+            o.seq_bases += L; o.n_aligned += L != 0;
+        }
+        if (S.sum_len > MAX_SET_BASES) { err = "hx_poa_sequences_mode: set " + std::to_string(i) + " holds " + std::to_string(S.sum_len) + " bases in all, more than the " + std::to_string(MAX_SET_BASES) + " nodes a graph can have"; return -1; }
+        S.cns_off = cns_off[i]; cns_off[i + 1] = cns_off[i] + S.sum_len;   // (a consensus has at most one base per node)
+    }
+    std::vector<uint8_t> codes(std::max<uint64_t>(1, nb));
+    for (uint64_t k = 0; k < nb; k++) { const char c = a.bases[k]; codes[k] = c == 'C' || c == 'c' ? 1 : c == 'G' || c == 'g' ? 2 : c == 'T' || c == 't' ? 3 : 0; }
+    int dev = 0, n_cu = 0;
+    MCHK(hipGetDevice(&dev));
+    MCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    Buf<MSet> d_sets; Buf<uint8_t> d_codes; Buf<uint64_t> d_soff; Buf<uint32_t> d_order, d_counter, d_status, d_vseen, d_cns_len; Buf<unsigned long long> d_cells; Buf<char> d_cns;
+    MCHK(d_sets.alloc(ns)); MCHK(d_codes.alloc(codes.size())); MCHK(d_soff.alloc(nseq + 1)); MCHK(d_order.alloc(ns)); MCHK(d_counter.alloc(N_INST));
+    MCHK(d_status.alloc(ns)); MCHK(d_vseen.alloc(ns)); MCHK(d_cns_len.alloc(ns)); MCHK(d_cells.alloc(ns)); MCHK(d_cns.alloc(cns_off[ns]));
+    MCHK(hipMemcpyAsync(d_sets.p, sets.data(), ns * sizeof(MSet), hipMemcpyHostToDevice, s));
+    MCHK(hipMemcpyAsync(d_codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice, s));
+    MCHK(hipMemcpyAsync(d_soff.p, a.seq_off, (nseq + 1) * 8, hipMemcpyHostToDevice, s));
+    MCHK(hipMemsetAsync(d_cns_len.p, 0, std::max<size_t>(1, ns) * 4, s));
+    MCHK(hipMemsetAsync(d_cells.p, 0, std::max<size_t>(1, ns) * 8, s));
+
+    // H is sized from an estimate of the graph's final size (noisy copies add about a tenth of their length each); a set that outgrows its
+    // slot comes back and is rerun with twice the room (or the room for what it had when it stopped, doubled), the worst case at most
+    std::vector<uint64_t> vest(ns);
+    std::vector<uint32_t> todo;
+    for (uint32_t i = 0; i < ns; i++) { vest[i] = std::min<uint64_t>(sets[i].sum_len, sets[i].lmax + sets[i].sum_len / 8 + 64); if (sets[i].sum_len) todo.push_back(i); }
+    auto need = [&](uint32_t i) { const MSet& S = sets[i]; return carve_pools(nullptr, S.sum_len, S.nseq, S.lmax, nullptr, nullptr, nullptr) + al256((vest[i] + 1) * (uint64_t)(S.lmax + 1) * 4); };
+    auto inst_of = [&](uint32_t i) { int k = 0; while ((uint64_t)kInst[k].nt * kInst[k].cpl < (uint64_t)sets[i].lmax + 1) k++; return k; };
+    uint64_t budget;
+    {
+        size_t fr = 0, tot = 0;
+        MCHK(hipMemGetInfo(&fr, &tot));
+        budget = a.workspace_gb > 0 ? (uint64_t)(a.workspace_gb * 1e9) : (uint64_t)((double)(fr + ws.cap) * 0.4);
+    }
+    hipEvent_t e0, e1;
+    MCHK(hipEventCreate(&e0)); MCHK(hipEventCreate(&e1));
+    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
+    std::vector<uint32_t> status(ns), vseen(ns);
+    for (bool first = true; !todo.empty(); first = false) {
+        // plan the round: per instance, its sets costliest first, one slot size (the largest need), as many slots as are resident and fit the budget
+        std::vector<std::vector<uint32_t>> by(N_INST);
+        for (uint32_t i : todo) by[inst_of(i)].push_back(i);
+        std::vector<uint64_t> slot(N_INST, 0), base(N_INST, 0);
+        std::vector<uint32_t> nslots(N_INST, 0);
+        std::vector<uint32_t> order;
+        uint64_t total = 0;
+        for (int k = 0; k < N_INST; k++) {
+            auto& v = by[k];
+            if (v.empty()) continue;
+            std::stable_sort(v.begin(), v.end(), [&](uint32_t x, uint32_t y) { return sets[x].sum_len * sets[x].lmax > sets[y].sum_len * sets[y].lmax; });
+            uint64_t sb = 0, pmax = 0;
+            uint32_t big = v[0];
+            for (uint32_t i : v) {
+                const uint64_t nd = need(i);
+                if (nd > sb) { sb = nd; big = i; }
+                pmax = std::max(pmax, carve_pools(nullptr, sets[i].sum_len, sets[i].nseq, sets[i].lmax, nullptr, nullptr, nullptr));
+            }
+            if (first && a.slot_kb_cap) sb = std::max(pmax, std::min<uint64_t>(sb, (uint64_t)a.slot_kb_cap << 10));   // (test switch: forces the overflow and rerun)
+            sb = al256(sb);
+            int occ = 0;
+            MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kInst[k].fn, kInst[k].nt, 0));
+            const uint64_t resident = (uint64_t)std::max(1, occ) * (uint64_t)n_cu;
+            const uint64_t fit = budget / sb;
+            if (fit == 0) { err = "hx_poa_sequences_mode: set " + std::to_string(big) + " needs " + std::to_string(sb) + " bytes of workspace, more than the budget of " + std::to_string(budget) + " (option poa_workspace_gb)"; return -1; }
+            slot[k] = sb; nslots[k] = (uint32_t)std::min<uint64_t>({(uint64_t)v.size(), resident, fit});
+            base[k] = order.size();
+            order.insert(order.end(), v.begin(), v.end());
+            total = std::max(total, nslots[k] * sb);   // (the instances run one after the other on the stream: they share the workspace)
+        }
+        if (total > ws.cap) {
+            MCHK(hipStreamSynchronize(s));
+            ws.release();
+            const hipError_t e = hipMalloc(&ws.p, total);
+            if (e != hipSuccess) { ws.p = nullptr; err = "hx_poa_sequences_mode: the workspace of " + std::to_string(total) + " bytes could not be allocated: " + hipGetErrorString(e); return -1; }
+            ws.cap = total;
+        }
+        MCHK(hipMemcpyAsync(d_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, s));
+        MCHK(hipMemsetAsync(d_counter.p, 0, N_INST * 4, s));
+        MCHK(hipMemsetAsync(d_status.p, 0xff, std::max<size_t>(1, ns) * 4, s));
+        MCHK(hipEventRecord(e0, s));
+        for (int k = 0; k < N_INST; k++) {
+            if (by[k].empty()) continue;
+            MArgs q{d_sets.p, d_order.p + base[k], (uint32_t)by[k].size(), d_counter.p + k, d_codes.p, d_soff.p, (uint8_t*)ws.p, slot[k],
+                    a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p};
+            launch(k, nslots[k], q, s);
+            MCHK(hipGetLastError());
+            o.launches++;
+            if (a.debug) fprintf(stderr, "[hx] POA modes: %zu sets on %u workgroups of %d lanes x %d columns, slots of %.1f MB\n", by[k].size(), nslots[k], kInst[k].nt, kInst[k].cpl, slot[k] / 1e6);
+        }
+        MCHK(hipEventRecord(e1, s));
+        MCHK(hipEventSynchronize(e1));
+        float ms = 0;
+        MCHK(hipEventElapsedTime(&ms, e0, e1));
+        o.kernel_ms += ms;
+        MCHK(hipMemcpy(status.data(), d_status.p, ns * 4, hipMemcpyDeviceToHost));
+        MCHK(hipMemcpy(vseen.data(), d_vseen.p, ns * 4, hipMemcpyDeviceToHost));
+        std::vector<uint32_t> next;
+        for (uint32_t i : todo) {
+            if (status[i] == MS_OK) continue;
+            const bool capped = first && a.slot_kb_cap;   // (a capped slot can be short of even the worst case)
+            if (status[i] != MS_H_OVERFLOW || (vest[i] >= sets[i].sum_len && !capped)) { err = "hx_poa_sequences_mode: set " + std::to_string(i) + " failed on the device (status " + std::to_string((int)status[i]) + ")"; return -1; }
+            vest[i] = std::min<uint64_t>(sets[i].sum_len, std::max<uint64_t>(2 * vest[i], 2 * (uint64_t)vseen[i] + 64));
+            next.push_back(i);
+            o.retried++;
+        }
+        todo.swap(next);
+    }
+    std::vector<uint32_t> len(ns);
+    std::vector<unsigned long long> cells(ns);
+    std::vector<char> cns(std::max<uint64_t>(1, cns_off[ns]));
+    MCHK(hipMemcpy(len.data(), d_cns_len.p, ns * 4, hipMemcpyDeviceToHost));
+    MCHK(hipMemcpy(cells.data(), d_cells.p, ns * 8, hipMemcpyDeviceToHost));
+    MCHK(hipMemcpy(cns.data(), d_cns.p, cns_off[ns], hipMemcpyDeviceToHost));
+    o.cns_off.assign((size_t)ns + 1, 0);
+    for (uint32_t i = 0; i < ns; i++) {
+        o.cns.append(cns.data() + cns_off[i], len[i]);
+        o.cns_off[i + 1] = o.cns.size();
+        o.cells += cells[i];
+    }
+    return 0;
+}
+
+}  // namespace hxk

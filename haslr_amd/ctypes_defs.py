@@ -60,6 +60,13 @@ class PoaParams(C.Structure):
     _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap", C.c_int32)]
 
 
+POA_TYPES = {"sw": 0, "nw": 1, "ov": 2}   # hx_poa_type: spoa's AlignmentType values
+
+
+class PoaModeParams(C.Structure):
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap", C.c_int32), ("type", C.c_int32)]
+
+
 class Backend(C.Structure):
     _fields_ = [("ctx", C.c_void_p)] + [(k, C.c_void_p) for k in
                                         ("chain_reads", "edge_support", "edge_coords", "poa_batch", "free_chain",

@@ -56,7 +56,9 @@ void hx_ctx_destroy(hx_ctx*);
  *                    _max / _topk / _cols, poa_wide_members, poa_wave_max, poa_ring_kb, poa_balance, poa_balance_pct, poa_balance_lanes, poa_streams,
  *                    poa_wide_delay_us, poa_prune_lanes, poa_prune_shared, poa_prune_lazy, poa_order_by_cells, poa_pass_lanes, poa_chain_ms, poa_chain_pct, poa_big_first,
  *                    poa_slots_by_work, poa_bucket_half_octaves, poa_own_bucket_first, poa_resident_first, poa_far_shift, poa_scratch_warm) and test switches that force rare paths (poa_poll_limit, poa_max_indeg, poa_node_est_pct,
- *                    poa_far_rows, poa_ring_zero, poa_slots, poa_slots_pct, poa_batches, poa_force_cm, poa_no_xcd_map, coords_lds_supp).
+ *                    poa_far_rows, poa_ring_zero, poa_slots, poa_slots_pct, poa_batches, poa_force_cm, poa_no_xcd_map, coords_lds_supp), and two of the
+ *                    general POA path (hx_poa_sequences_mode): poa_general (1: HX_POA_NW runs the general path too) and poa_modes_slot_kb (cap of
+ *                    its first round of workspace slots, forcing the rerun of sets in larger ones).
  *                    Results never depend on any of them. */
 int hx_set_option(hx_ctx*, const char* name, const char* value);
 int hx_get_option(const hx_ctx*, const char* name, double* value);
@@ -86,6 +88,12 @@ int hx_poa_batch(hx_ctx*, const hx_poa_params*, hx_cns_out* out);
  *                     entry include/spoa_hx.hpp (the spoa.hpp-shaped C++ header over this library) calls. */
 int hx_poa_supports(hx_ctx*, const hx_coords_out* sup, const hx_poa_params*, hx_cns_out* out);
 int hx_poa_sequences(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_params*, hx_cns_out* out);
+/*   hx_poa_sequences_mode  hx_poa_sequences with spoa's alignment type: HX_POA_NW is hx_poa_sequences itself (the tuned global path; option
+ *                     poa_general sends it through the general path instead, same results); HX_POA_SW (local) and HX_POA_OV (overlap) run the
+ *                     general path (kernels/poa_modes.hip, DESIGN.md "General POA path"): one workgroup per set, the full int32 score matrix,
+ *                     sequences of up to 32767 bases, sets of up to 2^21 - 2 bases in all. gap >= 0 or an unknown type: error. An alignment that
+ *                     holds no sequence position counts as empty (spoa leaves that case undefined): the sequence becomes a new chain. */
+int hx_poa_sequences_mode(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_mode_params*, hx_cns_out* out);
 void hx_free_chain(hx_ctx*, hx_chain_out*);
 void hx_free_edges(hx_ctx*, hx_edges_out*);
 void hx_free_coords(hx_ctx*, hx_coords_out*);

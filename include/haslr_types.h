@@ -130,6 +130,13 @@ typedef struct {
     int32_t match, mismatch, gap;
 } hx_poa_params;
 
+/* POA alignment type and scoring of hx_poa_sequences_mode: spoa's AlignmentType values (kSW local, kNW global, kOV overlap), linear gap. */
+typedef enum { HX_POA_SW = 0, HX_POA_NW = 1, HX_POA_OV = 2 } hx_poa_type;
+typedef struct {
+    int32_t match, mismatch, gap;
+    int32_t type; /* hx_poa_type */
+} hx_poa_mode_params;
+
 #ifdef __cplusplus
 }
 #endif

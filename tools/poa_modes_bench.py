@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Throughput of the general POA path (hx_poa_sequences_mode, kernels/poa_modes.hip) on two seeded workloads, in one process:
+  (a) noisy copies: 8-40 copies of 200-4 000-base templates (8 % insertions, 3 % deletions, 2 % substitutions), run as kSW with random
+      0-300-base flanks on both sides of every copy, and as kNW / kOV without them
+  (b) tiled fragments: 20 fragments of 1-3 kb drawn at random from 5 kb templates (same error model), kOV
+For every mode: sets, cells (sum of V x L, the full matrices spoa computes), kernel time (hipEvents; warmed up, median and spread of
+--repeats runs), GCUPS; for context the tuned kNW path on the same sets, and the CPU restatement (tests/poa_modes_ref.cpp) on 16 threads over
+a sample of the sets (GCUPS of the sample). Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+
+def text(a):
+    return ACGT[a].tobytes().decode()
+
+
+def noisy(rng, t):
+    """PacBio-like copy: 3 % deletions, 2 % substitutions, 8 % insertions (a random base after the position)"""
+    n = len(t)
+    u = rng.random(n)
+    base = np.where((u >= 0.03) & (u < 0.05), rng.integers(0, 4, n), t)
+    ins = rng.random(n) < 0.08
+    cnt = (u >= 0.03).astype(np.int64) + ins
+    out = np.repeat(base, cnt)
+    pos = np.cumsum(cnt)[ins & (cnt == 2)] - 1
+    out[pos] = rng.integers(0, 4, len(pos))
+    return out
+
+
+def workload_a(rng, n_sets, flanks):
+    sets = []
+    for _ in range(n_sets):
+        t = rng.integers(0, 4, int(rng.integers(200, 4001)))
+        st = []
+        for _ in range(int(rng.integers(8, 41))):
+            c = noisy(rng, t)
+            if flanks:
+                c = np.concatenate([rng.integers(0, 4, int(rng.integers(0, 301))), c, rng.integers(0, 4, int(rng.integers(0, 301)))])
+            st.append(text(c))
+        sets.append(st)
+    return sets
+
+
+def workload_b(rng, n_sets):
+    sets = []
+    for _ in range(n_sets):
+        t = rng.integers(0, 4, 5000)
+        st = []
+        for _ in range(20):
+            L = int(rng.integers(1000, 3001))
+            b = int(rng.integers(0, 5000 - L + 1))
+            st.append(text(noisy(rng, t[b:b + L])))
+        sets.append(st)
+    return sets
+
+
+def gpu_time(ctx, fn, repeats):
+    fn()   # warm-up (workspace allocation, code objects)
+    ms = []
+    for _ in range(repeats):
+        ctx.timing_reset()
+        fn()
+        ms.append(ctx.timing()["poa"]["ms"])
+    return ms
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sets-a", type=int, default=256)
+    ap.add_argument("--sets-b", type=int, default=256)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--cpu-sample", type=int, default=32, help="sets of each workload the CPU restatement runs (16 threads)")
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    from haslr_amd import hip
+    import pmrlib
+    rng = np.random.default_rng(a.seed)
+    loads = {"a_sw": ("sw", workload_a(rng, a.sets_a, True)), "a_nw": ("nw", workload_a(rng, a.sets_a, False))}
+    loads["a_ov"] = ("ov", loads["a_nw"][1])
+    loads["b_ov"] = ("ov", workload_b(rng, a.sets_b))
+    ctx = hip.HipContext(0)
+    res = {"tool": "poa_modes_bench", "seed": a.seed, "repeats": a.repeats}
+    with tempfile.TemporaryDirectory() as d:
+        ref = pmrlib.ModesRef(d)
+        for name, (mode, sets) in loads.items():
+            r = {"mode": mode, "sets": len(sets)}
+            for path, opts in (("general", {"poa_general": 1}), ("tuned_nw", {})):
+                if path == "tuned_nw" and mode != "nw":
+                    continue
+                with ctx.options(**opts):
+                    cells = ctx.poa_sequences_mode(sets, mode, stats=True)[1]["dp_cells"]
+                    ms = gpu_time(ctx, lambda: ctx.poa_sequences_mode(sets, mode), a.repeats)
+                med = float(np.median(ms))
+                r[path] = {"cells": int(cells), "kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
+                           "gcups": round(cells / med / 1e6, 2)}
+            sample = sets[:a.cpu_sample]
+            t0 = time.perf_counter()
+            with ThreadPoolExecutor(16) as ex:
+                out = list(ex.map(lambda st: ref.consensus_cells(st, mode), sample))
+            dt = time.perf_counter() - t0
+            sc = sum(c for _, c in out)
+            r["cpu_restatement_16t"] = {"sets": len(sample), "cells": int(sc), "s": round(dt, 2), "gcups": round(sc / dt / 1e9, 3)}
+            got = ctx.poa_sequences_mode(sample, mode)
+            r["sample_equal"] = got == [c for c, _ in out]
+            res[name] = r
+    ctx.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
