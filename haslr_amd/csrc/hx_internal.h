@@ -1,0 +1,256 @@
+// hx_internal.h - what the units of the C-ABI share (hx_api.hip, hx_poa_plan.hip, hx_poa.hip, hx_group.hip): the error helpers, device
+// buffers, the POA workspace arena, the options of a context and the context itself.
+#pragma once
+#include <atomic>
+#include <thread>
+#include <memory>
+#include <chrono>
+#include <cmath>
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <numeric>
+#include <string>
+#include <vector>
+#include <array>
+#include <mutex>
+
+#include "../../include/haslr_hip.h"
+#include "host/haslr_host.h"
+#include "kernels/kernels.h"
+#include "kernels/poa_modes.h"
+
+namespace hxi {
+
+extern thread_local std::string g_err;   // what hx_last_error returns (hx_api.hip)
+int fail(const std::string& m);          // sets it, returns -1
+
+#define HIPCHK(expr)                                                                                          \
+    do {                                                                                                      \
+        hipError_t _e = (expr);                                                                               \
+        if (_e != hipSuccess) return hxi::fail(std::string(#expr) + ": " + hipGetErrorString(_e));            \
+    } while (0)
+
+template <class T>
+struct DV {   // device vector (capacity grows, never shrinks)
+    T* p = nullptr;
+    size_t cap = 0;
+    hipError_t reserve(size_t n) {
+        if (n <= cap && p) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
+        if (e == hipSuccess) cap = std::max<size_t>(n, 1);
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    ~DV() { release(); }
+};
+
+struct DevSideBuf {
+    DV<uint32_t> qs, qe, ts, te, skf, skb;
+    DV<uint8_t> rev;
+    DV<uint64_t> cb, ce;
+    hipError_t reserve(size_t n) {
+        hipError_t e;
+        if ((e = qs.reserve(n)) || (e = qe.reserve(n)) || (e = ts.reserve(n)) || (e = te.reserve(n)) || (e = skf.reserve(n)) ||
+            (e = skb.reserve(n)) || (e = rev.reserve(n)) || (e = cb.reserve(n)) || (e = ce.reserve(n))) return e;
+        return hipSuccess;
+    }
+    DevSide view() { return DevSide{qs.p, qe.p, ts.p, te.p, rev.p, cb.p, ce.p, skf.p, skb.p}; }
+};
+
+struct RecBuf {
+    DV<uint64_t> key;
+    DV<uint32_t> lr, ch, ct;
+    DevSideBuf head, tail;
+    hipError_t reserve(size_t n) {
+        hipError_t e;
+        if ((e = key.reserve(n)) || (e = lr.reserve(n)) || (e = ch.reserve(n)) || (e = ct.reserve(n)) || (e = head.reserve(n)) || (e = tail.reserve(n))) return e;
+        return hipSuccess;
+    }
+    hxk::EdgeRecs view() { return hxk::EdgeRecs{key.p, lr.p, ch.p, ct.p, head.view(), tail.view()}; }
+};
+
+template <class T> T* host_copy(const T* d, size_t n) {
+    T* h = (T*)malloc(std::max<size_t>(1, n) * sizeof(T));
+    if (n) (void)hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost);
+    return h;
+}
+
+struct Timer {
+    hipEvent_t a = nullptr, b = nullptr;
+    double ms[4] = {0, 0, 0, 0};
+    uint64_t launches[4] = {0, 0, 0, 0};
+};
+
+// The POA workspace is ONE device allocation (round 6): an arena that every pool of a batch is carved out of. Forty pools used to be forty synchronous
+// hipMalloc calls inside the first consensus call of a context - seconds of a one-shot run at 140 Mb (215 GB), against a 0.5 s hot path. The arena can be
+// reserved ahead of the first call (hx_poa_reserve: the CLI does it on a thread of its own while the text inputs are parsed), grows when a batch needs
+// more (never shrinks), and is carved anew for every batch: nothing in it outlives a batch.
+template <class T> struct AP { T* p = nullptr; size_t off = 0; };   // a pool: pointer into the arena, byte offset of the current carving
+struct PoaPoolBufs {
+    AP<uint8_t> code, n_aligned, mark, check, row_code, row_sink, seq;
+    AP<uint32_t> aligned, in_head, in_tail, out_head, out_tail, rank2node, node2rank, stack, row_pred_off, pred_rank, e_from, e_to, e_next_in, e_next_out;
+    AP<int32_t> score, pred, e_w, aln_node, aln_pos, H, pred_w;
+    AP<uint32_t> row_meta, row_pred0, row_pred1;
+    AP<uint4> nrec, nrec2;
+    AP<uint8_t> dir, dirw; AP<uint32_t> wslot;
+    AP<unsigned long long> mbox; AP<int32_t> sinkbuf; AP<uint32_t> csync; AP<uint16_t> row_al;   // cluster mode (edges shared by several workgroups)
+    AP<char> cns;                                                                                  // consensus strings as the kernels leave them (capacity = node estimate per edge)
+};
+struct PoaArena {
+    uint8_t* p = nullptr;
+    size_t cap = 0;
+    uint64_t n_alloc = 0;       // device allocations made for it so far
+    double alloc_ms = 0;        // ... and the wall time they took
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    hipError_t ensure(size_t bytes) {   // at least `bytes`; the contents are not kept
+        if (bytes <= cap && p) return hipSuccess;
+        const auto t0 = std::chrono::steady_clock::now();
+        release();
+        const hipError_t e = hipMalloc((void**)&p, std::max<size_t>(bytes, 256));
+        if (e == hipSuccess) cap = std::max<size_t>(bytes, 256); else p = nullptr;
+        n_alloc++; alloc_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return e;
+    }
+    ~PoaArena() { release(); }
+};
+
+// ---- tuning and test switches of a context. They used to be HX_* environment variables read inside the library on every call; now they are
+// state of the context, set through hx_set_option (include/haslr_hip.h) - by the applications (the CLI and haslr_amd/hip.py copy the HX_*
+// variables of their environment in, once, when they create a context) and by the tests. Defaults in the table below; -1 = automatic.
+struct HxOptions {
+    int debug = 0;                 // progress and statistics of every consensus call on stderr
+    int prof = 0;                  // 1 / 2 / 3: how hx_poa_phase_cycles reads the phase words of a build with -DHX_DP_PROF / PROF2 / PROF3 (development)
+    double poa_workspace_gb = 0;   // cap of the POA workspace in GB (0: 90 % of the memory that was free at the context's first consensus call)
+    int poa_poll_limit = 1 << 24;  // polls before a wave gives up waiting for another member (testing: forces the unshared retry)
+    int poa_max_indeg = 16;        // in-degree the direction bytes hold (testing: forces the score-matrix retry earlier)
+    int poa_member_lanes = 256, poa_cluster_min = 2048, poa_cluster_max = -1, poa_cluster_topk = -1, poa_wide_members = -1, poa_cluster_cols = -1;
+    int poa_cols2_top = -1;        // the costliest shared edges of a call whose members take 2 columns per lane (twice the members, a shorter row): how many (-1: 4 in a few-edge call, else none)
+    int poa_node_est_pct = 100, poa_far_rows = -1;
+    int poa_far_shift = 3;         // rings of 4 kept rows (the many-edge regime): rows of H (rows read back from HBM) per edge = nodes >> this, + 256; an edge that needs more is redone with 4 x the room
+    int poa_wave_max = 512, poa_cols = -1, poa_ring_kb = -1, poa_ring_zero = 0;
+    int poa_balance = 1, poa_balance_pct = 125, poa_balance_lanes = 512;
+    int poa_slots_pct = 100, poa_slots = 0, poa_batches = 0, poa_force_cm = 0, poa_streams = 8, poa_wide_delay_us = 60;
+    int poa_prune = -1;            // exact score-bound pruning of the DP: -1 automatic (calls of thousands of edges), 0 never, else the threshold's percentage of the previous alignment's score per base
+    int poa_pass_lanes = -1;       // column passes: unshared multi-wave edges run in workgroups of this many lanes, their DP columns in windows taken one after the other (-1 automatic: by
+                                   // estimated chain length, where the rows are pruned; 0 never)
+    int poa_own_bucket_first = 1;  // a persistent workgroup takes the edges of its OWN need bucket before those of the smaller buckets it can also serve (0: whichever next edge has the longest chain, as until round 6 - see k_poa)
+    int poa_resident_first = 0;    // bit 0: the shared edges' launch of a many-edge call, bit 1: the wide persistent launches (512 lanes and more) - the next launch leaves when their workgroups have all begun (each adds itself to a word in host memory), not after a fixed delay. Measured at 140 Mb: the 37 workgroups of the 512-lane launch have all begun 40 us after it (the fixed delay is 60), and the one pass in five that took 550-620 ms was not about arrival at all (poa_own_bucket_first); 0 stays the default, the best pass is 0.459 against 0.480 s
+    int poa_chain_pct = 70;        // the automatic chain cap: the smallest one that is at least this percentage of the call's estimated wave-slot time over the waves resident (size_edges; 60 until the persistent workgroups took their own bucket first)
+    int poa_chain_ms = -1;         // ... the automatic choice: the narrowest workgroup whose estimated chain (size_edges: DP rows x what a row costs at that width and number of
+                                   // windows) stays below this many milliseconds; -1: the cap that balances the longest chain against the call's wave-slot time
+    int poa_prune_shared = 0;      // ... of the edges shared by several workgroups (round 6: their members take DP ATTEMPTS, not sequences, so a missed threshold is repeated by all of
+                                   // them): 0 never (the default), else the percentage. Measured at 12 Mb / 4.6 Mb with 95: 65 % of the wave-rows skipped, same consensus - and the longest
+                                   // chain 154 -> 207 ms / 106 -> 142 ms: in a pipeline of waves every row is live in SOME wave, which sets the pace of that row for all of them;
+                                   // what a skipped wave-row frees is issue slots, and a lone chain is not short of those
+    int poa_prune_lazy = 1;        // ... a wave that skipped a whole batch of rows polls for the next one rarely (0: like any wave)
+    int poa_prune_lanes = 128;     // ... in launches of workgroups of at least this many lanes (a one-wave workgroup has no block to skip)
+    int coords_lds_supp = -1;      // supports per edge the coordinate kernel sorts in LDS (testing: 0 sends every edge through the global scratch)
+    int poa_general = 0;           // hx_poa_sequences_mode with HX_POA_NW runs the general path (kernels/poa_modes.hip) instead of the tuned one: the cross-check of what the modes share with kNW
+    int poa_modes_slot_kb = 0;     // the general path's first round of slots holds at most this many KB (testing: forces the overflow and the rerun in a larger slot; 0 no cap)
+};
+
+template <class T>
+int up(DV<T>& d, const T* h, size_t n) {
+    HIPCHK(d.reserve(n));
+    if (n) HIPCHK(hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+}  // namespace hxi
+
+struct hx_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    // resident inputs
+    uint32_t n_contigs = 0, n_reads = 0;
+    uint64_t n_hits = 0, n_ops = 0;
+    hxi::DV<double> km;
+    hxi::DV<uint32_t> clen;
+    hxi::DV<uint8_t> cls;
+    hxi::DV<uint32_t> rlen;
+    hxi::DV<uint64_t> roff;
+    hxi::DV<uint8_t> packed;
+    hxi::DV<uint32_t> q_id, q_start, q_end, t_id, t_len, t_start, t_end, n_match, n_block, cg_ops;
+    hxi::DV<uint8_t> is_rev, mapq;
+    hxi::DV<uint64_t> cg_off, rho;
+    std::vector<uint32_t> h_rlen;
+    std::vector<uint64_t> h_rho;
+    uint32_t lr_begin = 0, lr_end = 0;
+    bool prefiltered = false;   // the resident records are the filtered set of an index.longread
+    hxi::DV<uint32_t> err;
+    // chain results
+    hxi::DV<uint32_t> c_hit, c_qs, c_qe, c_ts, c_te, c_nm, c_nb, c_skf, c_skb, c_cmp;
+    hxi::DV<uint64_t> c_cb, c_ce, aln_off, cmp_off;
+    uint64_t n_aln = 0, n_cmp = 0;
+    bool have_chain = false;
+    // edge records
+    hxi::RecBuf rec_un, rec;   // unsorted (emission order) and sorted
+    uint64_t n_rec_un = 0, n_rec = 0, n_edge = 0;
+    hxi::DV<uint64_t> edge_key, edge_off;
+    std::vector<uint64_t> h_edge_key, h_edge_off;
+    bool have_edges = false;
+    // coords results
+    hxi::DV<uint32_t> k_head_end, k_tail_beg, k_supp_lr, k_spos, k_epos;
+    std::vector<uint64_t> h_supp_off;
+    std::vector<uint32_t> h_supp_lr, h_spos, h_epos;
+    uint32_t n_sel = 0;
+    bool have_coords = false;
+    uint32_t dbg_slowest = 0;
+    std::vector<uint32_t> dbg_lmax, dbg_nseq;
+    std::vector<uint8_t> dbg_cls; uint32_t dbg_ring[11] = {};
+    std::vector<uint32_t> dbg_shape;   // per edge: lanes of its workgroup | column passes << 16 | members << 24
+    bool poa_no_dir = false;   // diagnostics: force the score-matrix traceback
+    int poa_block = 0;   // 0 = automatic (lanes per edge chosen from the gap length)
+    hipStream_t poa_streams[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint32_t* poa_started = nullptr;    // 16 words of mapped host memory: workgroups that have begun, per launch of a batch (kernels/poa.hip k_poa)
+    hipEvent_t poa_ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hxi::Timer tm;
+    // scratch of the chain / edge / coordinate operators lives as long as the context too (grows, never shrinks): no allocation, free or
+    // synchronisation for temporaries in a call once the sizes have been seen
+    hxk::Workspace ws;
+    struct {
+        hxi::DV<uint32_t> hit, qs, qe, ts, te, nm, nb, skf, skb, dp, cmp, naln, ncmp;
+        hxi::DV<uint64_t> cb, ce;
+        hxi::DV<int32_t> from;
+    } sc_chain;
+    struct { hxi::DV<uint32_t> npairs, perm, perm_tmp, flag; hxi::DV<uint64_t> pair_off, key_tmp, fscan; } sc_edges;
+    struct { hxi::DV<uint32_t> sel, nsupp, t_lr, t_sp, t_ep, best_list; hxi::DV<uint64_t> cap, out_off, b1, e1, b2, e2; hxi::DV<uint8_t> cur; } sc_coords;
+    // POA workspace lives as long as the context: allocating tens of GB per call costs more than the kernel
+    hxi::PoaPoolBufs poa_pools;
+    hxi::PoaArena poa_arena;
+    hxk::PoaModesWs poa_modes_ws;       // workspace of the general path (hx_poa_sequences_mode: kSW / kOV, and kNW under option poa_general)
+    std::mutex poa_arena_mu;            // hx_poa_reserve may run on a thread of its own beside the upload and the first stages
+    double poa_host_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // host wall time of the last consensus call: plan, workspace, enqueue, device wait, collect, finish, (unused), total
+    uint64_t poa_budget = 0;
+    hxi::DV<hxk::PoaEdge> poa_edges;
+    hxi::DV<hxk::PoaSeq> poa_seqs;
+    hxi::DV<uint32_t> poa_order, poa_len, poa_status, poa_counters, poa_btab;
+    hxi::DV<hxk::PoaSlot> poa_slots;
+    uint64_t poa_workspace_bytes = 0;   // largest POA workspace (pools) a call of this context has used
+    uint64_t poa_last_workspace_bytes = 0, poa_free_at_first_call = 0;   // ... the last call's; free device memory when the budget was taken
+    hxi::HxOptions opt;
+    hxi::DV<uint32_t> poa_gather;            // collection: (source offset lo / hi, destination offset lo / hi, length) of every finished edge's consensus
+    hxi::DV<char> poa_cns_dense;             // ... the strings side by side, as they are downloaded
+    hxi::DV<unsigned long long> poa_phase_d, poa_cells_d;
+    std::vector<unsigned long long> poa_phase;   // per edge x 6, cycles of the last hx_poa_batch
+
+    DevHits hits_view() const {
+        return DevHits{n_hits, q_id.p, q_start.p, q_end.p, t_id.p, t_len.p, t_start.p, t_end.p, n_match.p, n_block.p, is_rev.p, mapq.p, cg_off.p, cg_ops.p};
+    }
+    hxk::ChainFinal chain_view() { return hxk::ChainFinal{c_hit.p, c_qs.p, c_qe.p, c_ts.p, c_te.p, c_nm.p, c_nb.p, c_skf.p, c_skb.p, c_cb.p, c_ce.p, c_cmp.p}; }
+    void tick() { (void)hipEventRecord(tm.a, stream); }
+    void tock(int k) {
+        (void)hipEventRecord(tm.b, stream);
+        (void)hipEventSynchronize(tm.b);
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, tm.a, tm.b);
+        tm.ms[k] += ms; tm.launches[k]++;
+    }
+};

@@ -1,0 +1,602 @@
+// hx_poa.hip - the POA consensus call of the C-ABI: launch and collection of the batches the planner (hx_poa_plan.hip) lays out, the
+// hx_poa_* entry points, the workspace reservation and the statistics of the last call.
+#include "hx_poa_plan.h"
+
+using namespace hxi;
+
+// Every k_poa instance uses private memory (288 to 928 bytes per lane: spills, a by-value argument), and a hardware queue grows its scratch when a
+// dispatch asks for more per wave than the queue has had - a trip through the runtime (an allocation of device memory: slow while the driver is still
+// wiping what another process freed) that holds THAT launch back. In a process that has run the few-edge instances, the first many-edge call then had
+// some of its launches held and others not, they reached the CUs in another order, and the call took 600-640 ms instead of 415-440 (tools/dev_cold.py:
+// a 12 Mb context, then the 140 Mb one; bench.py's configs[3] leg: five runs of five). Once per process and device, every stream of the pool runs one
+// wave that asks for the most: from hx_poa_reserve (beside the parse) or, without a reservation, before the first launches.
+static int scratch_warm_once(hx_ctx* c) {
+    static std::mutex warm_mu;
+    static std::vector<char> warmed;
+    std::lock_guard<std::mutex> lk(warm_mu);
+    if ((int)warmed.size() <= c->device) warmed.resize((size_t)c->device + 1, 0);
+    if (warmed[(size_t)c->device]) return 0;
+    for (int i = 0; i < 8; i++) hxk::scratch_warm(c->poa_streams[i]);
+    for (int i = 0; i < 8; i++) HIPCHK(hipStreamSynchronize(c->poa_streams[i]));
+    warmed[(size_t)c->device] = 1;
+    return 0;
+}
+
+namespace {
+// One consensus call: the PLAN (PoaPlanner, hx_poa_plan.hip: sub-sequences, per-edge capacities, launch classes, workspace slots and batches against the
+// memory budget), the LAUNCH of a batch, and the COLLECTION of its results with the verdict on every edge (done / again with more room / again another way).
+struct PoaCall : PoaPlanner {
+    hx_ctx* c;
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    struct CnsView { const char* p = nullptr; size_t n = 0; const char* data() const { return p; } size_t size() const { return n; } };
+    std::vector<CnsView> cns;                            // per edge: where its finished consensus lies in ...
+    std::vector<std::unique_ptr<char[]>> cns_blocks;     // ... the download of its batch (kept to the end of the call: no copy per edge, no zero fill)
+
+    PoaCall(hx_ctx* c_, const PoaInput& in_, const hx_poa_params* pp_) : PoaPlanner(in_, pp_, c_->opt, c_->poa_block, c_->poa_no_dir), c(c_), cns(in_.n_edge) {}
+    double ms_since_start() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+    // ---- launch of one batch; what the collection needs afterwards
+    struct Launched { std::vector<uint32_t> edges; uint64_t cns_bytes = 0, bytes = 0; std::vector<Cls> classes; };
+    int launch_batch(const std::vector<uint32_t>& batch, uint32_t shrink, Launched& lb) {
+        hipStream_t s = c->stream;
+        PoaPoolBufs& B = c->poa_pools;
+        lb.edges = batch;
+        std::vector<Cls>& classes = lb.classes;
+        if (build_classes(batch, classes)) return -1;
+        // ---- slots and their offsets into the pools
+        std::vector<hxk::PoaSlot> h_slots;
+        uint64_t no = 0, eo = 0, ho = 0, dro = 0, wo = 0, so = 0, co = 0, sto = 0, ao = 0, clo = 0;
+        auto add_slot = [&](const Need& n) {
+            h_slots.push_back(hxk::PoaSlot{no, eo, ho, dro, wo, so, sto, ao, clo});
+            no += n.nn; eo += n.ec; ho += n.hc; dro += n.dc; wo += n.wc; so += n.lm; sto += n.st; ao += n.al; clo += n.mb;
+        };
+        arrange(classes, shrink);
+        for (Cls& q : classes) {
+            q.slot_at = h_slots.size();
+            for (size_t k = 0; k < q.n_slots; k++) {
+                if (!q.persistent) P.edges[q.edges[k]].slot = (uint32_t)h_slots.size();   // one workgroup (or cluster) per edge: the edge's own slot
+                add_slot(slot_need(q, k));
+            }
+            for (uint32_t e : q.edges) {
+                P.edges[e].cns_off = co; co += P.edges[e].vcap;
+                if (q.shared) { P.edges[e].cl_off = clo; clo += (uint64_t)P.edges[e].members * ((uint64_t)P.edges[e].vcap + 1); }
+            }
+        }
+        lb.cns_bytes = co;
+        const uint64_t bytes = no * 106 + eo * 28 + ho * 4 + dro + wo + so + sto * 4 + ao * 8 + clo * 8 + co;
+        lb.bytes = bytes;
+        // The pools of the batch, carved out of the context's arena (256-byte aligned). The arena grows when a batch needs more than it holds - by an eighth
+        // more than asked, so that the retries of a call (a few edges with more room) do not each allocate again - and never shrinks.
+        {
+            const auto tw0 = std::chrono::steady_clock::now();
+            size_t at = 0;
+            auto place = [&at](auto& buf, uint64_t n) { buf.off = at; at += (std::max<uint64_t>(1, n) * sizeof(*buf.p) + 255) & ~(size_t)255; };
+            auto bind = [this](auto& buf, uint64_t) { buf.p = reinterpret_cast<decltype(buf.p)>(c->poa_arena.p + buf.off); };
+#define HX_POOLS(F) \
+            F(B.H, ho); F(B.dir, dro); F(B.dirw, wo); F(B.wslot, no); F(B.code, no); F(B.n_aligned, no); F(B.mark, no); F(B.check, no); F(B.row_code, no); F(B.row_sink, no); \
+            F(B.row_al, no); F(B.aligned, 3 * no); F(B.in_head, no); F(B.in_tail, no); F(B.out_head, no); F(B.out_tail, no); F(B.rank2node, no); F(B.node2rank, no); \
+            F(B.row_pred_off, no); F(B.score, no); F(B.pred, no); F(B.pred_rank, eo); F(B.pred_w, eo); F(B.e_from, eo); F(B.e_to, eo); F(B.e_next_in, eo); F(B.e_next_out, eo); \
+            F(B.e_w, eo); F(B.stack, sto); F(B.aln_node, ao); F(B.aln_pos, ao); F(B.row_meta, no); F(B.row_pred0, no); F(B.row_pred1, no); F(B.nrec, no); F(B.nrec2, no); \
+            F(B.seq, so); F(B.cns, co); F(B.mbox, clo); F(B.csync, (uint64_t)ne * 8); F(B.sinkbuf, (uint64_t)ne * (1 + 2 * 1024));
+            HX_POOLS(place)
+            std::lock_guard<std::mutex> lk(c->poa_arena_mu);
+            if (at > c->poa_arena.cap) {
+                HIPCHK(hipStreamSynchronize(s));   // (nothing of an earlier batch is in flight: collect_batch has read its results)
+                hipError_t e = c->poa_arena.ensure(std::min<size_t>(at + at / 8, std::max<size_t>(at, (size_t)budget + (size_t)ne * 8400)));
+                if (e != hipSuccess) { (void)hipGetLastError(); e = c->poa_arena.ensure(at); }
+                if (e != hipSuccess) {
+                    // the budget was taken from what hipMemGetInfo called free - which somebody else (another context on this device: ranks that share a GPU, another
+                    // process) has taken since. The caller looks again and plans anew with what is there now.
+                    (void)hipGetLastError();
+                    g_err = "hx_poa_batch: cannot allocate " + std::to_string(at >> 20) + " MB of POA workspace: " + hipGetErrorString(e);
+                    return 1;
+                }
+            }
+            HX_POOLS(bind)
+#undef HX_POOLS
+            c->poa_host_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+        }
+        c->poa_workspace_bytes = std::max<uint64_t>(c->poa_workspace_bytes, bytes);
+        c->poa_last_workspace_bytes = std::max<uint64_t>(c->poa_last_workspace_bytes, bytes);
+        const auto te0 = std::chrono::steady_clock::now();
+        HIPCHK(hipMemsetAsync(B.csync.p, 0, (size_t)ne * 8 * 4, s));
+        if (clo) HIPCHK(hipMemsetAsync(B.mbox.p, 0, clo * 8, s));   // tag 0 = nothing published
+        HIPCHK(c->poa_edges.reserve(ne)); HIPCHK(c->poa_len.reserve(ne)); HIPCHK(c->poa_status.reserve(ne));
+        std::vector<uint32_t> order_all;   // shared launches: one entry per workgroup (edge | member << 24); persistent launches: the class's edges, costliest first
+        for (Cls& q : classes) {
+            q.order_at = order_all.size();
+            if (q.shared) {
+                // Workgroups are handed to the 8 XCDs round-robin by index: put the members of one edge 8 indices apart so that they share an
+                // XCD (one L2 for the carries, the handshakes and the direction bytes member 0 walks back over). Holes are no-op workgroups.
+                for (size_t g0 = 0; g0 < q.edges.size(); g0 += 8) {
+                    const size_t g1 = std::min(q.edges.size(), g0 + 8);
+                    uint32_t gmax = 0;
+                    for (size_t j = g0; j < g1; j++) gmax = std::max(gmax, P.edges[q.edges[j]].members);
+                    for (uint32_t m = 0; m < gmax; m++)
+                        for (size_t j = g0; j < g0 + 8; j++)
+                            order_all.push_back(j < g1 && m < P.edges[q.edges[j]].members ? (q.edges[j] | (m << 24)) : 0x00ffffffu);
+                }
+            } else
+                for (uint32_t e : q.edges) order_all.push_back(e);
+            q.blocks = q.shared ? order_all.size() - q.order_at : q.n_slots;   // (not shared: one workgroup per slot - per edge unless persistent)
+        }
+        if (ne >= (1u << 24)) return fail("hx_poa_batch: more than 2^24 edges in one call");
+        HIPCHK(hipMemcpyAsync(c->poa_edges.p, P.edges.data(), (size_t)ne * sizeof(hxk::PoaEdge), hipMemcpyHostToDevice, s));
+        HIPCHK(c->poa_order.reserve(order_all.size()));
+        HIPCHK(hipMemcpyAsync(c->poa_order.p, order_all.data(), order_all.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(c->poa_slots.reserve(h_slots.size()));
+        HIPCHK(hipMemcpyAsync(c->poa_slots.p, h_slots.data(), h_slots.size() * sizeof(hxk::PoaSlot), hipMemcpyHostToDevice, s));
+        HIPCHK(c->poa_counters.reserve(classes.size()));
+        HIPCHK(hipMemsetAsync(c->poa_counters.p, 0, classes.size() * 4, s));
+        hxk::PoaPools pools{B.code.p, B.n_aligned.p, B.aligned.p, B.in_head.p, B.in_tail.p, B.out_head.p, B.out_tail.p, B.rank2node.p, B.node2rank.p,
+                            B.mark.p, B.check.p, B.stack.p, B.score.p, B.pred.p, B.row_code.p, B.row_sink.p, B.row_pred_off.p, B.pred_rank.p, B.row_meta.p, B.row_pred0.p, B.row_pred1.p, B.nrec.p, B.nrec2.p,
+                            B.e_from.p, B.e_to.p, B.e_next_in.p, B.e_next_out.p, B.e_w.p, B.aln_node.p, B.aln_pos.p, B.H.p, B.dir.p, B.dirw.p, B.wslot.p, B.seq.p,
+                            B.mbox.p, B.csync.p, B.sinkbuf.p, B.row_al.p, B.pred_w.p};
+        const size_t n_streams = (size_t)std::min(8, std::max(1, o.poa_streams));   // (8: a stream per launch class of a 140 Mb call - with 6, the two one-wave classes waited 130 / 300 ms behind the shared edges)
+        size_t wg_total = 0;
+        for (const Cls& q : classes) wg_total += q.blocks;
+        c->tick();
+        // The launches. Persistent classes that differ only in their need bucket (build_classes) leave in ONE launch: their slots, lists and counters
+        // lie side by side in class order (largest need first), `btab` tells a workgroup which bucket its slot belongs to (kernels/poa.hip k_poa).
+        std::vector<uint32_t> h_btab;
+        std::vector<std::array<size_t, 3>> groups;   // first class, one past the last, offset of the group's table in h_btab
+        for (size_t i = 0; i < classes.size();) {
+            size_t j = i + 1;
+            const Cls& a = classes[i];
+            while (j < classes.size() && same_instance(a, classes[j])) j++;
+            groups.push_back({i, j, h_btab.size()});
+            if (a.persistent) {
+                h_btab.push_back((uint32_t)(j - i) | (o.poa_own_bucket_first ? 1u << 16 : 0u));
+                uint32_t se = 0, ib = 0;
+                for (size_t k = i; k < j; k++) { se += (uint32_t)classes[k].blocks; h_btab.push_back(se); }
+                for (size_t k = i; k < j; k++) { h_btab.push_back(ib); ib += (uint32_t)classes[k].edges.size(); }
+                h_btab.push_back(ib);
+                for (size_t k = i; k < j; k++) for (uint32_t e : classes[k].edges) h_btab.push_back((uint32_t)std::min(4.0e9, (double)chain_ms[e] * 1000.0));   // est[]: microseconds
+            }
+            i = j;
+        }
+        HIPCHK(c->poa_btab.reserve(std::max<size_t>(1, h_btab.size())));
+        if (!h_btab.empty()) HIPCHK(hipMemcpyAsync(c->poa_btab.p, h_btab.data(), h_btab.size() * 4, hipMemcpyHostToDevice, s));
+        if (scratch_warm_once(c)) return -1;
+        HIPCHK(hipEventRecord(c->poa_ev[8], s));
+        size_t gi = 0;
+        for (const auto& grp : groups) {
+            const size_t ci = grp[0];
+            const Cls& q = classes[ci];
+            size_t g_blocks = 0, g_items = 0;
+            for (size_t k = grp[0]; k < grp[1]; k++) { g_blocks += classes[k].blocks; g_items += classes[k].edges.size(); }
+            const int sk = (int)(gi % n_streams);   // stream / event of the launch (launches that share a stream run one after the other)
+            // LDS of the launch: the ring its row width allows, a power of two of kept rows
+            uint64_t ring_need = 0;
+            const uint32_t dp_nt = q.dpl ? q.dpl : q.nt;   // lanes in the DP
+            const uint32_t R = ring_rows_of(dp_nt, q.cm, ring_need);
+            // few edges: ask for enough LDS per workgroup that the dispatcher cannot stack them on a handful of CUs while others idle
+            // (a lone wave runs at twice the speed of two waves sharing a SIMD); many edges: request only what the ring needs
+            uint64_t lds_bytes = ring_need;
+            {
+                const uint64_t per_cu = (wg_total + 255) / 256;
+                if (per_cu < 8) lds_bytes = std::max<uint64_t>(lds_bytes, std::min<uint64_t>(kPoaLdsMax, (158 * 1024) / per_cu - 18 * 1024));
+                // hundreds of edges: the longest ones set the duration, and their waves run faster with two neighbours on a SIMD than with
+                // three - 10 KB of LDS per wave keeps a CU at 12 waves (thousands of edges: 16, the ring alone is 8.3 KB per wave)
+                if (!many_edges) lds_bytes = std::max<uint64_t>(lds_bytes, std::min<uint64_t>(kPoaLdsMax, 10 * 1024 * (uint64_t)(dp_nt / 64)));
+                if (o.poa_ring_zero) lds_bytes = ring_need;   // (one row's worth: the kernel then finds room for no kept row either)
+            }
+            const int dcls = q.shared ? 0 : q.nt >= 1024 ? 1 : q.nt >= 512 ? 2 : q.nt >= 256 ? 3 : q.nt >= 128 ? 4 : 5;
+            for (size_t k = grp[0]; k < grp[1]; k++)
+                for (uint32_t e : classes[k].edges) { c->dbg_cls[e] = (uint8_t)(dcls + (q.dir ? 0 : 5)); c->dbg_shape[e] = q.nt | std::min<uint32_t>(255, P.edges[e].passes) << 16 | std::min<uint32_t>(255, P.edges[e].members) << 24; }
+            c->dbg_ring[dcls + (q.dir ? 0 : 5)] = R;
+            HIPCHK(hipStreamWaitEvent(c->poa_streams[sk], c->poa_ev[8], 0));
+            hxk::PoaLaunch L{};
+            L.edges = c->poa_edges.p; L.order = c->poa_order.p + q.order_at; L.n_items = q.persistent ? (uint32_t)g_items : (uint32_t)q.blocks;
+            L.slots = c->poa_slots.p + (q.persistent ? q.slot_at : 0); L.counter = q.persistent ? c->poa_counters.p + ci : nullptr; L.n_blocks = (uint32_t)g_blocks;
+            L.btab = q.persistent ? c->poa_btab.p + grp[2] : nullptr;
+            L.seqs = c->poa_seqs.p; L.packed = in.d_packed; L.read_off = in.d_roff; L.read_len = in.d_rlen; L.pools = pools;
+            L.match = pp->match; L.mismatch = pp->mismatch; L.gap = pp->gap; L.cns = B.cns.p; L.cns_len = c->poa_len.p; L.status = c->poa_status.p;
+            L.cells = c->poa_cells_d.p; L.phase = c->poa_phase_d.p; L.block_threads = (int)q.nt; L.cm = (int)q.cm; L.poll_limit = (uint32_t)o.poa_poll_limit; L.ring_bytes = (uint32_t)lds_bytes;
+            L.use_dir = q.dir; L.max_indeg = (uint32_t)std::min(16, std::max(1, o.poa_max_indeg)); L.dp_lanes = q.dpl;
+            const bool wide_q = q.dpl || (balanced && q.nt >= balance_nt && q.nt >= 512 && q.persistent), shared_first = many_edges && q.shared && (o.poa_resident_first & 1);
+            L.started = ((wide_q && (o.poa_resident_first & 2)) || shared_first) && gi < 16 ? c->poa_started + gi : nullptr;
+            if (L.started) *(volatile uint32_t*)L.started = 0u;
+            L.prune_pct = launch_pruned(q) ? (std::min<uint32_t>(q.shared ? prune_shared_pct : prune_pct, 1000u) | (o.poa_prune_lazy ? 1u << 16 : 0u)) : 0u;
+            if (o.debug) { int occ = 0; L.occupancy = &occ; hxk::poa_run(L, c->poa_streams[sk]); L.occupancy = nullptr; fprintf(stderr, "[hx] launch %zu: %zu workgroups of %u lanes, %.1f KB of ring: %d workgroups per CU\n", gi, g_blocks, q.nt, lds_bytes / 1024.0, occ); }
+            hxk::poa_run(L, c->poa_streams[sk]);
+            HIPCHK(hipEventRecord(c->poa_ev[sk], c->poa_streams[sk]));
+            HIPCHK(hipStreamWaitEvent(s, c->poa_ev[sk], 0));
+            if (wide_q || shared_first) {
+                // a 1024-lane workgroup needs an EMPTY CU: give the dispatcher a head start before the other launches fill the chip with small
+                // workgroups (once they have, a CU only empties when its longest resident workgroup ends)
+                HIPCHK(hipEventSynchronize(c->poa_ev[8]));   // (what precedes the launches on `s` is done: the wide launch is starting)
+                const auto tw = std::chrono::steady_clock::now();
+                if (L.started) {
+                    // (round 6: not a fixed delay but the launch's own word - every workgroup adds itself when it begins. One pass in five of the 140 Mb call took 610-650 ms
+                    // instead of 440-470: no edge redone, the same launches - in another order of arrival on the CUs. The shared edges' members and the wide classes
+                    // must be the oldest waves where they sit; the next launch leaves when they have all begun, or after 2 ms)
+                    volatile uint32_t* w = L.started;
+                    while (*w < L.n_blocks && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count() < 2000.0) { }
+                    if (o.debug) fprintf(stderr, "[hx] launch %zu: %u of %u workgroups had begun %.0f us after the launch\n", gi, (unsigned)*w, L.n_blocks, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count());
+                } else
+                    while (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count() < o.poa_wide_delay_us) { }
+            }
+            gi++;
+        }
+        const auto te1 = std::chrono::steady_clock::now();
+        c->tock(3);
+        c->poa_host_ms[2] += std::chrono::duration<double, std::milli>(te1 - te0).count();
+        c->poa_host_ms[3] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te1).count();
+        HIPCHK(hipGetLastError());
+        if (o.debug) {
+            HIPCHK(hipStreamSynchronize(s));
+            fprintf(stderr, "[hx] POA batch: %zu edges, %.2f GB workspace, workgroups", batch.size(), bytes / 1e9);
+            for (const Cls& q : classes) fprintf(stderr, " %s%s%s%s%ux%u:%zu(%zu edges, largest %.1f MB)", q.shared ? "shared/" : "", q.persistent ? "persistent/" : "", q.dir ? "" : "matrix/",
+                                                 launch_pruned(q) ? (q.pk ? "pruned/passes/" : "pruned/") : "", q.nt, q.cm, q.blocks, q.edges.size(), need_bytes(q.need) / 1e6);
+            fprintf(stderr, ", %.1f ms since the call began\n", ms_since_start());
+        }
+        return 0;
+    }
+
+    // ---- collection: consensus strings of the edges that are done; the others go to `retry` (worst-case workspace next) / `retry_same` (another way)
+    int collect_batch(const Launched& lb, std::vector<uint32_t>& retry, std::vector<uint32_t>& retry_same) {
+        const auto tc0 = std::chrono::steady_clock::now();
+        hipStream_t s = c->stream;
+        std::vector<uint32_t> h_len(ne), h_status(ne);
+        HIPCHK(hipMemcpy(h_len.data(), c->poa_len.p, (size_t)ne * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_status.data(), c->poa_status.p, (size_t)ne * 4, hipMemcpyDeviceToHost));
+        // the finished strings, moved side by side on the device before the download: the buffer the kernels write into is sized by the node estimates
+        // (100 MB for the 13 000 edges of a 140 Mb genome, of which 30 MB are consensus)
+        std::vector<uint32_t> desc;
+        std::vector<uint64_t> dense_off(lb.edges.size() + 1, 0);
+        desc.reserve(lb.edges.size() * 5);
+        for (size_t i = 0; i < lb.edges.size(); i++) {
+            const uint32_t e = lb.edges[i];
+            const uint32_t n = h_status[e] ? 0u : std::min<uint32_t>(h_len[e], P.edges[e].vcap);
+            dense_off[i + 1] = dense_off[i] + n;
+            if (!n) continue;
+            const uint64_t so = P.edges[e].cns_off, to = dense_off[i];
+            desc.insert(desc.end(), {(uint32_t)so, (uint32_t)(so >> 32), (uint32_t)to, (uint32_t)(to >> 32), n});
+        }
+        cns_blocks.emplace_back(new char[std::max<uint64_t>(1, dense_off.back())]);
+        const char* h_cns = cns_blocks.back().get();
+        if (!desc.empty()) {
+            HIPCHK(c->poa_gather.reserve(desc.size())); HIPCHK(c->poa_cns_dense.reserve(dense_off.back()));
+            HIPCHK(hipMemcpyAsync(c->poa_gather.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, s));
+            hxk::gather_bytes(c->poa_pools.cns.p, c->poa_gather.p, (uint32_t)(desc.size() / 5), c->poa_cns_dense.p, s);
+            HIPCHK(hipMemcpyAsync(cns_blocks.back().get(), c->poa_cns_dense.p, dense_off.back(), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        struct Lap { double& ms; std::chrono::steady_clock::time_point t0; ~Lap() { ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } lap{c->poa_host_ms[4], tc0};
+        if (o.debug) {
+            size_t n_far = 0, n_nodir = 0, n_over = 0, n_wide = 0, n_sinks = 0, n_stall = 0;
+            for (uint32_t e : lb.edges) { n_far += !!(h_status[e] & HXE_POA_FARROWS); n_nodir += !!(h_status[e] & HXE_POA_NODIR); n_over += !!(h_status[e] & HXE_POA_OVERFLOW); n_wide += !!(h_status[e] & HXE_POA_WIDEROWS); n_sinks += !!(h_status[e] & HXE_POA_SINKS); n_stall += !!(h_status[e] & HXE_POA_STALLED); }
+            if (n_far + n_nodir + n_over + n_wide + n_sinks + n_stall) fprintf(stderr, "[hx] POA batch: to be redone: %zu (rows read back from HBM outgrew H), %zu (in-degree above the direction bytes' limit), %zu (graph outgrew its workspace), %zu (rows with more than 4 predecessors outgrew the wide-row pool), %zu (more sink rows than the launch keeps), %zu (members of a shared edge not resident together%s: unshared next)\n",
+                                                                       n_far, n_nodir, n_over, n_wide, n_sinks, n_stall, balanced ? ", in a balanced launch" : "");
+        }
+        for (size_t i = 0; i < lb.edges.size(); i++) {
+            const uint32_t e = lb.edges[i];
+            if (h_status[e] & HXE_POA_FARROWS) { if (P.edges[e].hrows >= P.edges[e].vcap + 1) return fail("hx_poa_batch: internal error (far-row retry)"); far_full[e]++; retry_same.push_back(e); continue; }
+            if (h_status[e] & HXE_POA_STALLED) {
+                if (P.edges[e].members < 2) return fail("hx_poa_batch: internal error (a wave of an unshared edge gave up waiting)");
+                no_share[e] = 1; retry_same.push_back(e); continue;
+            }
+            if (h_status[e] & HXE_POA_WIDEROWS) { if (P.edges[e].wrows >= P.edges[e].vcap + 1) return fail("hx_poa_batch: internal error (wide-row retry)"); wide_grow[e]++; retry_same.push_back(e); continue; }
+            if (h_status[e] & HXE_POA_SINKS) { if (many_sinks[e]) return fail("hx_poa_batch: internal error (sink-list retry)"); many_sinks[e] = 1; retry_same.push_back(e); continue; }
+            if (h_status[e] & HXE_POA_NODIR) { if (force_nodir[e]) return fail("hx_poa_batch: internal error (direction-byte retry)"); force_nodir[e] = 1; retry_same.push_back(e); continue; }
+            if (h_status[e] & ~(uint32_t)HXE_POA_OVERFLOW) return fail("hx_poa_batch: internal error (kernel variant / column count mismatch)");
+            if (h_status[e] & HXE_POA_OVERFLOW) {
+                if (P.edges[e].vcap >= P.sumL[e]) return fail("hx_poa_batch: POA workspace overflow at worst-case size (internal error)");
+                grow[e]++;
+                retry.push_back(e);
+            } else cns[e] = CnsView{h_cns + dense_off[i], (size_t)(dense_off[i + 1] - dense_off[i])};
+        }
+        return 0;
+    }
+};
+}  // namespace
+
+static int poa_consensus(hx_ctx* c, const PoaInput& in, const hx_poa_params* pp, hx_cns_out* out) {
+    memset(out, 0, sizeof(*out));
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    PoaCall K(c, in, pp);
+    const uint32_t ne = K.ne;
+    std::vector<uint32_t> todo;
+    for (double& v : c->poa_host_ms) v = 0;
+    auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    if (K.plan_input(todo)) return -1;
+    c->poa_host_ms[0] += K.ms_since_start();
+    if (c->opt.debug) fprintf(stderr, "[hx] POA call: %u edges prepared in %.1f ms\n", (unsigned)ne, K.ms_since_start());
+    c->dbg_cls.assign(ne, 11); for (int k = 0; k < 11; k++) c->dbg_ring[k] = 0;
+    c->dbg_shape.assign(ne, 0);
+    c->dbg_nseq = K.P.nseq; c->dbg_lmax.resize(ne); for (uint32_t e = 0; e < ne; e++) c->dbg_lmax[e] = K.P.edges[e].lmax;
+    HIPCHK(c->poa_seqs.reserve(K.P.seqs.size()));
+    if (!K.P.seqs.empty()) HIPCHK(hipMemcpyAsync(c->poa_seqs.p, K.P.seqs.data(), K.P.seqs.size() * sizeof(hxk::PoaSeq), hipMemcpyHostToDevice, s));
+    HIPCHK(c->poa_cells_d.reserve(1));
+    HIPCHK(hipMemsetAsync(c->poa_cells_d.p, 0, 8, s));
+    if (!c->poa_budget) {   // measured once: later calls would count the context's own (persistent) workspace as used
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        { std::lock_guard<std::mutex> lk(c->poa_arena_mu); free_b += c->poa_arena.cap; }   // (an arena reserved ahead - hx_poa_reserve - is the workspace's own)
+        c->poa_budget = (uint64_t)(free_b * 0.9);
+        c->poa_free_at_first_call = free_b;
+    }
+    // option poa_workspace_gb: cap of the POA workspace (default: 90 % of what was free when the context first ran a consensus). The workgroups in
+    // flight per launch class are scaled down until the slots fit. Measured at 140 Mb (13 230 edges): 257 GB 2.0-2.1 s, 138 GB 2.10-2.13 s (and
+    // the first call, which allocates the pools, 4.1 instead of 5-7.6 s), 39 GB 4.6 s, 22 GB 8.5 s; a 400 Mb genome (37 608 edges): 148 GB 6.7 s.
+    // (Round 6, measured on the 140 Mb data set, 13 197 edges: 0.50 s with the 215 GB the plan takes of a 257 GB budget, 0.75-0.90 s under a cap of 140 GB, 1.04 s
+    // under 100 GB - the slot counts of the one-wave classes are what shrinks. No cap of its own, then: 90 % of what is free.)
+    K.budget = c->opt.poa_workspace_gb > 0 ? (uint64_t)(c->opt.poa_workspace_gb * 1e9) : c->poa_budget;
+    c->poa_last_workspace_bytes = 0;
+    HIPCHK(c->poa_phase_d.reserve((size_t)ne * hxk::POA_PHASE_WORDS));
+    HIPCHK(hipMemsetAsync(c->poa_phase_d.p, 0, std::max<size_t>(1, (size_t)ne * hxk::POA_PHASE_WORDS) * 8, s));
+    while (!todo.empty()) {
+        const auto tp0 = std::chrono::steady_clock::now();
+        if (K.knobs(todo.size()) || K.size_edges(todo)) return -1;
+        const double t_size = since(tp0);
+        std::vector<std::vector<uint32_t>> batches;
+        std::vector<uint32_t> batch_shrink;
+        if (K.plan_batches(todo, batches, batch_shrink)) return -1;
+        c->poa_host_ms[0] += since(tp0);
+        if (c->opt.debug) fprintf(stderr, "[hx] POA plan: widths and rooms of %zu edges %.2f ms, batches and slots %.2f ms\n", todo.size(), t_size, since(tp0) - t_size);
+        std::vector<uint32_t> retry, retry_same;   // retry with the worst-case workspace / with the score-matrix traceback
+        for (size_t bi = 0; bi < batches.size(); bi++) {
+            if (batches[bi].empty()) continue;
+            PoaCall::Launched lb;
+            K.by_work = bi < K.batch_by_work.size() && K.batch_by_work[bi] != 0;
+            const int rc = K.launch_batch(batches[bi], batch_shrink[bi], lb);
+            if (rc == 1) {   // the arena could not be had at the planned size: the budget again from what is free NOW, the rest of the round planned anew
+                size_t free_b = 0, total_b = 0;
+                HIPCHK(hipMemGetInfo(&free_b, &total_b));
+                uint64_t now_b;
+                { std::lock_guard<std::mutex> lk(c->poa_arena_mu); now_b = (uint64_t)((double)(free_b + c->poa_arena.cap) * 0.9); }
+                if (now_b + (now_b >> 6) >= K.budget) return -1;   // (nothing changed: the error stands)
+                if (c->opt.debug) fprintf(stderr, "[hx] POA workspace: %.1f GB could not be allocated; %.1f GB are free now, budget %.1f -> %.1f GB\n", lb.bytes / 1e9, free_b / 1e9, K.budget / 1e9, now_b / 1e9);
+                K.budget = now_b;
+                if (c->opt.poa_workspace_gb <= 0) c->poa_budget = now_b;
+                for (size_t bj = bi; bj < batches.size(); bj++) retry_same.insert(retry_same.end(), batches[bj].begin(), batches[bj].end());
+                break;
+            }
+            if (rc || K.collect_batch(lb, retry, retry_same)) return -1;
+        }
+        todo.swap(retry);
+        todo.insert(todo.end(), retry_same.begin(), retry_same.end());
+    }
+    const auto tf0 = std::chrono::steady_clock::now();
+    unsigned long long cells = 0;
+    HIPCHK(hipMemcpy(&cells, c->poa_cells_d.p, 8, hipMemcpyDeviceToHost));
+    c->poa_phase.resize((size_t)ne * hxk::POA_PHASE_WORDS);
+    if (ne) HIPCHK(hipMemcpy(c->poa_phase.data(), c->poa_phase_d.p, (size_t)ne * hxk::POA_PHASE_WORDS * 8, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> off((size_t)ne + 1, 0);
+    for (uint32_t e = 0; e < ne; e++) off[e + 1] = off[e] + K.cns[e].size();
+    out->n_edge = ne;
+    out->cns_off = (uint64_t*)malloc(((size_t)ne + 1) * 8); memcpy(out->cns_off, off.data(), ((size_t)ne + 1) * 8);
+    out->cns = (char*)malloc(std::max<uint64_t>(1, off[ne]));
+    {   // (30 MB of strings at 140 Mb: a few threads, each its range of the edges)
+        const uint32_t nt = off[ne] > (4u << 20) ? 4u : 1u;
+        auto part = [&](uint32_t t) { for (uint32_t e = (uint32_t)((uint64_t)ne * t / nt); e < (uint32_t)((uint64_t)ne * (t + 1) / nt); e++) if (K.cns[e].size()) memcpy(out->cns + off[e], K.cns[e].data(), K.cns[e].size()); };
+        std::vector<std::thread> th;
+        for (uint32_t t = 1; t < nt; t++) th.emplace_back(part, t);
+        part(0);
+        for (std::thread& x : th) x.join();
+    }
+    out->dp_cells = cells; out->seq_bases = K.seq_bases; out->n_aligned = K.n_aligned;
+    c->poa_host_ms[5] = since(tf0); c->poa_host_ms[7] = K.ms_since_start();
+    if (c->opt.debug) fprintf(stderr, "[hx] POA call, host wall time: plan %.1f ms, workspace %.1f ms (%llu device allocations so far, %.0f ms), enqueue %.1f ms, device %.1f ms, collect %.1f ms, finish %.1f ms, total %.1f ms\n",
+                              c->poa_host_ms[0], c->poa_host_ms[1], (unsigned long long)c->poa_arena.n_alloc, c->poa_arena.alloc_ms, c->poa_host_ms[2], c->poa_host_ms[3], c->poa_host_ms[4], c->poa_host_ms[5], c->poa_host_ms[7]);
+    return 0;
+}
+
+extern "C" int hx_poa_batch(hx_ctx* c, const hx_poa_params* pp, hx_cns_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!c->have_coords) return fail("hx_poa_batch: hx_edge_coords has not run");
+    const PoaInput in{c->n_sel, c->h_supp_off.data(), c->h_supp_lr.data(), c->h_spos.data(), c->h_epos.data(), c->h_rlen.data(), c->packed.p, c->roff.p, c->rlen.p};
+    return poa_consensus(c, in, pp, out);
+}
+
+extern "C" int hx_poa_supports(hx_ctx* c, const hx_coords_out* sup, const hx_poa_params* pp, hx_cns_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!c->n_reads) return fail("hx_poa_supports: no reads are resident (hx_upload)");
+    for (uint64_t k = 0; k < sup->supp_off[sup->n_edge]; k++)
+        if ((sup->supp_lr[k] & 0x7fffffffu) >= c->n_reads) return fail("hx_poa_supports: long-read id out of range");
+    const PoaInput in{sup->n_edge, sup->supp_off, sup->supp_lr, sup->spos, sup->epos, c->h_rlen.data(), c->packed.p, c->roff.p, c->rlen.p};
+    return poa_consensus(c, in, pp, out);
+}
+
+extern "C" int hx_poa_sequences(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_params* pp, hx_cns_out* out) {
+    memset(out, 0, sizeof(*out));
+    HIPCHK(hipSetDevice(c->device));
+    const uint64_t nseq = set_off[n_sets];
+    if (nseq >= 0x7fffffffULL) return fail("hx_poa_sequences: too many sequences");
+    // pack like the long reads (2 bits, A0 C1 G2 T3, anything else A; every sequence on a 4-byte boundary) and align them whole, forward
+    std::vector<uint32_t> len(nseq), lr(nseq), sp(nseq, 0), ep(nseq);
+    std::vector<uint64_t> off(nseq + 1, 0);
+    for (uint64_t i = 0; i < nseq; i++) {
+        const uint64_t L = seq_off[i + 1] - seq_off[i];
+        if (L >= 0xffffffffULL) return fail("hx_poa_sequences: sequence too long");
+        len[i] = (uint32_t)L; lr[i] = (uint32_t)i; ep[i] = (uint32_t)L - 1;   // an empty sequence gives epos = spos - 1: skipped, as in the reference (Assemble.cpp:537)
+        off[i + 1] = off[i] + ((L + 15) / 16) * 4;
+    }
+    std::vector<uint8_t> packed(std::max<uint64_t>(4, off[nseq]), 0);
+    for (uint64_t i = 0; i < nseq; i++)
+        for (uint32_t j = 0; j < len[i]; j++) {
+            const char ch = bases[seq_off[i] + j];
+            const uint8_t code = ch == 'C' || ch == 'c' ? 1 : ch == 'G' || ch == 'g' ? 2 : ch == 'T' || ch == 't' ? 3 : 0;
+            packed[off[i] + (j >> 2)] |= (uint8_t)(code << ((j & 3) * 2));
+        }
+    DV<uint8_t> d_packed; DV<uint64_t> d_off; DV<uint32_t> d_len;
+    if (up(d_packed, packed.data(), packed.size()) || up(d_off, off.data(), off.size()) || up(d_len, len.data(), std::max<size_t>(1, len.size()))) return -1;
+    const PoaInput in{n_sets, set_off, lr.data(), sp.data(), ep.data(), len.data(), d_packed.p, d_off.p, d_len.p};
+    const int rc = poa_consensus(c, in, pp, out);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return rc;
+}
+
+extern "C" int hx_poa_sequences_mode(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_mode_params* mp, hx_cns_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!mp) return fail("hx_poa_sequences_mode: no parameters");
+    if (mp->gap >= 0) return fail("hx_poa_sequences_mode: the gap score must be negative (linear gap penalty), not " + std::to_string(mp->gap));
+    if (mp->type != HX_POA_SW && mp->type != HX_POA_NW && mp->type != HX_POA_OV) return fail("hx_poa_sequences_mode: unknown alignment type " + std::to_string(mp->type) + " (HX_POA_SW 0, HX_POA_NW 1, HX_POA_OV 2)");
+    if (set_off[n_sets] >= 0x7fffffffULL) return fail("hx_poa_sequences_mode: too many sequences");
+    const hx_poa_params pp{mp->match, mp->mismatch, mp->gap};
+    if (mp->type == HX_POA_NW && !c->opt.poa_general) return hx_poa_sequences(c, n_sets, set_off, seq_off, bases, &pp, out);   // the tuned global path
+    HIPCHK(hipSetDevice(c->device));
+    const hxk::PoaModesArgs a{n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap, mp->type, (uint32_t)std::max(0, c->opt.poa_modes_slot_kb), c->opt.poa_workspace_gb, c->opt.debug};
+    hxk::PoaModesOut o;
+    std::string err;
+    if (hxk::poa_modes_run(c->stream, c->poa_modes_ws, a, o, err)) return fail(err);
+    c->tm.ms[3] += o.kernel_ms; c->tm.launches[3] += o.launches;
+    out->n_edge = n_sets;
+    out->cns_off = (uint64_t*)malloc(((size_t)n_sets + 1) * 8); memcpy(out->cns_off, o.cns_off.data(), ((size_t)n_sets + 1) * 8);
+    out->cns = (char*)malloc(std::max<size_t>(1, o.cns.size())); memcpy(out->cns, o.cns.data(), o.cns.size());
+    out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
+    if (c->opt.debug) fprintf(stderr, "[hx] POA modes call: %u sets, %.3g cells, kernels %.2f ms, %u sets rerun in a larger slot\n", n_sets, (double)o.cells, o.kernel_ms, o.retried);
+    return 0;
+}
+
+extern "C" void hx_free_cns(hx_ctx*, hx_cns_out* o) { free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }
+
+extern "C" uint32_t hx_poa_phase_cycles(hx_ctx* c, uint64_t* sum6, uint64_t* max6) {
+    // lane-0 cycle counters of the last hx_poa_batch: [decode, dp, traceback, graph update+consensus, toposort, csr];
+    // sum over edges and the breakdown of the edge with the largest total (the critical path)
+    constexpr size_t PW_ = hxk::POA_PHASE_WORDS;
+    for (int k = 0; k < 6; k++) { sum6[k] = 0; max6[k] = 0; }
+    unsigned long long best = 0;
+    size_t ne = c->poa_phase.size() / PW_;
+    for (size_t e = 0; e < ne; e++) for (int k = 0; k < 6; k++) if ((long long)c->poa_phase[e * PW_ + k] < 0) c->poa_phase[e * PW_ + k] = 0;   // (a phase that began and ended on different waves' clocks)
+    for (size_t e = 0; e < ne; e++) {
+        unsigned long long t = 0;
+        for (int k = 0; k < 6; k++) { sum6[k] += c->poa_phase[e * PW_ + k]; t += c->poa_phase[e * PW_ + k]; }
+        if (t > best) { best = t; for (int k = 0; k < 6; k++) max6[k] = c->poa_phase[e * PW_ + k]; c->dbg_slowest = (uint32_t)e; }
+    }
+    if (c->opt.debug && ne) {
+        const unsigned long long* q = &c->poa_phase[(size_t)c->dbg_slowest * PW_];
+        if (c->opt.prof == 1) {   // (a build with -DHX_DP_PROF: where the rows of the first wave of every workgroup spend their cycles, per launch class)
+            static const char* seg[6] = {"decode", "predecessors + cells + chain", "wave scan", "carry", "carry applied + ring", "stores"};
+            unsigned long long cs[12][7] = {};
+            for (size_t e = 0; e < ne; e++) { const int k = e < c->dbg_cls.size() ? c->dbg_cls[e] : 11; for (int j = 0; j < 6; j++) cs[k][j] += c->poa_phase[e * PW_ + 6 + j]; cs[k][6] += c->poa_phase[e * PW_ + 1]; }
+            for (int k = 0; k < 12; k++) {
+                unsigned long long t = 0; for (int j = 0; j < 6; j++) t += cs[k][j];
+                if (!t) continue;
+                fprintf(stderr, "[hx] prof1 class %d: row segments of wave 0, %.3g cycles (DP phase %.3g):", k, (double)t, (double)cs[k][6]);
+                for (int j = 0; j < 6; j++) fprintf(stderr, " %s %.1f %%%s", seg[j], 100.0 * (double)cs[k][j] / (double)t, j < 5 ? "," : "\n");
+            }
+            return (uint32_t)ne;
+        }
+        if (c->opt.prof == 2) {   // (a build with -DHX_DP_PROF -DHX_DP_PROF2: where member 0's DP phase goes, for the five longest edges)
+            std::vector<std::pair<unsigned long long, uint32_t>> tt;
+            for (size_t e = 0; e < ne; e++) { unsigned long long t = 0; for (int k = 0; k < 6; k++) t += c->poa_phase[e * PW_ + k]; tt.push_back({t, (uint32_t)e}); }
+            std::sort(tt.rbegin(), tt.rend());
+            for (size_t k = 0; k < std::min<size_t>(5, tt.size()); k++) {
+                const unsigned long long* q2 = &c->poa_phase[(size_t)tt[k].second * PW_];
+                fprintf(stderr, "[hx] prof2 edge %u lmax=%u nseq=%u dp phase %llu: publish %llu own columns %llu wait members %llu end node %llu (ties sorted %llu, toposort %llu)\n", tt[k].second, c->dbg_lmax[tt[k].second],
+                        c->dbg_nseq[tt[k].second], q2[1], q2[6], q2[7], q2[8], q2[9], q2[10], q2[11]);
+            }
+            return (uint32_t)ne;
+        }
+        if (c->opt.prof == 3) {   // (a build with -DHX_DP_PROF3: per member of the five longest edges, kilocycles inside the DP and of them waiting for carries)
+            std::vector<std::pair<unsigned long long, uint32_t>> tt;
+            for (size_t e = 0; e < ne; e++) { unsigned long long t = 0; for (int k = 0; k < 6; k++) t += c->poa_phase[e * PW_ + k]; tt.push_back({t, (uint32_t)e}); }
+            std::sort(tt.rbegin(), tt.rend());
+            for (size_t k = 0; k < std::min<size_t>(5, tt.size()); k++) {
+                const unsigned long long* q2 = &c->poa_phase[(size_t)tt[k].second * PW_];
+                fprintf(stderr, "[hx] prof3 edge %u lmax=%u nseq=%u dp %llu:", tt[k].second, c->dbg_lmax[tt[k].second], c->dbg_nseq[tt[k].second], q2[1]);
+                for (int m = 0; m < 6; m++) fprintf(stderr, " m%d dp %lluk wait %lluk", m, q2[6 + m] & 0xffffffffull, q2[6 + m] >> 32);
+                fprintf(stderr, "\n");
+            }
+            return (uint32_t)ne;
+        }
+        const unsigned long long M40 = (1ull << 40) - 1;
+        if (c->opt.debug >= 2) {   // every edge: shape of its launch, begin and end on the 100 MHz wall clock (relative to the call's first edge), phase cycles, DP rows
+            unsigned long long t0 = ~0ull;
+            const unsigned long long M44 = (1ull << 44) - 1;
+            for (size_t e = 0; e < ne; e++) if (c->poa_phase[e * PW_ + 16]) t0 = std::min(t0, c->poa_phase[e * PW_ + 16] & M44);
+            for (size_t e = 0; e < ne; e++) {
+                const unsigned long long* q2 = &c->poa_phase[e * PW_];
+                if (!q2[16]) continue;
+                const uint32_t sh = e < c->dbg_shape.size() ? c->dbg_shape[e] : 0;
+                fprintf(stderr, "[hx-edge] %zu lmax %u nseq %u cls %d lanes %u passes %u members %u hw %u begin_us %.1f end_us %.1f decode %llu dp %llu tb %llu graph %llu order %llu csr %llu rows %llu wrows %llu wskip %llu wbulk %llu cns %llu refcns %llu\n", e, c->dbg_lmax[e], c->dbg_nseq[e],
+                        e < c->dbg_cls.size() ? c->dbg_cls[e] : 11, sh & 0xffffu, (sh >> 16) & 255u, sh >> 24, (unsigned)(q2[16] >> 44), (double)((q2[16] & M44) - t0) * 0.01, (double)(q2[17] - t0) * 0.01, q2[0], q2[1], q2[2], q2[3], q2[4], q2[5], q2[6], q2[12], q2[13], q2[20], q2[18], q2[19]);
+            }
+        }
+        fprintf(stderr, "[hx] slowest edge %u: lmax=%u nseq=%u | DP rows %llu (multi-pred %llu, ring refs %llu, far refs %llu, kept %llu, more than 4 predecessors %llu, fifth-and-later entries %llu) over %llu sequences\n", c->dbg_slowest,
+                c->dbg_lmax[c->dbg_slowest], c->dbg_nseq[c->dbg_slowest], q[6], q[7], q[8] & M40, q[9] & M40, q[10], q[9] >> 40, q[8] >> 40, q[11] & 0xffffffffull);
+        {   // the five longest edges (critical-path candidates)
+            std::vector<std::pair<unsigned long long, uint32_t>> tt;
+            for (size_t e = 0; e < ne; e++) { unsigned long long t = 0; for (int k = 0; k < 6; k++) t += c->poa_phase[e * PW_ + k]; tt.push_back({t, (uint32_t)e}); }
+            std::sort(tt.rbegin(), tt.rend());
+            for (size_t k = 0; k < std::min<size_t>(5, tt.size()); k++) {
+                const unsigned long long* q2 = &c->poa_phase[(size_t)tt[k].second * PW_];
+                fprintf(stderr, "[hx] top edge %u: lmax=%u nseq=%u cycles=%llu (dp %llu tb %llu graph %llu order %llu csr %llu) rows %llu multi %llu ring %llu far %llu kept %llu wide %llu fifth+ %llu\n", tt[k].second, c->dbg_lmax[tt[k].second], c->dbg_nseq[tt[k].second],
+                        tt[k].first, q2[1], q2[2], q2[3], q2[4], q2[5], q2[6], q2[7], q2[8] & ((1ull << 40) - 1), q2[9] & ((1ull << 40) - 1), q2[10], q2[9] >> 40, q2[8] >> 40);
+            }
+        }
+        {   // finished graphs against the workspace estimate: nodes per base of the longest sequence, as a + b x sequences
+            std::vector<double> grow, fill;
+            for (size_t e = 0; e < ne; e++) {
+                const double V = (double)(c->poa_phase[e * PW_ + 11] >> 32), L = c->dbg_lmax[e], S = c->dbg_nseq[e];
+                if (V <= 0 || L <= 0 || S <= 0) continue;
+                grow.push_back((V - L) / (L * S));
+                fill.push_back(V / (L * (3 + S / 10) + 1024));
+            }
+            std::sort(grow.begin(), grow.end()); std::sort(fill.begin(), fill.end());
+            auto pc = [](const std::vector<double>& v, double q) { return v.empty() ? 0.0 : v[std::min(v.size() - 1, (size_t)(q * v.size()))]; };
+            fprintf(stderr, "[hx] graph growth (nodes - L) / (L x sequences): median %.3f  p90 %.3f  p99 %.3f  max %.3f | nodes / estimate: median %.2f  p99 %.2f  max %.2f\n",
+                    pc(grow, 0.5), pc(grow, 0.9), pc(grow, 0.99), pc(grow, 1.0), pc(fill, 0.5), pc(fill, 0.99), pc(fill, 1.0));
+        }
+        {   // per launch class: how often a row is read back from the LDS ring / from HBM
+            unsigned long long cr[12][4] = {};
+            for (size_t e = 0; e < ne; e++) { const int k = e < c->dbg_cls.size() ? c->dbg_cls[e] : 11; const unsigned long long* q3 = &c->poa_phase[e * PW_]; cr[k][0] += q3[6]; cr[k][1] += q3[10]; cr[k][2] += q3[8] & ((1ull << 40) - 1); cr[k][3] += q3[9] & ((1ull << 40) - 1); }
+            for (int k = 0; k < 12; k++) if (cr[k][0]) fprintf(stderr, "[hx] class %d (ring %u): DP rows %llu, kept %.1f %%, ring refs %.1f %%, far refs %.2f %%\n", k, k < 11 ? c->dbg_ring[k] : 0, cr[k][0], 100.0 * cr[k][1] / cr[k][0], 100.0 * cr[k][2] / cr[k][0], 100.0 * cr[k][3] / cr[k][0]);
+            unsigned long long cy[12][4] = {};   // edges, all cycles, DP cycles, longest edge
+            for (size_t e = 0; e < ne; e++) {
+                const int k = e < c->dbg_cls.size() ? c->dbg_cls[e] : 11; const unsigned long long* q3 = &c->poa_phase[e * PW_];
+                unsigned long long t = 0; for (int j = 0; j < 6; j++) t += q3[j];
+                cy[k][0]++; cy[k][1] += t; cy[k][2] += q3[1]; cy[k][3] = std::max(cy[k][3], t);
+            }
+            for (int k = 0; k < 12; k++) if (cy[k][0]) fprintf(stderr, "[hx] class %d: %llu workgroups, %.3e cycles in all (DP %.0f %%), longest %.3e, DP cycles per row %.0f\n", k, cy[k][0], (double)cy[k][1], 100.0 * cy[k][2] / cy[k][1], (double)cy[k][3], cr[k][0] ? (double)cy[k][2] / cr[k][0] : 0.0);
+        }
+        {   // the pruning (kernels/poa.hip PRUNE): wave-rows of the pruned launches, those skipped, attempts repeated, per launch class
+            unsigned long long pr[12][4] = {};
+            for (size_t e = 0; e < ne; e++) { const int k = e < c->dbg_cls.size() ? c->dbg_cls[e] : 11; for (int j = 0; j < 4; j++) pr[k][j] += c->poa_phase[e * PW_ + 12 + j]; }
+            for (int k = 0; k < 12; k++) if (pr[k][0]) fprintf(stderr, "[hx] class %d pruning: %.4g wave-rows, %.1f %% skipped, %llu alignments with a threshold, %llu repeated\n", k, (double)pr[k][0], 100.0 * pr[k][1] / pr[k][0], pr[k][3], pr[k][2]);
+        }
+        unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};
+        for (size_t e = 0; e < ne; e++) for (int k = 0; k < 6; k++) tot[k] += k == 5 ? (c->poa_phase[e * PW_ + 11] & 0xffffffffull) : (k == 2 || k == 3 ? c->poa_phase[e * PW_ + 6 + k] & ((1ull << 40) - 1) : c->poa_phase[e * PW_ + 6 + k]);
+        fprintf(stderr, "[hx] all edges: DP rows %llu (multi-pred %llu, ring refs %llu, far refs %llu, kept %llu) over %llu sequences\n", tot[0], tot[1], tot[2], tot[3], tot[4], tot[5]);
+    }
+    return (uint32_t)ne;
+}
+extern "C" uint64_t hx_poa_workspace_bytes(const hx_ctx* c) { return c->poa_workspace_bytes; }
+extern "C" int hx_poa_release_workspace(hx_ctx* c) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { std::lock_guard<std::mutex> lk(c->poa_arena_mu); c->poa_arena.release(); }
+    c->poa_modes_ws.release();
+    c->poa_budget = 0;   // taken again, from what is free then, by the next consensus call
+    return 0;
+}
+extern "C" int hx_poa_reserve(hx_ctx* c, uint64_t bytes) {
+    // the arena of the consensus workspace, ahead of the first call (the CLI: on a thread of its own, beside the parse of the text inputs): at most 80 % of
+    // what is free now (counting what the arena already holds), whatever the caller guessed; a later call that needs more allocates again
+    HIPCHK(hipSetDevice(c->device));
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    std::lock_guard<std::mutex> lk(c->poa_arena_mu);
+    uint64_t cap_b = (uint64_t)((double)(free_b + c->poa_arena.cap) * 0.8);                             // (the inputs go beside it: hx_upload gives the arena back if they do not fit)
+    if (c->opt.poa_workspace_gb > 0) cap_b = std::min<uint64_t>(cap_b, (uint64_t)(c->opt.poa_workspace_gb * 1.02e9) + (64ull << 20));   // (option poa_workspace_gb: no call will take more)
+    const size_t want = (size_t)std::min<uint64_t>(bytes, cap_b);
+    if (want <= c->poa_arena.cap) return 0;
+    const hipError_t e = c->poa_arena.ensure(want);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(std::string("hx_poa_reserve: ") + hipGetErrorString(e)); }
+    if (scratch_warm_once(c)) return -1;
+    return 0;
+}
+extern "C" void hx_poa_host_times(const hx_ctx* c, double* ms8) { for (int k = 0; k < 8; k++) ms8[k] = c->poa_host_ms[k]; }
+extern "C" void hx_poa_arena_stats(const hx_ctx* c, uint64_t* capacity, uint64_t* allocations, double* alloc_ms) { *capacity = c->poa_arena.cap; *allocations = c->poa_arena.n_alloc; *alloc_ms = c->poa_arena.alloc_ms; }
+extern "C" void hx_poa_memory_stats(const hx_ctx* c, uint64_t* free_at_first_call, uint64_t* budget, uint64_t* last_call_workspace) {
+    *free_at_first_call = c->poa_free_at_first_call; *budget = c->poa_budget; *last_call_workspace = c->poa_last_workspace_bytes;
+}
+extern "C" void hx_poa_prune_stats(const hx_ctx* c, uint64_t* out4) {
+    for (int j = 0; j < 4; j++) out4[j] = 0;
+    const size_t PW_ = hxk::POA_PHASE_WORDS, ne = c->poa_phase.size() / PW_;
+    for (size_t e = 0; e < ne; e++) for (int j = 0; j < 4; j++) out4[j] += c->poa_phase[e * PW_ + 12 + j];
+}
+extern "C" void hx_set_poa_traceback(hx_ctx* c, int use_direction_bytes) { c->poa_no_dir = !use_direction_bytes; }
+extern "C" void hx_set_poa_block(hx_ctx* c, int t) { c->poa_block = t <= 0 ? 0 : t >= 1024 ? 1024 : t >= 512 ? 512 : t >= 256 ? 256 : t >= 128 ? 128 : 64; }

@@ -1,5 +1,5 @@
 // poa_dp.inl - part of kernels/poa.hip: the DP over (rank, column) - block / wave scans, row stores (nibbles through a buffer resource), the keys' constants, the mailboxes of the
-// wave pipeline, and dp_rows (the row loop, its pruned form and the fast-row switch).
+// wave pipeline, and dp_rows (the row loop and its pruned form).
 __device__ __forceinline__ int block_excl_scan_max(int v, int* lds /* blockDim/64 */) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int inc = wave_scan_max(v);
@@ -295,10 +295,7 @@ template <int CM> __device__ __forceinline__ void store_nibbles_buf(__amdgpu_buf
         // (8 columns per lane = the instances of the many-edge regime: the nibble rows leave as NON-TEMPORAL stores. A 13 000-edge call writes 0.45 TB of them, of
         // which the traceback reads back one byte in a few thousand; streamed past the L2 they leave it to the graph arrays and the far rows, whose round trips
         // are what the serial phases are made of - wave cycles of all workgroups of the 140 Mb call: -2.8 %. aux 2 = nt on gfx940/gfx950.)
-#ifndef HX_NIB_AUX
-#define HX_NIB_AUX 2
-#endif
-        if constexpr (CM == 8) __builtin_amdgcn_raw_buffer_store_b32(w[0], r, (int)off, 0, HX_NIB_AUX);
+        if constexpr (CM == 8) __builtin_amdgcn_raw_buffer_store_b32(w[0], r, (int)off, 0, 2);   // (aux 2: the non-temporal store)
         else if constexpr (CM == 16) { typedef uint32_t u32x2 __attribute__((ext_vector_type(2))); __builtin_amdgcn_raw_buffer_store_b64((u32x2){w[0], w[1]}, r, (int)off, 0, 0); }
         else { typedef uint32_t u32x4 __attribute__((ext_vector_type(4))); __builtin_amdgcn_raw_buffer_store_b128((u32x4){w[0], w[1], w[2], w[3]}, r, (int)off, 0, 0); }
     }
@@ -318,11 +315,6 @@ template <int CM> __device__ __forceinline__ void store_nibbles_buf(__amdgpu_buf
 // predecessor lives (registers / LDS ring / anything else), then straight-line code: rare events (row spilled to HBM, sink row) share
 // one not-taken branch, only rows with a non-adjacent reader are copied to the LDS ring (slot from the row's record), selects are
 // arithmetic.
-#ifdef HX_FARREAD_STORE   // (development: dead far-read rows store "nothing" and need a look, flags or not - as before the sticky far bit)
-#define HX_FARREAD_RISKY(fb) true
-#else
-#define HX_FARREAD_RISKY(fb) (!(fb))
-#endif
 template <int CM, bool DIR, bool PRUNE, bool ONEW /* the workgroup is one wave (the 64-lane instances): no LDS mailbox on either side, no relay - known at compile time, the row loses its tests of them */>
 __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uint8_t* __restrict__ D, uint8_t* __restrict__ Dwide, const uint32_t W, const uint32_t WH, const uint8_t* __restrict__ seq,
                         const uint32_t L_, const uint32_t V_, int32_t* ring, const uint32_t R_, const uint32_t ring_w_, const int match, const int mismatch, const int gap,
@@ -499,17 +491,6 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
     auto far_set = [&](const uint32_t slot, const uint32_t fl) {   // (slot, fl: wave-uniform)
         if (far_bits && lane == ((slot >> 5) & 63u)) farbits = (farbits & ~(1u << (slot & 31u))) | (fl << (slot & 31u));
     };
-#ifdef HX_RING_PREFETCH
-    // (development, round 6: the ring rows the NEXT row names as its first / second predecessor are requested while the current row is in its scan - an LDS round trip
-    // is ~100 cycles for a lone wave and a row makes 1.14 of them. pf_row = the row they were requested for.)
-    constexpr bool PF = !PRUNE && DIR;
-    int q0[CM], q0l = NEGK, q1[CM], q1l = NEGK;
-    uint32_t pf_row = 0xffffffffu, pf_s0 = 0xffu, pf_s1 = 0xffu;   // ... and the ring slots (location codes) they were read from
-#pragma unroll
-    for (int k = 0; k < CM; k++) { q0[k] = NEGK; q1[k] = NEGK; }
-#else
-    constexpr bool PF = false;
-#endif
     auto pred_row = [&](const uint32_t ent, int (&hp)[CM], int& left, const bool slot_known) {
         const uint32_t loc = ent >> 28;
         if (__builtin_expect(loc == 13u, 1)) {   // the previous row: registers (the likely case falls through: a taken scalar branch costs a lone wave ~35 cycles)
@@ -624,7 +605,7 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
                 // (codes 14 and 15 - the virtual row 0, a row in HBM - name something live only where this wave has their bit of FM set. A row that is itself read back
                 // from HBM needs a look only where the far rows have no flags: with them its bit is clear until somebody stores it live, and nobody fetches it)
                 auto outside = [&](const uint32_t ent) -> bool { const uint32_t c = ent >> 28; return c >= 14u && ((FM >> c) & 1u) != 0u; };
-                const bool risky = outside(aC) || (np_l > 1u && outside(bC)) || (np_l > 2u && outside(cC)) || (np_l > 3u && outside(dC)) || np_l > 4u || (HX_FARREAD_RISKY(far_bits) && (mC & 8u) != 0u);
+                const bool risky = outside(aC) || (np_l > 1u && outside(bC)) || (np_l > 2u && outside(cC)) || (np_l > 3u && outside(dC)) || np_l > 4u || (!far_bits && (mC & 8u) != 0u);
                 const bool clive = lane < nb && cinV >= thr_cin;
                 bad = (__builtin_amdgcn_ballot_w64(risky) >> rb) | __builtin_amdgcn_ballot_w64(clive);
                 if ((FM & 0x8000u) == 0u) {   // the rows that name a far row: they need a look from the moment one is stored live (below)
@@ -655,14 +636,10 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
             uint32_t rj0 = 0;
             if constexpr (PRUNE) rj0 = skip_run(0u);
             uint32_t meta_nx = __builtin_amdgcn_readlane(mC, (rb + rj0) & 63u), p0_nx = __builtin_amdgcn_readlane(aC, (rb + rj0) & 63u);
-            // The row, in two forms of one body. FAST (direction bytes, no pruning: the instances of the few-edge regime, where ONE wave's instruction count per row is
-            // what the call waits for) = a row whose record names ONE predecessor, the previous row: three rows in five. Such rows run in a loop of their own
-            // (below): the cells come straight out of the previous row's registers (as one of three sources joined in one set of registers the compiler copies them:
-            // six v_mov), the row format's constants are the 4-bit ones, and neither the dispatch on the first predecessor's location nor the branch around the
-            // later predecessors exists. (Round 5 tried the same cells as a block inside the one loop: + 14 %, through the two taken branches around it.)
+            // The row. (Round 6 measured a second form of it for the rows whose record names ONE predecessor, the previous row, run in a loop of their own - slower,
+            // see below; round 5 tried the same cells as a block inside the one loop: + 14 %, through the two taken branches around it. The code is in git history.)
             uint32_t rj = rj0;
-            auto row = [&](auto fast_tag) __attribute__((always_inline)) {
-                constexpr bool FAST = decltype(fast_tag)::value;
+            auto row = [&]() __attribute__((always_inline)) {
                 const uint32_t ri = rb + rj, i = ib + ri + 1;
                 const uint32_t meta = meta_nx, p0 = p0_nx;
                 const uint32_t npred = meta >> META_NP;
@@ -697,7 +674,7 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
                         }
                         if (__builtin_expect((meta & 8u) != 0u, 0)) {   // a far successor will read this row from HBM: keys of "nothing" (its flag is always taken for set)
                             const uint32_t fslot = __builtin_amdgcn_readlane(fC, ri);
-                            if (HX_FARREAD_RISKY(far_bits) && live) {   // (with flags: the row's bit is clear - every DP begins with none set - and nobody fetches an unflagged row)
+                            if (!far_bits && live) {   // (with flags: the row's bit is clear - every DP begins with none set - and nobody fetches an unflagged row)
                                 int32_t* F = H + (uint64_t)fslot * WH;
                                 int ng[CM];
 #pragma unroll
@@ -724,16 +701,11 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
                 // Move codes (the low 6 bits of a key while a row is computed; they are masked off before the row is used as a predecessor, so the
                 // format is the row's own). A row with at most 4 predecessors uses 4 bits - type * 4 + 3 - predecessor slot - which are its
                 // traceback nibble as they are; a "wide" row (rare) uses type * 16 + 15 - slot and stores a byte per cell in a side pool.
-                const bool wide = !FAST && (!DIR || (meta & 32u));   // (a fast row has one predecessor: never the wide format)
+                const bool wide = !DIR || (meta & 32u);
                 // (a diagonal move leaves the ramp of column j - 1 for that of column j; a finished key carries KHC; both formats' constants wait in
                 // scalar registers: one bit test and three selects per row)
                 const int md = wide ? mdW : mdN, gv = wide ? gvW : gvN, mmd = wide ? mdW + (mm64 - m64) : mdN + (mm64 - m64);
                 auto score_of = [&](int k) -> int {   // 64 x substitution score of column k + the diagonal move code
-                    if constexpr (CM <= 8 && FAST) {   // (the bit field through an asm statement: with constant terms around it the compiler turns one of the cells into v_and + v_cmp + two v_mov + v_cndmask)
-                        int bit;
-                        asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(bit) : "v"(hit), "n"((4 * k) & 31));
-                        return mmd + ((m64 - mm64) & bit);
-                    }
                     if constexpr (CM <= 8) return mmd + ((m64 - mm64) & __builtin_amdgcn_sbfe((int)hit, (4 * k) & 31, 1));   // (-1 on a match)
                     int neg;   // -1 on a mismatch, 0 on a match
                     if constexpr (CM <= 16) neg = __builtin_amdgcn_sbfe((int)mis, 2 * k, 1);
@@ -743,15 +715,7 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
                 hrow += WH;
                 DP_T(0);   // row decode
                 int m[CM];
-                if constexpr (FAST) {
-                    // (see the loops below: ONE predecessor, the previous row - its cells straight from the registers they are in, the 4-bit row format's constants,
-                    // no dispatch, nothing behind the cells to skip)
-                    const int left = wave_shift_up1(tp[CM - 1], lnp);
-#pragma unroll
-                    for (int k = 0; k < CM; k++) m[k] = max((k == 0 ? left : tp[k - 1]) + score_of(k), tp[k] + gv);
-                } else
                 if (!PRUNE || __builtin_expect(fl0 != 0u, 1)) {   // the first predecessor (or row 0): diagonal and vertical move
-#ifndef HX_NO_PREV_DIRECT
                     if (PRUNE && __builtin_expect((p0 >> 28) == 13u, 1)) {   // (PRUNE = the instances of the many-edge regime; the row of the 4-column instances a lone wave runs got 14 % SLOWER with this block: 292 -> 332 M cycles on the longest 12 Mb edge)
                         // the previous row: its cells straight from the registers they are in. (Through pred_row the three sources of a predecessor row join
                         // in ONE set of registers and the compiler copies the previous row into them - ten v_mov per row of the 8-column instances. The
@@ -761,16 +725,8 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
                         for (int k = 0; k < CM; k++) m[k] = max((k == 0 ? left : tp[k - 1]) + score_of(k), tp[k] + gv);
                         asm volatile("" : "+v"(m[CM - 1]));
                     } else
-#endif
                     {
                         int hp[CM], left;
-#ifdef HX_RING_PREFETCH
-                        if (PF && pf_row == i && pf_s0 == (p0 >> 28)) {
-#pragma unroll
-                            for (int k = 0; k < CM; k++) hp[k] = q0[k];
-                            left = q0l;
-                        } else
-#endif
                         pred_row(p0, hp, left, true);
 #pragma unroll
                         for (int k = 0; k < CM; k++) m[k] = max((k == 0 ? left : hp[k - 1]) + score_of(k), hp[k] + gv);
@@ -779,7 +735,7 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
 #pragma unroll
                     for (int k = 0; k < CM; k++) m[k] = NEGK;
                 }
-                if (!FAST && npred > 1) {   // (two rows in five at 25-45x)
+                if (npred > 1) {   // (two rows in five at 25-45x)
                     // the maximum over the predecessors: the low bits carry the move type and 15 - p, so ONE running maximum does it all
                     // (a diagonal beats a vertical move of the same score, the first predecessor in in-edge order beats the later ones).
                     // The second, third and fourth predecessor are spelled out - their entries come with the row records, one readlane each, and most of
@@ -805,20 +761,7 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
                             m[k] = max(m[k], max(dg, hp[k] + gvp));
                         }
                     };
-#ifdef HX_RING_PREFETCH
-                    const uint32_t entB_ = __builtin_amdgcn_readlane(bC, ri);
-                    if (PF && pf_row == i && pf_s1 == (entB_ >> 28)) {
-                        const int gvp = gv - 1;
-#pragma unroll
-                        for (int k = 0; k < CM; k++) {
-                            int dg;
-                            asm("v_add3_u32 %0, %1, %2, %3" : "=v"(dg) : "v"(k == 0 ? q1l : q1[k - 1]), "v"(score_of(k)), "s"(-1));
-                            m[k] = max(m[k], max(dg, q1[k] + gvp));
-                        }
-                    } else if (!PRUNE || flB != 0u) more(entB_, DIR ? 1 : 0, true);
-#else
                     if (!PRUNE || flB != 0u) more(__builtin_amdgcn_readlane(bC, ri), DIR ? 1 : 0, true);
-#endif
                     if (npred > 2) {
                         if (!PRUNE || flC != 0u) more(__builtin_amdgcn_readlane(cC, ri), DIR ? 2 : 0, false);
                         if (npred > 3) {
@@ -847,25 +790,7 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
                 DP_T(2);   // wave scan
                 const int cin = __builtin_amdgcn_readlane(cinV, rj);   // NEGK without a wave on the left
                 meta_nx = __builtin_amdgcn_readlane(mC, (ri + 1) & 63u);   // (the next row's record; beyond the batch: unused)
-                if constexpr (!FAST) p0_nx = __builtin_amdgcn_readlane(aC, (ri + 1) & 63u);   // (inside a run of fast rows the first predecessor is known; read again behind the run)
-#ifdef HX_RING_PREFETCH
-                if constexpr (PF) {   // the next row's ring predecessors (within the batch): requested now, used when the row comes
-                    pf_row = 0xffffffffu;
-                    if (rj + 1 < nb) {
-                        const uint32_t l0 = p0_nx >> 28, npn = meta_nx >> META_NP;
-                        const uint32_t entN = __builtin_amdgcn_readlane(bC, (ri + 1) & 63u), l1 = npn > 1u ? entN >> 28 : 0xffu;
-                        const bool r0 = l0 - 1u < 12u, r1 = l1 - 1u < 12u;
-                        if (r0 | r1) {
-                            const int32_t* S0 = ring_me + (size_t)(r0 ? l0 - 1u : 0u) * ring_w;
-                            const int32_t* S1 = ring_me + (size_t)(r1 ? l1 - 1u : 0u) * ring_w;
-#pragma unroll
-                            for (int k = 0; k < CM; k++) { q0[k] = S0[k * PW + 1]; q1[k] = S1[k * PW + 1]; }
-                            q0l = S0[(CM - 1) * PW]; q1l = S1[(CM - 1) * PW];
-                            pf_row = i + 1; pf_s0 = r0 ? l0 : 0xffu; pf_s1 = r1 ? l1 : 0xffu;
-                        }
-                    }
-                }
-#endif
+                p0_nx = __builtin_amdgcn_readlane(aC, (ri + 1) & 63u);
                 // the carry of this row for the wave on the right: the prefix maximum through this wave's last column (lane 63 holds it)
                 if (out_l != 0u) { if (lane == 63) *(volatile __attribute__((address_space(3))) unsigned long long*)(uintptr_t)mb_addr = (unsigned long long)mb_tag | ((unsigned long long)(uint32_t)max(cin, inc) << 32); }
                 if (out_h != 0u) { if (lane == 63) st_dev64(mb_out_h + i, (unsigned long long)mb_tag | ((unsigned long long)(uint32_t)max(cin, inc) << 32)); }
@@ -945,33 +870,9 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
             // Measured (round 6, 12 Mb, A/B of two builds in one GPU call): SLOWER - the longest edge's DP 284 -> 322 M cycles, the step 164 -> 180 ms. Its 303 916 rows
             // are 42 % rows with several predecessors, 30 % rows whose one predecessor sits in the ring (bubbles interleave in rank order), and only 28 % fast rows, in
             // runs of 1.3: what a run costs to set up (mask shift, count, the first predecessor's entry read again: ~100 cycles) and what every other row pays for the
-            // test is more than the ~25 instructions a fast row saves. Kept behind -DHX_FAST_ROWS (off) as the measured alternative it is.
-#ifdef HX_FAST_ROWS
-            constexpr bool FAST_OK = DIR && !PRUNE;
-#else
-            constexpr bool FAST_OK = false;
-#endif
-            // fast <=> one predecessor (meta >> META_NP == 1) with the location code 13 (the previous row). Which rows of the batch are is read off the 64 records in
-            // their lanes ONCE, as a mask (bit r = row i0 + r, nothing beyond the batch); a run of fast rows is then a counted loop - its back edge is s_sub + s_cmp +
-            // one branch (as a test of the next row's record after every row it was a flag-guarded pair of branches and five scalar instructions).
-            unsigned long long fastm = 0;
-            if constexpr (FAST_OK) {
-                fastm = __builtin_amdgcn_ballot_w64(((mC >> META_NP) << 4 | (aC >> 28)) == (1u << 4 | 13u)) >> rb;
-                if (nb < 64u) fastm &= (1ull << nb) - 1ull;
-            }
+            // test is more than the ~25 instructions a fast row saves. The code is in git history.
             while (rj < nb) {
-                if constexpr (FAST_OK) {
-                    // (bit nb - rj of the complement is set, so the run ends with the batch at the latest - except for a batch of 64 fast rows seen from its first
-                    // row: the complement is zero there, and the count of trailing zeros of zero is not 64 but whatever the instruction leaves)
-                    const unsigned long long inv = ~(fastm >> rj);
-                    uint32_t run = inv ? (uint32_t)__builtin_ctzll(inv) : 64u;
-                    if (__builtin_expect(run != 0u, 1)) {
-                        do { row(std::true_type{}); rj++; } while (--run != 0u);
-                        p0_nx = __builtin_amdgcn_readlane(aC, (rb + rj) & 63u);
-                        continue;
-                    }
-                }
-                row(std::false_type{});
+                row();
                 rj++;
             }
             if constexpr (PRUNE) lazy = (uint32_t)(n_dead - dead_before == nb) & lazy_on;

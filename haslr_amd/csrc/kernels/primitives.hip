@@ -201,7 +201,7 @@ void radix_sort_pairs(uint64_t* key, uint32_t* val, uint64_t* key_tmp, uint32_t*
     }
 }
 
-// Consensus collection (hx_api.hip collect_batch): the kernels leave every edge's string at its own offset of a buffer sized by the node ESTIMATES (a
+// Consensus collection (hx_poa.hip collect_batch): the kernels leave every edge's string at its own offset of a buffer sized by the node ESTIMATES (a
 // hundred megabytes for 13 000 edges); the finished strings are moved side by side before they cross PCIe. One workgroup per string;
 // desc = (source offset lo / hi, destination offset lo / hi, length).
 __global__ void __launch_bounds__(256) k_gather_bytes(const char* __restrict__ src, const uint32_t* __restrict__ desc, char* __restrict__ dst) {
@@ -215,7 +215,7 @@ void gather_bytes(const char* src, const uint32_t* desc, uint32_t n_items, char*
 }
 
 // One wave with as much private memory per lane as the largest k_poa instance spills (kernels/poa.hip: 288 to 928 bytes per lane): run once on a
-// stream, it takes the stream's hardware queue to that scratch size. See hx_api.hip (poa_scratch_warm) for why.
+// stream, it takes the stream's hardware queue to that scratch size. See hx_poa.hip (scratch_warm_once) for why.
 __global__ void __launch_bounds__(64) k_scratch_warm(uint32_t* out, uint32_t n) {
     volatile uint32_t a[256];
     for (uint32_t i = 0; i < 256; i++) a[i] = i * n;

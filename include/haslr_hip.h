@@ -54,9 +54,9 @@ void hx_ctx_destroy(hx_ctx*);
  *                    poa_prune (exact score-bound pruning of the DP: -1 automatic = calls of thousands of edges, 0 never, else the threshold as a
  *                    percentage of the previous alignment's score per base), launch-shape knobs (poa_cols, poa_cols2_top, poa_member_lanes, poa_cluster_min /
  *                    _max / _topk / _cols, poa_wide_members, poa_wave_max, poa_ring_kb, poa_balance, poa_balance_pct, poa_balance_lanes, poa_streams,
- *                    poa_wide_delay_us, poa_prune_lanes, poa_prune_shared, poa_prune_lazy, poa_order_by_cells, poa_pass_lanes, poa_chain_ms, poa_chain_pct, poa_big_first,
- *                    poa_slots_by_work, poa_bucket_half_octaves, poa_own_bucket_first, poa_resident_first, poa_far_shift, poa_scratch_warm) and test switches that force rare paths (poa_poll_limit, poa_max_indeg, poa_node_est_pct,
- *                    poa_far_rows, poa_ring_zero, poa_slots, poa_slots_pct, poa_batches, poa_force_cm, poa_no_xcd_map, coords_lds_supp), and two of the
+ *                    poa_wide_delay_us, poa_prune_lanes, poa_prune_shared, poa_prune_lazy, poa_pass_lanes, poa_chain_ms, poa_chain_pct,
+ *                    poa_own_bucket_first, poa_resident_first, poa_far_shift) and test switches that force rare paths (poa_poll_limit, poa_max_indeg, poa_node_est_pct,
+ *                    poa_far_rows, poa_ring_zero, poa_slots, poa_slots_pct, poa_batches, poa_force_cm, coords_lds_supp), and two of the
  *                    general POA path (hx_poa_sequences_mode): poa_general (1: HX_POA_NW runs the general path too) and poa_modes_slot_kb (cap of
  *                    its first round of workspace slots, forcing the rerun of sets in larger ones).
  *                    Results never depend on any of them. */
@@ -164,7 +164,7 @@ int hx_poa_release_workspace(hx_ctx*);
  * 80 % of the device memory that is free at the time is taken (and no more than option poa_workspace_gb allows, when it is set); hx_upload gives the arena back if the inputs do not fit beside it; a call that needs more
  * than was reserved allocates again. Thread-safe against the operators of the same context. The first reservation (or, without one, the first consensus call) of a
  * process also takes the hardware queues of the launch streams to the scratch size the largest kernel instance asks for - one wave each, once per process and
- * device (option poa_scratch_warm=0: not): queues that grow their scratch in the middle of a call hold some of its launches back.
+ * device: queues that grow their scratch in the middle of a call hold some of its launches back.
  *   hx_poa_host_times   host wall time (ms) of the LAST consensus call, by part: [0] plan, [1] workspace (arena allocation + carving), [2] enqueue
  *                       (tables to the device, launches), [3] waiting for the device, [4] collection (status + consensus strings), [5] results
  *                       assembled, [6] unused, [7] the whole call

@@ -671,7 +671,7 @@ def test_configs4_share_full_size_properties(sim, ctx, tmp_path):
         # 7.75 x this data set). Second pass at that shape for real: the workspace is released, a device BALLAST brings what is resident beside it to
         # 82 GB, the budget is taken again from what hipMemGetInfo reports free (no option caps it) - same consensus, same assembly. Third pass under
         # real shortage: more ballast until less is free than the workspace wanted, so the slot counts of the launch classes are scaled down until the
-        # pools fit (hx_api.hip plan_batches / slots_wanted): the path a rank of a 288 GB device takes when its input share grows.
+        # pools fit (hx_poa_plan.hip plan_batches / slots_wanted): the path a rank of a 288 GB device takes when its input share grows.
         resident = {"packed_read_bytes": int(ds.reads.off[ds.reads.n]), "cigar_word_bytes": 4 * int(ds.hits.cg_off[ds.hits.n]), "paf_records": int(ds.hits.n),
                     "read_bases": int(ds.total_read_bases), "poa_workspace_bytes_unconstrained": int(ws_free)}
         ballast = util.DeviceBallast(0)

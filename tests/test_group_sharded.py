@@ -205,7 +205,7 @@ def test_edge_merge_through_the_c_abi_equals_edge_support(sim, built):
 def test_a_failure_inside_the_collective_ends_the_exchange_with_an_error(sim, built):
     """a rank whose all-gather fails (injected: hx_group_inject_fault) raises the group's abort flag instead of leaving anybody parked on a stream: the
     call returns the error, and the group refuses further exchanges. One rank over real RCCL (the only world size a one-GPU box can run it at); the
-    ranks that would be WAITING in a larger group take the same bounded-poll path (hx_api.hip hx_edge_merge)."""
+    ranks that would be WAITING in a larger group take the same bounded-poll path (hx_group.hip hx_edge_merge)."""
     from haslr_amd import hip
     pre = sim("--genome-len", "150000", "--seed", "21", "--variant-per-mb", "30")
     ds = host.Dataset(pre + ".contigs.fa", pre + ".reads.fa", pre + ".paf")
