@@ -152,6 +152,7 @@ struct HxOptions {
     int poa_prune_lanes = 128;     // ... in launches of workgroups of at least this many lanes (a one-wave workgroup has no block to skip)
     int coords_lds_supp = -1;      // supports per edge the coordinate kernel sorts in LDS (testing: 0 sends every edge through the global scratch)
     int poa_general = 0;           // hx_poa_sequences_mode with HX_POA_NW runs the general path (kernels/poa_modes.hip) instead of the tuned one: the cross-check of what the modes share with kNW
+    int poa_affine = 0;            // hx_poa_sequences_affine with gap_extend == gap_open runs the affine instances of the general path instead of the linear paths: the cross-check of the affine kernel against the linear ones
     int poa_modes_slot_kb = 0;     // the general path's first round of slots holds at most this many KB (testing: forces the overflow and the rerun in a larger slot; 0 no cap)
 };
 
@@ -225,7 +226,7 @@ struct hx_ctx {
     // POA workspace lives as long as the context: allocating tens of GB per call costs more than the kernel
     hxi::PoaPoolBufs poa_pools;
     hxi::PoaArena poa_arena;
-    hxk::PoaModesWs poa_modes_ws;       // workspace of the general path (hx_poa_sequences_mode: kSW / kOV, and kNW under option poa_general)
+    hxk::PoaModesWs poa_modes_ws;       // workspace of the general path (hx_poa_sequences_mode: kSW / kOV, and kNW under option poa_general; hx_poa_sequences_affine)
     std::mutex poa_arena_mu;            // hx_poa_reserve may run on a thread of its own beside the upload and the first stages
     double poa_host_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // host wall time of the last consensus call: plan, workspace, enqueue, device wait, collect, finish, (unused), total
     uint64_t poa_budget = 0;

@@ -428,16 +428,12 @@ extern "C" int hx_poa_sequences(hx_ctx* c, uint32_t n_sets, const uint64_t* set_
     return rc;
 }
 
-extern "C" int hx_poa_sequences_mode(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_mode_params* mp, hx_cns_out* out) {
-    memset(out, 0, sizeof(*out));
-    if (!mp) return fail("hx_poa_sequences_mode: no parameters");
-    if (mp->gap >= 0) return fail("hx_poa_sequences_mode: the gap score must be negative (linear gap penalty), not " + std::to_string(mp->gap));
-    if (mp->type != HX_POA_SW && mp->type != HX_POA_NW && mp->type != HX_POA_OV) return fail("hx_poa_sequences_mode: unknown alignment type " + std::to_string(mp->type) + " (HX_POA_SW 0, HX_POA_NW 1, HX_POA_OV 2)");
-    if (set_off[n_sets] >= 0x7fffffffULL) return fail("hx_poa_sequences_mode: too many sequences");
-    const hx_poa_params pp{mp->match, mp->mismatch, mp->gap};
-    if (mp->type == HX_POA_NW && !c->opt.poa_general) return hx_poa_sequences(c, n_sets, set_off, seq_off, bases, &pp, out);   // the tuned global path
+// the general path (kernels/poa_modes.hip) for one call: linear instances, or the affine ones with gap = gap open
+static int poa_general_call(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, int32_t match, int32_t mismatch, int32_t gap,
+                            int32_t gap_extend, int affine, int32_t type, hx_cns_out* out) {
     HIPCHK(hipSetDevice(c->device));
-    const hxk::PoaModesArgs a{n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap, mp->type, (uint32_t)std::max(0, c->opt.poa_modes_slot_kb), c->opt.poa_workspace_gb, c->opt.debug};
+    hxk::PoaModesArgs a{n_sets, set_off, seq_off, bases, match, mismatch, gap, type, (uint32_t)std::max(0, c->opt.poa_modes_slot_kb), c->opt.poa_workspace_gb, c->opt.debug};
+    a.gap_extend = gap_extend; a.affine = affine;
     hxk::PoaModesOut o;
     std::string err;
     if (hxk::poa_modes_run(c->stream, c->poa_modes_ws, a, o, err)) return fail(err);
@@ -446,8 +442,35 @@ extern "C" int hx_poa_sequences_mode(hx_ctx* c, uint32_t n_sets, const uint64_t*
     out->cns_off = (uint64_t*)malloc(((size_t)n_sets + 1) * 8); memcpy(out->cns_off, o.cns_off.data(), ((size_t)n_sets + 1) * 8);
     out->cns = (char*)malloc(std::max<size_t>(1, o.cns.size())); memcpy(out->cns, o.cns.data(), o.cns.size());
     out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
-    if (c->opt.debug) fprintf(stderr, "[hx] POA modes call: %u sets, %.3g cells, kernels %.2f ms, %u sets rerun in a larger slot\n", n_sets, (double)o.cells, o.kernel_ms, o.retried);
+    if (c->opt.debug) fprintf(stderr, "[hx] POA modes call%s: %u sets, %.3g cells, kernels %.2f ms, %u sets rerun in a larger slot\n", affine ? " (affine)" : "", n_sets, (double)o.cells, o.kernel_ms, o.retried);
     return 0;
+}
+
+extern "C" int hx_poa_sequences_mode(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_mode_params* mp, hx_cns_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!mp) return fail("hx_poa_sequences_mode: no parameters");
+    if (mp->gap >= 0) return fail("hx_poa_sequences_mode: the gap score must be negative (linear gap penalty), not " + std::to_string(mp->gap));
+    if (mp->type != HX_POA_SW && mp->type != HX_POA_NW && mp->type != HX_POA_OV) return fail("hx_poa_sequences_mode: unknown alignment type " + std::to_string(mp->type) + " (HX_POA_SW 0, HX_POA_NW 1, HX_POA_OV 2)");
+    if (set_off[n_sets] >= 0x7fffffffULL) return fail("hx_poa_sequences_mode: too many sequences");
+    const hx_poa_params pp{mp->match, mp->mismatch, mp->gap};
+    if (mp->type == HX_POA_NW && !c->opt.poa_general) return hx_poa_sequences(c, n_sets, set_off, seq_off, bases, &pp, out);   // the tuned global path
+    return poa_general_call(c, n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap, mp->gap, 0, mp->type, out);
+}
+
+extern "C" int hx_poa_sequences_affine(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_affine_params* ap, hx_cns_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!ap) return fail("hx_poa_sequences_affine: no parameters");
+    if (ap->gap_open >= 0) return fail("hx_poa_sequences_affine: the gap open score must be negative, not " + std::to_string(ap->gap_open));
+    if (ap->gap_extend > 0) return fail("hx_poa_sequences_affine: the gap extend score must not be positive, not " + std::to_string(ap->gap_extend));
+    // (spoa is said to fall back to its linear engine here, silently; that cannot be checked without the library, so the call is refused)
+    if (ap->gap_extend < ap->gap_open) return fail("hx_poa_sequences_affine: the gap extend score " + std::to_string(ap->gap_extend) + " is below the gap open score " + std::to_string(ap->gap_open) + " (extending a gap must not cost more than opening one)");
+    if (ap->type != HX_POA_SW && ap->type != HX_POA_NW && ap->type != HX_POA_OV) return fail("hx_poa_sequences_affine: unknown alignment type " + std::to_string(ap->type) + " (HX_POA_SW 0, HX_POA_NW 1, HX_POA_OV 2)");
+    if (set_off[n_sets] >= 0x7fffffffULL) return fail("hx_poa_sequences_affine: too many sequences");
+    if (ap->gap_extend == ap->gap_open && !c->opt.poa_affine) {   // the linear model: the linear paths (kNW keeps the tuned one)
+        const hx_poa_mode_params mp{ap->match, ap->mismatch, ap->gap_open, ap->type};
+        return hx_poa_sequences_mode(c, n_sets, set_off, seq_off, bases, &mp, out);
+    }
+    return poa_general_call(c, n_sets, set_off, seq_off, bases, ap->match, ap->mismatch, ap->gap_open, ap->gap_extend, 1, ap->type, out);
 }
 
 extern "C" void hx_free_cns(hx_ctx*, hx_cns_out* o) { free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }

@@ -1,5 +1,5 @@
-// poa_modes.h — host side of the general POA path (kernels/poa_modes.hip): spoa's linear-gap engine in its three alignment modes
-// (kSW local, kNW global, kOV overlap) for caller-given sequence sets, one workgroup per set. DESIGN.md "General POA path".
+// poa_modes.h — host side of the general POA path (kernels/poa_modes.hip): spoa's linear-gap and affine-gap engines in their three
+// alignment modes (kSW local, kNW global, kOV overlap) for caller-given sequence sets, one workgroup per set. DESIGN.md "General POA path".
 #ifndef HX_POA_MODES_H
 #define HX_POA_MODES_H
 #include <hip/hip_runtime.h>
@@ -25,6 +25,8 @@ struct PoaModesArgs {
     uint32_t slot_kb_cap;                // first round only: workspace slots of at most this many KB (0: no cap); sets that overflow are rerun in larger slots
     double workspace_gb;                 // cap of the workspace (0: 40 % of the free device memory)
     int debug;
+    int32_t gap_extend = 0;              // affine calls: gap is the gap open score, this the gap extend score (gap <= gap_extend <= 0)
+    int affine = 0;                      // 1: the affine instances (a cell is an (H, F) pair, sequences of up to 16383 bases)
 };
 
 struct PoaModesOut {

@@ -1,5 +1,6 @@
 // poa_modes.hip — the general POA path: spoa's linear-gap engine in its three alignment modes (kSW local, kNW global, kOV overlap) for
-// caller-given sequence sets (hx_poa_sequences_mode; DESIGN.md "General POA path" has the semantics and the mapping).
+// caller-given sequence sets (hx_poa_sequences_mode; DESIGN.md "General POA path" has the semantics and the mapping), and the affine-gap
+// engine in the same modes (hx_poa_sequences_affine; k_poa_affine below: same mapping, a cell is the pair (H, F), its own instance table).
 //
 // It is a kernel family of its own beside the tuned global-only k_poa (kernels/poa.hip), which depends on kNW throughout (de-ramped keys
 // with tie bits, score-bound pruning, sink lists, end-node ties decided on closures, multi-member pipelines). What the modes share with
@@ -44,6 +45,7 @@ struct MArgs {
     uint8_t* ws; uint64_t slot_bytes;
     int32_t m, n, g, type;
     char* cns; uint32_t *cns_len, *status, *vseen; unsigned long long* cells;
+    int32_t e;   // affine instances only: gap extend (g is gap open)
 };
 
 __host__ __device__ inline uint64_t al256(uint64_t x) { return (x + 255) & ~255ull; }
@@ -238,7 +240,150 @@ __device__ uint32_t traceback(G& g, const int32_t* H, const uint8_t* s, const ui
     return anypos ? na : 0u;
 }
 
+// ---- affine gaps (DESIGN.md "General POA path", "Affine gaps"): gap open a.g, gap extend a.e, g <= e <= 0 ----
+// A cell of the matrix is the pair (H, F). E is not stored: a row needs it only in registers, and the traceback rebuilds it as it walks.
+//
+// DP row: per predecessor, H[p][j-1] + sigma is folded into the diagonal candidate and max(H[p][j] + g, F[p][j] + e) into F. With
+// X[k] = max(diagonal, F) of column k (kSW: clamped at 0; column 0: H[r][0]) the horizontal recurrence E[j] = max(H[j-1] + g, E[j-1] + e),
+// H[j] = max(X[j], E[j]) unrolls to E[j] = g + (j-1) e + max over k < j of (X[k] - k e): a term that passes through an E[k] on its way
+// (H[k] = E[k]) pays g where the direct term from the same X[k'] pays e, and g <= e, so it never wins. e = 0 needs nothing else (the
+// argument uses g <= e only), and the kSW clamp commutes with the maximum: max(X[k], E[k], 0) = max(max(X[k], 0), E[k]). So E is the
+// linear path's prefix maximum made exclusive.
 template <int NT, int CPL>
+__device__ void dp_rows_affine(const G& g, int2* HF, const uint32_t V, const uint8_t* s, const uint32_t L, const MArgs& a, Shared& sh, int* s_wtot,
+                               uint32_t* bi_out, uint32_t* bj_out) {
+    constexpr int NEG2 = -(1 << 30);
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    const uint32_t W = L + 1, j0 = t * CPL;
+    const int32_t m = a.m, n = a.n, go = a.g, ge = a.e;
+    const int type = a.type;
+    uint32_t sq[(CPL + 15) / 16];
+#pragma unroll
+    for (int q = 0; q < (CPL + 15) / 16; q++) sq[q] = 0;
+#pragma unroll
+    for (int k = 0; k < CPL; k++) { const uint32_t j = j0 + k; if (j >= 1 && j <= L) sq[k >> 4] |= (uint32_t)s[j - 1] << (2 * (k & 15)); }
+#pragma unroll
+    for (int k = 0; k < CPL; k++) { const uint32_t j = j0 + k; if (j <= L) HF[j] = make_int2(type == MT_NW && j ? go + ((int32_t)j - 1) * ge : 0, NEG); }
+    __syncthreads();
+    int32_t bv = type == MT_SW ? 0 : NEG;
+    uint32_t bi = 0, bj = 0;
+    uint32_t meta = g.row_meta[0], off = g.row_pred_off[0];
+    for (uint32_t i = 1; i <= V; i++) {
+        const uint32_t cmeta = meta, coff = off;
+        if (i < V) { meta = g.row_meta[i]; off = g.row_pred_off[i]; }
+        const uint32_t np = cmeta >> META_NP, code = cmeta & 3u;
+        const bool sink = (cmeta & 4u) != 0;
+        int32_t x[CPL], f[CPL];
+#pragma unroll
+        for (int k = 0; k < CPL; k++) { x[k] = NEG; f[k] = NEG; }
+        const uint32_t npp = np ? np : 1u;
+        for (uint32_t p = 0; p < npp; p++) {
+            const uint32_t prow = np ? g.pred_rank[coff + p] + 1u : 0u;
+            const int2* hp = HF + (size_t)prow * W;
+            int32_t left = j0 >= 1 && j0 <= W ? hp[j0 - 1].x : NEG;
+#pragma unroll
+            for (int k = 0; k < CPL; k++) {
+                const uint32_t j = j0 + k;
+                if (j <= L) {
+                    const int2 v = hp[j];
+                    const int32_t sg = ((sq[k >> 4] >> (2 * (k & 15))) & 3u) == code ? m : n;
+                    x[k] = max(x[k], left + sg);
+                    f[k] = max(f[k], max(v.x + go, v.y + ge));
+                    left = v.x;
+                }
+            }
+        }
+        if (type != MT_NW && j0 == 0) { x[0] = 0; f[0] = NEG; }   // column 0 of kSW / kOV: H = 0, F = -inf (kNW: H[r][0] = F[r][0], which the fold gave)
+#pragma unroll
+        for (int k = 0; k < CPL; k++) { x[k] = max(x[k], f[k]); if (type == MT_SW) x[k] = max(x[k], 0); }
+        // y[k] = X[k] - j e, its in-lane inclusive prefix maximum, then the exclusive carry of the lanes before
+        int32_t y[CPL];
+#pragma unroll
+        for (int k = 0; k < CPL; k++) { y[k] = x[k] - (int32_t)(j0 + k) * ge; if (k) y[k] = max(y[k], y[k - 1]); }
+        const int incl = wave_scan_max(y[CPL - 1]);
+        int carry = wave_shift_up1(incl, NEG2);
+        if (NT > 64) {
+            if (lane == 63) s_wtot[w] = incl;
+            __syncthreads();
+            for (uint32_t q = 0; q < w; q++) carry = max(carry, s_wtot[q]);
+        }
+        int2* row = HF + (size_t)i * W;
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            const uint32_t j = j0 + k;
+            const int32_t ex = k ? max(carry, y[k - 1]) : carry;           // max over columns < j of X - k e
+            const int32_t h = max(x[k], ex + go + ((int32_t)j - 1) * ge);  // (column 0: ex is the identity, E stays below every real value)
+            if (j <= L) {
+                row[j] = make_int2(h, f[k]);
+                const bool cand = j >= 1 && (type == MT_SW || (type == MT_NW ? sink && j == L : sink || j == L));
+                if (cand && h > bv) { bv = h; bi = i; bj = j; }
+            }
+        }
+        __syncthreads();
+    }
+    if (t == 0) { sh.best = type == MT_SW ? 0 : NEG; sh.key = ~0ull; }
+    __syncthreads();
+    if (bi) atomicMax(&sh.best, bv);
+    __syncthreads();
+    if (bi && bv == sh.best) atomicMin(&sh.key, ((unsigned long long)bi << 32) | bj);
+    __syncthreads();
+    const unsigned long long key = sh.key;
+    *bi_out = key == ~0ull ? 0u : (uint32_t)(key >> 32);
+    *bj_out = key == ~0ull ? 0u : (uint32_t)key;
+    __syncthreads();
+}
+
+// the affine traceback: a walk with a state (H, F or E); thread 0. E of the current cell is carried in ev: state E is entered where
+// H == E, and E[i][j-1] = E[i][j] - e wherever E[i][j] != H[i][j-1] + g. Same output layout as traceback().
+__device__ uint32_t traceback_affine(G& g, const int2* HF, const uint8_t* s, const uint32_t L, uint32_t i, uint32_t j, const MArgs& a) {
+    const uint32_t W = L + 1;
+    uint32_t na = 0;
+    bool anypos = false;
+    int st = 0;   // 0 H, 1 F, 2 E
+    int32_t ev = 0;
+    for (;;) {
+        const int2 c = HF[(size_t)i * W + j];
+        uint32_t np = 0, off = 0, code = 0;
+        if (i != 0) { const uint32_t meta = g.row_meta[i - 1]; np = meta >> META_NP; off = g.row_pred_off[i - 1]; code = meta & 3u; }
+        const uint32_t npp = np ? np : 1u;
+        if (st == 0) {
+            if (a.type == MT_SW ? c.x == 0 : a.type == MT_NW ? (i == 0 && j == 0) : (i == 0 || j == 0)) break;
+            bool ok = false;
+            if (i != 0 && j != 0) {
+                const int32_t sg = s[j - 1] == code ? a.m : a.n;
+                for (uint32_t p = 0; p < npp && !ok; p++) {
+                    const uint32_t prow = np ? g.pred_rank[off + p] + 1u : 0u;
+                    if (c.x == HF[(size_t)prow * W + j - 1].x + sg) {
+                        g.aln_node[na] = (int32_t)g.rank2node[i - 1]; g.aln_pos[na] = (int32_t)(j - 1); na++;
+                        anypos = true; i = prow; j--; ok = true;
+                    }
+                }
+            }
+            if (!ok) { if (i != 0 && c.x == c.y) st = 1; else { st = 2; ev = c.x; } }
+        } else if (st == 1) {
+            bool ok = false;
+            for (uint32_t p = 0; p < npp && !ok; p++) {
+                const uint32_t prow = np ? g.pred_rank[off + p] + 1u : 0u;
+                const int2 v = HF[(size_t)prow * W + j];
+                const bool open = c.y == v.x + a.g;
+                if (open || c.y == v.y + a.e) {
+                    g.aln_node[na] = (int32_t)g.rank2node[i - 1]; g.aln_pos[na] = -1; na++;
+                    i = prow; st = open ? 0 : 1; ok = true;
+                }
+            }
+            if (!ok) break;   // (cannot happen on a consistent matrix)
+        } else {
+            if (j == 0) break;   // (cannot happen on a consistent matrix)
+            g.aln_node[na] = -1; g.aln_pos[na] = (int32_t)(j - 1); na++;
+            anypos = true;
+            if (ev == HF[(size_t)i * W + j - 1].x + a.g) st = 0; else ev -= a.e;
+            j--;
+        }
+    }
+    return anypos ? na : 0u;
+}
+
+template <int NT, int CPL, bool AFF = false>
 __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Shared& sh, int* s_wtot, uint32_t* s_scan) {
     const uint32_t t = threadIdx.x;
     const MSet S = a.sets[set];
@@ -246,7 +391,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     const uint64_t pools = carve_pools(slot, S.sum_len, S.nseq, S.lmax, &g, &path, &colref);
     if (pools > a.slot_bytes) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
     int32_t* H = (int32_t*)(slot + pools);
-    const uint64_t hcap = (a.slot_bytes - pools) / 4;
+    const uint64_t hcap = (a.slot_bytes - pools) / (AFF ? 8 : 4);   // cells the slot holds (affine: an (H, F) pair each)
     uint32_t V = 0, E = 0, non_empty = 0;
     unsigned long long cells = 0;
     for (uint32_t k = 0; k < S.nseq; k++) {
@@ -260,8 +405,13 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
             if ((uint64_t)(V + 1) * (L + 1) > hcap) { if (t == 0) { a.status[set] = MS_H_OVERFLOW; a.vseen[set] = V; } return; }
             cells += (unsigned long long)V * L;
             uint32_t bi, bj;
-            dp_rows<NT, CPL>(g, H, V, s, L, a, sh, s_wtot, &bi, &bj);
-            if (t == 0 && bi) na = traceback(g, H, s, L, bi, bj, a);
+            if (AFF) {
+                dp_rows_affine<NT, CPL>(g, (int2*)H, V, s, L, a, sh, s_wtot, &bi, &bj);
+                if (t == 0 && bi) na = traceback_affine(g, (const int2*)H, s, L, bi, bj, a);
+            } else {
+                dp_rows<NT, CPL>(g, H, V, s, L, a, sh, s_wtot, &bi, &bj);
+                if (t == 0 && bi) na = traceback(g, H, s, L, bi, bj, a);
+            }
         }
         if (t == 0) {
             uint32_t v = V, e = E;
@@ -296,6 +446,22 @@ __global__ __launch_bounds__(NT) void k_poa_modes(MArgs a) {
     }
 }
 
+template <int NT, int CPL>
+__global__ __launch_bounds__(NT) void k_poa_affine(MArgs a) {
+    __shared__ Shared sh;
+    __shared__ int s_wtot[NT / 64];
+    __shared__ uint32_t s_scan[NT / 64];
+    uint8_t* slot = a.ws + (size_t)blockIdx.x * a.slot_bytes;
+    for (;;) {
+        if (threadIdx.x == 0) sh.item = atomicAdd(a.counter, 1u);
+        __syncthreads();
+        const uint32_t q = sh.item;
+        __syncthreads();
+        if (q >= a.n_items) return;
+        run_set<NT, CPL, true>(a, a.order[q], slot, sh, s_wtot, s_scan);
+    }
+}
+
 // the instances: workgroup lanes x columns per lane; a set goes to the first whose NT x CPL columns hold its longest sequence + 1
 struct Inst { int nt, cpl; const void* fn; };
 const Inst kInst[] = {
@@ -306,6 +472,14 @@ const Inst kInst[] = {
 };
 constexpr int N_INST = sizeof(kInst) / sizeof(kInst[0]);
 constexpr uint32_t MAX_LEN = 1024 * 32 - 1;
+// the affine instances keep two accumulators per column (diagonal and F): 16 columns per lane throughout, more lanes instead
+const Inst kInstAffine[N_INST] = {
+    {64, 16, (const void*)k_poa_affine<64, 16>},
+    {256, 16, (const void*)k_poa_affine<256, 16>},
+    {512, 16, (const void*)k_poa_affine<512, 16>},
+    {1024, 16, (const void*)k_poa_affine<1024, 16>},
+};
+constexpr uint32_t MAX_LEN_AFFINE = 1024 * 16 - 1;
 
 void launch(int inst, uint32_t blocks, const MArgs& a, hipStream_t s) {
     switch (inst) {
@@ -313,6 +487,15 @@ void launch(int inst, uint32_t blocks, const MArgs& a, hipStream_t s) {
         case 1: k_poa_modes<256, 16><<<blocks, 256, 0, s>>>(a); break;
         case 2: k_poa_modes<256, 32><<<blocks, 256, 0, s>>>(a); break;
         default: k_poa_modes<1024, 32><<<blocks, 1024, 0, s>>>(a); break;
+    }
+}
+
+void launch_affine(int inst, uint32_t blocks, const MArgs& a, hipStream_t s) {
+    switch (inst) {
+        case 0: k_poa_affine<64, 16><<<blocks, 64, 0, s>>>(a); break;
+        case 1: k_poa_affine<256, 16><<<blocks, 256, 0, s>>>(a); break;
+        case 2: k_poa_affine<512, 16><<<blocks, 512, 0, s>>>(a); break;
+        default: k_poa_affine<1024, 16><<<blocks, 1024, 0, s>>>(a); break;
     }
 }
 
@@ -328,6 +511,11 @@ template <class T> struct Buf {   // device buffer of one call
 
 int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModesOut& o, std::string& err) {
     const uint32_t ns = a.n_sets;
+    const bool aff = a.affine != 0;
+    const Inst* const inst = aff ? kInstAffine : kInst;
+    const uint32_t max_len = aff ? MAX_LEN_AFFINE : MAX_LEN;
+    const uint64_t cell_bytes = aff ? 8 : 4;   // affine: an (H, F) pair per cell
+    const std::string who = aff ? "hx_poa_sequences_affine" : "hx_poa_sequences_mode";
     const uint64_t nseq = a.set_off[ns], nb = a.seq_off[nseq];
     std::vector<MSet> sets(ns);
     std::vector<uint64_t> cns_off((size_t)ns + 1, 0);
@@ -337,11 +525,11 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
         S.seq_begin = a.set_off[i]; S.nseq = (uint32_t)(a.set_off[i + 1] - a.set_off[i]); S.sum_len = 0; S.lmax = 0;
         for (uint64_t k = a.set_off[i]; k < a.set_off[i + 1]; k++) {
             const uint64_t L = a.seq_off[k + 1] - a.seq_off[k];
-            if (L > MAX_LEN) { err = "hx_poa_sequences_mode: set " + std::to_string(i) + " holds a sequence of " + std::to_string(L) + " bases, longer than " + std::to_string(MAX_LEN) + " (the longest the general POA path takes)"; return -1; }
+            if (L > max_len) { err = who + ": set " + std::to_string(i) + " holds a sequence of " + std::to_string(L) + " bases, longer than " + std::to_string(max_len) + (aff ? " (the longest the general POA path takes with affine gaps)" : " (the longest the general POA path takes)"); return -1; }
             S.sum_len += L; S.lmax = std::max(S.lmax, (uint32_t)L);
             o.seq_bases += L; o.n_aligned += L != 0;
         }
-        if (S.sum_len > MAX_SET_BASES) { err = "hx_poa_sequences_mode: set " + std::to_string(i) + " holds " + std::to_string(S.sum_len) + " bases in all, more than the " + std::to_string(MAX_SET_BASES) + " nodes a graph can have"; return -1; }
+        if (S.sum_len > MAX_SET_BASES) { err = who + ": set " + std::to_string(i) + " holds " + std::to_string(S.sum_len) + " bases in all, more than the " + std::to_string(MAX_SET_BASES) + " nodes a graph can have"; return -1; }
         S.cns_off = cns_off[i]; cns_off[i + 1] = cns_off[i] + S.sum_len;   // (a consensus has at most one base per node)
     }
     std::vector<uint8_t> codes(std::max<uint64_t>(1, nb));
@@ -363,8 +551,8 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
     std::vector<uint64_t> vest(ns);
     std::vector<uint32_t> todo;
     for (uint32_t i = 0; i < ns; i++) { vest[i] = std::min<uint64_t>(sets[i].sum_len, sets[i].lmax + sets[i].sum_len / 8 + 64); if (sets[i].sum_len) todo.push_back(i); }
-    auto need = [&](uint32_t i) { const MSet& S = sets[i]; return carve_pools(nullptr, S.sum_len, S.nseq, S.lmax, nullptr, nullptr, nullptr) + al256((vest[i] + 1) * (uint64_t)(S.lmax + 1) * 4); };
-    auto inst_of = [&](uint32_t i) { int k = 0; while ((uint64_t)kInst[k].nt * kInst[k].cpl < (uint64_t)sets[i].lmax + 1) k++; return k; };
+    auto need = [&](uint32_t i) { const MSet& S = sets[i]; return carve_pools(nullptr, S.sum_len, S.nseq, S.lmax, nullptr, nullptr, nullptr) + al256((vest[i] + 1) * (uint64_t)(S.lmax + 1) * cell_bytes); };
+    auto inst_of = [&](uint32_t i) { int k = 0; while ((uint64_t)inst[k].nt * inst[k].cpl < (uint64_t)sets[i].lmax + 1) k++; return k; };
     uint64_t budget;
     {
         size_t fr = 0, tot = 0;
@@ -397,10 +585,10 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
             if (first && a.slot_kb_cap) sb = std::max(pmax, std::min<uint64_t>(sb, (uint64_t)a.slot_kb_cap << 10));   // (test switch: forces the overflow and rerun)
             sb = al256(sb);
             int occ = 0;
-            MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kInst[k].fn, kInst[k].nt, 0));
+            MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, inst[k].fn, inst[k].nt, 0));
             const uint64_t resident = (uint64_t)std::max(1, occ) * (uint64_t)n_cu;
             const uint64_t fit = budget / sb;
-            if (fit == 0) { err = "hx_poa_sequences_mode: set " + std::to_string(big) + " needs " + std::to_string(sb) + " bytes of workspace, more than the budget of " + std::to_string(budget) + " (option poa_workspace_gb)"; return -1; }
+            if (fit == 0) { err = who + ": set " + std::to_string(big) + " needs " + std::to_string(sb) + " bytes of workspace, more than the budget of " + std::to_string(budget) + " (option poa_workspace_gb)"; return -1; }
             slot[k] = sb; nslots[k] = (uint32_t)std::min<uint64_t>({(uint64_t)v.size(), resident, fit});
             base[k] = order.size();
             order.insert(order.end(), v.begin(), v.end());
@@ -410,7 +598,7 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
             MCHK(hipStreamSynchronize(s));
             ws.release();
             const hipError_t e = hipMalloc(&ws.p, total);
-            if (e != hipSuccess) { ws.p = nullptr; err = "hx_poa_sequences_mode: the workspace of " + std::to_string(total) + " bytes could not be allocated: " + hipGetErrorString(e); return -1; }
+            if (e != hipSuccess) { ws.p = nullptr; err = who + ": the workspace of " + std::to_string(total) + " bytes could not be allocated: " + hipGetErrorString(e); return -1; }
             ws.cap = total;
         }
         MCHK(hipMemcpyAsync(d_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, s));
@@ -420,11 +608,11 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
         for (int k = 0; k < N_INST; k++) {
             if (by[k].empty()) continue;
             MArgs q{d_sets.p, d_order.p + base[k], (uint32_t)by[k].size(), d_counter.p + k, d_codes.p, d_soff.p, (uint8_t*)ws.p, slot[k],
-                    a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p};
-            launch(k, nslots[k], q, s);
+                    a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p, a.gap_extend};
+            if (aff) launch_affine(k, nslots[k], q, s); else launch(k, nslots[k], q, s);
             MCHK(hipGetLastError());
             o.launches++;
-            if (a.debug) fprintf(stderr, "[hx] POA modes: %zu sets on %u workgroups of %d lanes x %d columns, slots of %.1f MB\n", by[k].size(), nslots[k], kInst[k].nt, kInst[k].cpl, slot[k] / 1e6);
+            if (a.debug) fprintf(stderr, "[hx] POA modes%s: %zu sets on %u workgroups of %d lanes x %d columns, slots of %.1f MB\n", aff ? " (affine)" : "", by[k].size(), nslots[k], inst[k].nt, inst[k].cpl, slot[k] / 1e6);
         }
         MCHK(hipEventRecord(e1, s));
         MCHK(hipEventSynchronize(e1));
@@ -437,7 +625,7 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
         for (uint32_t i : todo) {
             if (status[i] == MS_OK) continue;
             const bool capped = first && a.slot_kb_cap;   // (a capped slot can be short of even the worst case)
-            if (status[i] != MS_H_OVERFLOW || (vest[i] >= sets[i].sum_len && !capped)) { err = "hx_poa_sequences_mode: set " + std::to_string(i) + " failed on the device (status " + std::to_string((int)status[i]) + ")"; return -1; }
+            if (status[i] != MS_H_OVERFLOW || (vest[i] >= sets[i].sum_len && !capped)) { err = who + ": set " + std::to_string(i) + " failed on the device (status " + std::to_string((int)status[i]) + ")"; return -1; }
             vest[i] = std::min<uint64_t>(sets[i].sum_len, std::max<uint64_t>(2 * vest[i], 2 * (uint64_t)vseen[i] + 64));
             next.push_back(i);
             o.retried++;

@@ -67,6 +67,10 @@ class PoaModeParams(C.Structure):
     _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap", C.c_int32), ("type", C.c_int32)]
 
 
+class PoaAffineParams(C.Structure):
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("type", C.c_int32)]
+
+
 class Backend(C.Structure):
     _fields_ = [("ctx", C.c_void_p)] + [(k, C.c_void_p) for k in
                                         ("chain_reads", "edge_support", "edge_coords", "poa_batch", "free_chain",

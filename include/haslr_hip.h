@@ -58,7 +58,8 @@ void hx_ctx_destroy(hx_ctx*);
  *                    poa_own_bucket_first, poa_resident_first, poa_far_shift) and test switches that force rare paths (poa_poll_limit, poa_max_indeg, poa_node_est_pct,
  *                    poa_far_rows, poa_ring_zero, poa_slots, poa_slots_pct, poa_batches, poa_force_cm, coords_lds_supp), and two of the
  *                    general POA path (hx_poa_sequences_mode): poa_general (1: HX_POA_NW runs the general path too) and poa_modes_slot_kb (cap of
- *                    its first round of workspace slots, forcing the rerun of sets in larger ones).
+ *                    its first round of workspace slots, forcing the rerun of sets in larger ones), and poa_affine (1: hx_poa_sequences_affine
+ *                    with gap_extend == gap_open runs the affine kernel instead of the linear paths).
  *                    Results never depend on any of them. */
 int hx_set_option(hx_ctx*, const char* name, const char* value);
 int hx_get_option(const hx_ctx*, const char* name, double* value);
@@ -94,6 +95,12 @@ int hx_poa_sequences(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const ui
  *                     sequences of up to 32767 bases, sets of up to 2^21 - 2 bases in all. gap >= 0 or an unknown type: error. An alignment that
  *                     holds no sequence position counts as empty (spoa leaves that case undefined): the sequence becomes a new chain. */
 int hx_poa_sequences_mode(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_mode_params*, hx_cns_out* out);
+/*   hx_poa_sequences_affine  the same with affine gaps (spoa's five-score engine; DESIGN.md "General POA path", "Affine gaps"): a gap of k bases
+ *                     costs gap_open + (k - 1) gap_extend. gap_extend == gap_open is the linear model and goes to hx_poa_sequences_mode (option
+ *                     poa_affine sends it through the affine kernel instead, same results); gap_open < gap_extend runs the affine instances of
+ *                     the general path: a cell holds H and F, sequences of up to 16383 bases. Errors: gap_open >= 0, gap_extend > 0,
+ *                     gap_extend < gap_open (refused, not reinterpreted: what spoa does with such scores cannot be checked here), unknown type. */
+int hx_poa_sequences_affine(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_affine_params*, hx_cns_out* out);
 void hx_free_chain(hx_ctx*, hx_chain_out*);
 void hx_free_edges(hx_ctx*, hx_edges_out*);
 void hx_free_coords(hx_ctx*, hx_coords_out*);

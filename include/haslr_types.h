@@ -137,6 +137,13 @@ typedef struct {
     int32_t type; /* hx_poa_type */
 } hx_poa_mode_params;
 
+/* hx_poa_sequences_affine: the same with affine gaps. A gap of k bases costs gap_open + (k - 1) gap_extend;
+ * gap_open < 0, gap_extend <= 0, gap_open <= gap_extend (gap_extend == gap_open is the linear model). */
+typedef struct {
+    int32_t match, mismatch, gap_open, gap_extend;
+    int32_t type; /* hx_poa_type */
+} hx_poa_affine_params;
+
 #ifdef __cplusplus
 }
 #endif

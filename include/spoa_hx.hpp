@@ -16,7 +16,8 @@
 // the work happens in generate_consensus(): align_sequence_with_graph() returns a token (an Alignment holding one
 // (-1, ticket) pair, not a list of node/position pairs), add_alignment() appends the sequence that goes with a token,
 // generate_consensus() sends the recorded sequences, in order, through hx_poa_sequences_mode (the engine's alignment type and
-// three scores, linear gap, unit weights) and returns what spoa's generate_consensus returns for them.
+// three scores, linear gap, unit weights; an engine made with five scores, gap open below gap extend, goes through
+// hx_poa_sequences_affine) and returns what spoa's generate_consensus returns for them.
 // All three of spoa's alignment types are taken: kNW (global, what the reference uses) runs the tuned global path, kSW (local) and
 // kOV (overlap) the general path of the library (DESIGN.md "General POA path"). What is supported beyond that is the reference's call
 // pattern: weight 1 only, every alignment added to the graph it was computed against, in the order it was computed. spoa 1.1.3 exits on invalid input; this header throws std::runtime_error with the
@@ -26,7 +27,7 @@
 // All of them share one device context here (created on first use, device HASLR_DEVICE or 0), and their generate_consensus() calls are
 // FLAT-COMBINED: a caller queues its sequence set; the first one in becomes the submitter, waits HASLR_SPOA_BATCH_US microseconds (default
 // 200) or until HASLR_SPOA_BATCH sets (default 256) are queued - only while it has company: a lone caller (-t 1) submits at once - and sends
-// everything queued through ONE hx_poa_sequences_mode call per alignment type and score triple; callers that arrive while a call is on the device form the next batch. A set that makes the
+// everything queued through ONE hx_poa_sequences_mode / hx_poa_sequences_affine call per alignment type and set of scores; callers that arrive while a call is on the device form the next batch. A set that makes the
 // shared call fail is isolated (every set of that call again, on its own): only its caller gets the exception. With -t 64 the reference's own thread fan-out therefore puts ~64 edges into
 // every launch instead of one. spoa::hx::consensus_batch() below is the entry to use from new code: all edges in one call (that is what
 // haslr_amd's own pipeline does through hx_poa_batch). spoa::hx::stats() tells how many device calls served how many sets.
@@ -60,7 +61,7 @@ struct Device {
     hx_ctx* ctx = nullptr;
     std::mutex mu;                    // guards ctx and every call into it
     // flat combining of concurrent generate_consensus() calls
-    struct Request { const std::vector<std::string>* seqs; AlignmentType type; std::int8_t m, n, g; std::string result, error; bool done, answered; };   // answered: result or error is final (an empty consensus is a result)
+    struct Request { const std::vector<std::string>* seqs; AlignmentType type; std::int8_t m, n, g, e; std::string result, error; bool done, answered; };   // answered: result or error is final (an empty consensus is a result)
     std::mutex qmu;
     std::condition_variable qcv;
     std::vector<Request*> queue;
@@ -148,12 +149,39 @@ inline std::vector<std::string> consensus_batch(const std::vector<std::vector<st
     return consensus_batch(p, type, m, n, g);
 }
 
+// ... with affine gaps: gap open g, gap extend e (g <= e <= 0; e == g is the linear model and takes the overloads above)
+inline std::vector<std::string> consensus_batch(const std::vector<const std::vector<std::string>*>& sets, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) {
+    if (e == g) return consensus_batch(sets, type, m, n, g);
+    std::vector<std::uint64_t> set_off{0}, seq_off{0};
+    std::string bases;
+    for (const auto* st : sets) {
+        for (const auto& s : *st) { bases += s; seq_off.push_back(bases.size()); }
+        set_off.push_back(seq_off.size() - 1);
+    }
+    const hx_poa_affine_params ap{m, n, g, e, static_cast<std::int32_t>(type)};
+    hx_cns_out out;
+    Device& d = device();
+    std::lock_guard<std::mutex> lock(d.mu);
+    hx_ctx* ctx = context_locked(d);
+    if (hx_poa_sequences_affine(ctx, (std::uint32_t)sets.size(), set_off.data(), seq_off.data(), bases.c_str(), &ap, &out) != 0)
+        throw std::runtime_error(std::string("spoa_hx: ") + hx_last_error());
+    std::vector<std::string> res(sets.size());
+    for (std::size_t i = 0; i < sets.size(); i++) res[i].assign(out.cns + out.cns_off[i], out.cns + out.cns_off[i + 1]);
+    hx_free_cns(ctx, &out);
+    return res;
+}
+inline std::vector<std::string> consensus_batch(const std::vector<std::vector<std::string>>& sets, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) {
+    std::vector<const std::vector<std::string>*> p;
+    for (const auto& st : sets) p.push_back(&st);
+    return consensus_batch(p, type, m, n, g, e);
+}
+
 // one set on behalf of one caller thread, combined with whatever other threads have queued (see "Threads" above)
-inline std::string consensus_combined(const std::vector<std::string>& seqs, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g) {
+inline std::string consensus_combined(const std::vector<std::string>& seqs, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) {
     Device& d = device();
     static const long window_us = std::getenv("HASLR_SPOA_BATCH_US") ? std::atol(std::getenv("HASLR_SPOA_BATCH_US")) : 200;
     static const std::size_t batch_max = std::getenv("HASLR_SPOA_BATCH") ? (std::size_t)std::max(1L, std::atol(std::getenv("HASLR_SPOA_BATCH"))) : 256;
-    Device::Request me{&seqs, type, m, n, g, std::string(), std::string(), false, false};
+    Device::Request me{&seqs, type, m, n, g, e, std::string(), std::string(), false, false};
     std::unique_lock<std::mutex> lk(d.qmu);
     d.queue.push_back(&me);
     d.arrivals++;
@@ -176,7 +204,7 @@ inline std::string consensus_combined(const std::vector<std::string>& seqs, Alig
             if (batch.size() > batch_max) { d.queue.assign(batch.begin() + (std::ptrdiff_t)batch_max, batch.end()); batch.resize(batch_max); }
             d.arrivals = d.queue.size();                           // arrivals from here on = company for the next submitter
             lk.unlock();
-            // one device call per (alignment type, score triple) in the batch (the reference uses one of each)
+            // one device call per (alignment type, four scores) in the batch (the reference uses one of each)
             std::vector<char> served(batch.size(), 0);
             std::uint64_t calls = 0;
             for (std::size_t i = 0; i < batch.size(); i++) {
@@ -184,9 +212,9 @@ inline std::string consensus_combined(const std::vector<std::string>& seqs, Alig
                 std::vector<std::size_t> idx;
                 std::vector<const std::vector<std::string>*> sets;
                 for (std::size_t j = i; j < batch.size(); j++)
-                    if (!served[j] && batch[j]->type == batch[i]->type && batch[j]->m == batch[i]->m && batch[j]->n == batch[i]->n && batch[j]->g == batch[i]->g) { idx.push_back(j); sets.push_back(batch[j]->seqs); served[j] = 1; }
+                    if (!served[j] && batch[j]->type == batch[i]->type && batch[j]->m == batch[i]->m && batch[j]->n == batch[i]->n && batch[j]->g == batch[i]->g && batch[j]->e == batch[i]->e) { idx.push_back(j); sets.push_back(batch[j]->seqs); served[j] = 1; }
                 try {
-                    std::vector<std::string> res = consensus_batch(sets, batch[i]->type, batch[i]->m, batch[i]->n, batch[i]->g);
+                    std::vector<std::string> res = consensus_batch(sets, batch[i]->type, batch[i]->m, batch[i]->n, batch[i]->g, batch[i]->e);
                     for (std::size_t q = 0; q < idx.size(); q++) { batch[idx[q]]->result.swap(res[q]); batch[idx[q]]->answered = true; }
                     calls++;
                 } catch (const std::exception& e) {
@@ -199,7 +227,7 @@ inline std::string consensus_combined(const std::vector<std::string>& seqs, Alig
                         for (std::size_t q = 0; q < idx.size(); q++) {
                             Device::Request* r = batch[idx[q]];
                             if (same >= 2) { r->error = group_error; r->answered = true; continue; }
-                            try { r->result = consensus_batch(std::vector<const std::vector<std::string>*>{sets[q]}, batch[i]->type, batch[i]->m, batch[i]->n, batch[i]->g)[0]; same = 0; }
+                            try { r->result = consensus_batch(std::vector<const std::vector<std::string>*>{sets[q]}, batch[i]->type, batch[i]->m, batch[i]->n, batch[i]->g, batch[i]->e)[0]; same = 0; }
                             catch (const std::exception& e1) { r->error = e1.what(); same = r->error == group_error ? same + 1 : 0; }
                             r->answered = true;
                             calls++;
@@ -231,6 +259,10 @@ inline std::string consensus_combined(const std::vector<std::string>& seqs, Alig
     return me.result;
 }
 
+inline std::string consensus_combined(const std::vector<std::string>& seqs, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g) {
+    return consensus_combined(seqs, type, m, n, g, g);   // linear gap
+}
+
 }  // namespace hx
 
 class Graph {
@@ -246,7 +278,7 @@ public:
     // spoa::Graph::generate_consensus()
     std::string generate_consensus() {
         if (sequences_.empty()) return std::string();
-        return hx::consensus_combined(sequences_, type_, m_, n_, g_);
+        return hx::consensus_combined(sequences_, type_, m_, n_, g_, e_);
     }
 
 private:
@@ -254,29 +286,39 @@ private:
     std::vector<std::string> sequences_;
     std::uint32_t ticket_ = 0;
     AlignmentType type_ = AlignmentType::kNW;
-    std::int8_t m_ = 5, n_ = -4, g_ = -8;
+    std::int8_t m_ = 5, n_ = -4, g_ = -8, e_ = -8;
 };
 
 class AlignmentEngine {
 public:
     // spoa::AlignmentEngine::align_sequence_with_graph(sequence, graph): a token for add_alignment (see the header comment)
     Alignment align_sequence_with_graph(const std::string& /*sequence*/, const std::unique_ptr<Graph>& graph) {
-        graph->type_ = type_; graph->m_ = m_; graph->n_ = n_; graph->g_ = g_;
+        graph->type_ = type_; graph->m_ = m_; graph->n_ = n_; graph->g_ = g_; graph->e_ = e_;
         return Alignment{{-1, (std::int32_t)graph->ticket_}};
     }
 
 private:
     friend std::unique_ptr<AlignmentEngine> createAlignmentEngine(AlignmentType, std::int8_t, std::int8_t, std::int8_t);
-    AlignmentEngine(AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g) : type_(type), m_(m), n_(n), g_(g) {}
+    friend std::unique_ptr<AlignmentEngine> createAlignmentEngine(AlignmentType, std::int8_t, std::int8_t, std::int8_t, std::int8_t);
+    AlignmentEngine(AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) : type_(type), m_(m), n_(n), g_(g), e_(e) {}
     AlignmentType type_;
-    std::int8_t m_, n_, g_;
+    std::int8_t m_, n_, g_, e_;
 };
 
 // spoa::createAlignmentEngine(type, match, mismatch, gap) — linear gap penalties, as spoa 1.1.3 has them
 inline std::unique_ptr<AlignmentEngine> createAlignmentEngine(AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g) {
     if (type != AlignmentType::kSW && type != AlignmentType::kNW && type != AlignmentType::kOV) throw std::invalid_argument("spoa_hx: unknown AlignmentType");
     if (g >= 0) throw std::invalid_argument("spoa_hx: the gap penalty must be negative");
-    return std::unique_ptr<AlignmentEngine>(new AlignmentEngine(type, m, n, g));
+    return std::unique_ptr<AlignmentEngine>(new AlignmentEngine(type, m, n, g, g));
+}
+// spoa::createAlignmentEngine(type, match, mismatch, gap_open, gap_extend) — affine gap penalties: a gap of k bases costs g + (k - 1) e.
+// e == g is the linear engine above. e < g is refused: what spoa does with such scores cannot be checked here, so nothing is guessed.
+inline std::unique_ptr<AlignmentEngine> createAlignmentEngine(AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) {
+    if (type != AlignmentType::kSW && type != AlignmentType::kNW && type != AlignmentType::kOV) throw std::invalid_argument("spoa_hx: unknown AlignmentType");
+    if (g >= 0) throw std::invalid_argument("spoa_hx: the gap open penalty must be negative");
+    if (e > 0) throw std::invalid_argument("spoa_hx: the gap extend penalty must not be positive");
+    if (e < g) throw std::invalid_argument("spoa_hx: the gap extend penalty must not be below the gap open penalty");
+    return std::unique_ptr<AlignmentEngine>(new AlignmentEngine(type, m, n, g, e));
 }
 inline std::unique_ptr<Graph> createGraph() { return std::unique_ptr<Graph>(new Graph()); }
 

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""Throughput of the general POA path (hx_poa_sequences_mode, kernels/poa_modes.hip) on two seeded workloads, in one process:
+"""Throughput of the general POA path (hx_poa_sequences_mode and hx_poa_sequences_affine, kernels/poa_modes.hip) on two seeded workloads,
+in one process:
   (a) noisy copies: 8-40 copies of 200-4 000-base templates (8 % insertions, 3 % deletions, 2 % substitutions), run as kSW with random
       0-300-base flanks on both sides of every copy, and as kNW / kOV without them
   (b) tiled fragments: 20 fragments of 1-3 kb drawn at random from 5 kb templates (same error model), kOV
 For every mode: sets, cells (sum of V x L, the full matrices spoa computes), kernel time (hipEvents; warmed up, median and spread of
 --repeats runs), GCUPS; for context the tuned kNW path on the same sets, and the CPU restatement (tests/poa_modes_ref.cpp) on 16 threads over
-a sample of the sets (GCUPS of the sample). Prints one JSON line."""
+a sample of the sets (GCUPS of the sample). Every row also runs the affine kernel on the same sets (hx_poa_sequences_affine with
+--affine-scores, default 5 -4 -8 -6): same figures, the affine / linear ratio of the median kernel times, and the sample compared with the
+affine restatement (tests/poa_affine_ref.cpp). Prints one JSON line."""
 import argparse
 import json
 import os
@@ -83,17 +86,20 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--cpu-sample", type=int, default=32, help="sets of each workload the CPU restatement runs (16 threads)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--affine-scores", type=int, nargs=4, default=[5, -4, -8, -6], metavar=("M", "N", "G", "E"), help="match, mismatch, gap open, gap extend of the affine rows")
     a = ap.parse_args()
     from haslr_amd import hip
+    import parlib
     import pmrlib
     rng = np.random.default_rng(a.seed)
     loads = {"a_sw": ("sw", workload_a(rng, a.sets_a, True)), "a_nw": ("nw", workload_a(rng, a.sets_a, False))}
     loads["a_ov"] = ("ov", loads["a_nw"][1])
     loads["b_ov"] = ("ov", workload_b(rng, a.sets_b))
     ctx = hip.HipContext(0)
-    res = {"tool": "poa_modes_bench", "seed": a.seed, "repeats": a.repeats}
+    res = {"tool": "poa_modes_bench", "seed": a.seed, "repeats": a.repeats, "affine_scores": list(a.affine_scores)}
     with tempfile.TemporaryDirectory() as d:
         ref = pmrlib.ModesRef(d)
+        aref = parlib.AffineRef(d)
         for name, (mode, sets) in loads.items():
             r = {"mode": mode, "sets": len(sets)}
             for path, opts in (("general", {"poa_general": 1}), ("tuned_nw", {})):
@@ -114,6 +120,14 @@ def main():
             r["cpu_restatement_16t"] = {"sets": len(sample), "cells": int(sc), "s": round(dt, 2), "gcups": round(sc / dt / 1e9, 3)}
             got = ctx.poa_sequences_mode(sample, mode)
             r["sample_equal"] = got == [c for c, _ in out]
+            cells = ctx.poa_sequences_affine(sets, mode, *a.affine_scores, stats=True)[1]["dp_cells"]
+            ms = gpu_time(ctx, lambda: ctx.poa_sequences_affine(sets, mode, *a.affine_scores), a.repeats)
+            med = float(np.median(ms))
+            r["affine"] = {"cells": int(cells), "kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
+                           "gcups": round(cells / med / 1e6, 2), "over_linear": round(med / r["general"]["kernel_ms_median"], 3)}
+            with ThreadPoolExecutor(16) as ex:
+                out = list(ex.map(lambda st: aref.consensus(st, mode, *a.affine_scores), sample))
+            r["affine_sample_equal"] = ctx.poa_sequences_affine(sample, mode, *a.affine_scores) == out
             res[name] = r
     ctx.close()
     print(json.dumps(res))
