@@ -457,15 +457,21 @@ extern "C" int hx_poa_sequences_mode(hx_ctx* c, uint32_t n_sets, const uint64_t*
     return poa_general_call(c, n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap, mp->gap, 0, mp->type, out);
 }
 
+// what hx_poa_sequences_affine and hx_poa_msa ask of their scores, type and sequence count (0 = fine)
+static int check_affine_call(const std::string& who, int32_t gap_open, int32_t gap_extend, int32_t type, uint64_t n_seq) {
+    if (gap_open >= 0) return fail(who + ": the gap open score must be negative, not " + std::to_string(gap_open));
+    if (gap_extend > 0) return fail(who + ": the gap extend score must not be positive, not " + std::to_string(gap_extend));
+    // (spoa is said to fall back to its linear engine here, silently; that cannot be checked without the library, so the call is refused)
+    if (gap_extend < gap_open) return fail(who + ": the gap extend score " + std::to_string(gap_extend) + " is below the gap open score " + std::to_string(gap_open) + " (extending a gap must not cost more than opening one)");
+    if (type != HX_POA_SW && type != HX_POA_NW && type != HX_POA_OV) return fail(who + ": unknown alignment type " + std::to_string(type) + " (HX_POA_SW 0, HX_POA_NW 1, HX_POA_OV 2)");
+    if (n_seq >= 0x7fffffffULL) return fail(who + ": too many sequences");
+    return 0;
+}
+
 extern "C" int hx_poa_sequences_affine(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_affine_params* ap, hx_cns_out* out) {
     memset(out, 0, sizeof(*out));
     if (!ap) return fail("hx_poa_sequences_affine: no parameters");
-    if (ap->gap_open >= 0) return fail("hx_poa_sequences_affine: the gap open score must be negative, not " + std::to_string(ap->gap_open));
-    if (ap->gap_extend > 0) return fail("hx_poa_sequences_affine: the gap extend score must not be positive, not " + std::to_string(ap->gap_extend));
-    // (spoa is said to fall back to its linear engine here, silently; that cannot be checked without the library, so the call is refused)
-    if (ap->gap_extend < ap->gap_open) return fail("hx_poa_sequences_affine: the gap extend score " + std::to_string(ap->gap_extend) + " is below the gap open score " + std::to_string(ap->gap_open) + " (extending a gap must not cost more than opening one)");
-    if (ap->type != HX_POA_SW && ap->type != HX_POA_NW && ap->type != HX_POA_OV) return fail("hx_poa_sequences_affine: unknown alignment type " + std::to_string(ap->type) + " (HX_POA_SW 0, HX_POA_NW 1, HX_POA_OV 2)");
-    if (set_off[n_sets] >= 0x7fffffffULL) return fail("hx_poa_sequences_affine: too many sequences");
+    if (check_affine_call("hx_poa_sequences_affine", ap->gap_open, ap->gap_extend, ap->type, set_off[n_sets])) return -1;
     if (ap->gap_extend == ap->gap_open && !c->opt.poa_affine) {   // the linear model: the linear paths (kNW keeps the tuned one)
         const hx_poa_mode_params mp{ap->match, ap->mismatch, ap->gap_open, ap->type};
         return hx_poa_sequences_mode(c, n_sets, set_off, seq_off, bases, &mp, out);
@@ -473,7 +479,36 @@ extern "C" int hx_poa_sequences_affine(hx_ctx* c, uint32_t n_sets, const uint64_
     return poa_general_call(c, n_sets, set_off, seq_off, bases, ap->match, ap->mismatch, ap->gap_open, ap->gap_extend, 1, ap->type, out);
 }
 
+// the multiple sequence alignment of every set: the general path's MSA instances (all three types: the tuned kNW path keeps no node per
+// base), linear ones when the two gap scores are equal
+extern "C" int hx_poa_msa(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_msa_params* mp, hx_msa_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!mp) return fail("hx_poa_msa: no parameters");
+    if (check_affine_call("hx_poa_msa", mp->gap_open, mp->gap_extend, mp->type, set_off[n_sets])) return -1;
+    HIPCHK(hipSetDevice(c->device));
+    hxk::PoaModesArgs a{n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap_open, mp->type, (uint32_t)std::max(0, c->opt.poa_modes_slot_kb), c->opt.poa_workspace_gb, c->opt.debug};
+    a.gap_extend = mp->gap_extend; a.affine = mp->gap_extend != mp->gap_open || c->opt.poa_affine;
+    a.msa = 1; a.include_consensus = mp->include_consensus != 0;
+    hxk::PoaModesOut o;
+    std::string err;
+    if (hxk::poa_modes_run(c->stream, c->poa_modes_ws, a, o, err)) return fail(err);
+    c->tm.ms[3] += o.kernel_ms; c->tm.launches[3] += o.launches;
+    auto dup = [](const void* p, size_t bytes) { void* q = malloc(std::max<size_t>(1, bytes)); memcpy(q, p, bytes); return q; };
+    out->n_set = n_sets;
+    out->n_rows = (uint32_t*)dup(o.msa_rows.data(), (size_t)n_sets * 4);
+    out->n_cols = (uint32_t*)dup(o.msa_cols.data(), (size_t)n_sets * 4);
+    out->msa_off = (uint64_t*)dup(o.msa_off.data(), ((size_t)n_sets + 1) * 8);
+    out->msa = (char*)dup(o.msa.data(), o.msa.size());
+    out->cns_off = (uint64_t*)dup(o.cns_off.data(), ((size_t)n_sets + 1) * 8);
+    out->cns = (char*)dup(o.cns.data(), o.cns.size());
+    out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
+    out->rows_kernel_ms = o.msa_rows_ms; out->rows_kernel_bytes = o.msa_moved_bytes;
+    if (c->opt.debug) fprintf(stderr, "[hx] POA MSA call%s: %u sets, %.3g cells, %zu bytes of rows, kernels %.2f ms (rows %.3f ms), %u sets rerun in a larger slot\n", a.affine ? " (affine)" : "", n_sets, (double)o.cells, o.msa.size(), o.kernel_ms, o.msa_rows_ms, o.retried);
+    return 0;
+}
+
 extern "C" void hx_free_cns(hx_ctx*, hx_cns_out* o) { free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }
+extern "C" void hx_free_msa(hx_ctx*, hx_msa_out* o) { free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa); free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }
 
 extern "C" uint32_t hx_poa_phase_cycles(hx_ctx* c, uint64_t* sum6, uint64_t* max6) {
     // lane-0 cycle counters of the last hx_poa_batch: [decode, dp, traceback, graph update+consensus, toposort, csr];

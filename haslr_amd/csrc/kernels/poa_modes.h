@@ -27,6 +27,8 @@ struct PoaModesArgs {
     int debug;
     int32_t gap_extend = 0;              // affine calls: gap is the gap open score, this the gap extend score (gap <= gap_extend <= 0)
     int affine = 0;                      // 1: the affine instances (a cell is an (H, F) pair, sequences of up to 16383 bases)
+    int msa = 0;                         // 1: the MSA instances, and the alignment text in PoaModesOut (hx_poa_msa)
+    int include_consensus = 0;           // MSA calls: the consensus is the last row of every set
 };
 
 struct PoaModesOut {
@@ -35,6 +37,13 @@ struct PoaModesOut {
     uint64_t cells = 0, seq_bases = 0, n_aligned = 0;
     double kernel_ms = 0;                // hipEvents around the launches
     uint32_t launches = 0, retried = 0;  // kernel launches, sets rerun in a larger slot
+    // MSA calls: per set its rows (one per given sequence, + 1 with the consensus row) and columns; set i is the rows x columns
+    // characters at msa_off[i], row-major, no terminators
+    std::vector<uint32_t> msa_rows, msa_cols;
+    std::vector<uint64_t> msa_off;       // n_sets + 1
+    std::string msa;
+    double msa_rows_ms = 0;              // the row-writing kernel alone (it is part of kernel_ms)
+    uint64_t msa_moved_bytes = 0;        // what it has to move: the text + 4 bytes per base read
 };
 
 // 0 = ok, else -1 with the reason in err

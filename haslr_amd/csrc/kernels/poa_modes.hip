@@ -16,6 +16,10 @@
 //   * graph update (add_alignment), spoa's topological sort (thread 0), rank-ordered predecessor rows (all lanes)
 // and at the end the heaviest bundle with branch completion by the first wavefront. A set whose next alignment needs more of H than its slot
 // holds stops with a status; the host reruns it in a larger slot.
+//
+// The multiple sequence alignment of a set (hx_poa_msa; DESIGN.md "MSA output") comes from the same workgroup under a template flag: it keeps
+// the node of every base that add_alignment reports, turns nodes into columns after the last sort, and a second, grid-wide kernel
+// (k_msa_rows) writes the row text once the host knows the sizes.
 #include <algorithm>
 #include <chrono>
 #include <numeric>
@@ -46,7 +50,13 @@ struct MArgs {
     int32_t m, n, g, type;
     char* cns; uint32_t *cns_len, *status, *vseen; unsigned long long* cells;
     int32_t e;   // affine instances only: gap extend (g is gap open)
+    // MSA instances only: per base of the call (global offset) its node, rewritten to its column when the set is done; columns per set;
+    // column of every consensus base beside cns (null: not asked for)
+    uint32_t *base_col, *n_cols, *cns_col;
 };
+
+// one row of the MSA text: its columns (rising) start at cols[src], its letters at codes[src] (a sequence) or cns[src] (the consensus row)
+struct MRow { uint64_t src, dst; uint32_t len, ncols, is_cns, pad; };
 
 __host__ __device__ inline uint64_t al256(uint64_t x) { return (x + 255) & ~255ull; }
 
@@ -383,7 +393,109 @@ __device__ uint32_t traceback_affine(G& g, const int2* HF, const uint8_t* s, con
     return anypos ? na : 0u;
 }
 
-template <int NT, int CPL, bool AFF = false>
+// ---- MSA output (DESIGN.md "General POA path", "MSA output") ----
+// The columns of spoa's generate_multiple_sequence_alignment on the final rank order (order_rows leaves aligned nodes contiguous): rank r
+// opens a column iff none of its node's aligned nodes has a smaller rank, and the column of a rank is the number of openers up to it, less
+// one. colr (by rank) receives them; returns the number of columns. All lanes.
+template <int NT>
+__device__ uint32_t msa_columns(const G& g, const uint32_t V, uint32_t* colr, uint32_t* s_scan) {
+    const uint32_t t = threadIdx.x;
+    uint32_t carry = 0;
+    for (uint32_t b = 0; b < V; b += NT) {
+        const uint32_t r = b + t;
+        uint32_t opens = 0;
+        if (r < V) {
+            const uint32_t n = g.rank2node[r], na = g.n_aligned[n];
+            opens = 1;
+            for (uint32_t k = 0; k < na; k++) if (g.node2rank[g.aligned[3 * n + k]] < r) opens = 0;
+        }
+        uint32_t tot;
+        const uint32_t pre = block_excl_sum<NT>(opens, s_scan, &tot);
+        if (r < V) colr[r] = carry + pre + opens - 1u;   // (rank 0 always opens: never below 0)
+        carry += tot;
+    }
+    __syncthreads();
+    return carry;
+}
+
+// consensus_wave of poa_graph.inl (k_poa uses that one, so it stays as it is) that also hands back the rank the walk back starts from:
+// the ranks of the consensus nodes are that rank and its chain of g.pred
+__device__ uint32_t consensus_wave_end(G& g, const uint32_t V, char* out, uint32_t* end_rank) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t best, nbest;
+    bundle_pass(g, V, 0, false, -1, best, nbest);
+    if (best == NONE) best = g.node2rank[0];
+    for (uint32_t round = 0; !(g.row_meta[best] & 4u) && round <= V; round++) {
+        const uint32_t n0 = g.rank2node[best];
+        if (lane == 0)
+            for (uint32_t e = g.out_head[n0]; e != NONE; e = g.e_next_out[e])
+                for (uint32_t oe = g.in_head[g.e_to[e]]; oe != NONE; oe = g.e_next_in[oe])
+                    if (g.e_from[oe] != n0) g.score[g.node2rank[g.e_from[oe]]] = -1;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        uint32_t nb;
+        bundle_pass(g, V, best + 1, true, 0, nb, nbest);
+        best = nb == NONE ? g.node2rank[0] : nb;
+    }
+    *end_rank = best;
+    return bundle_backtrack(g, best, out);
+}
+
+// the columns of the len consensus bases, by the first wavefront: bundle_backtrack's walk (64 ranks around the walk fetched at once, the
+// walk inside them on v_readlane) with the rank's column in place of its base; back to front in rev, then turned round by all lanes
+__device__ void consensus_columns(const G& g, const uint32_t end_rank, const uint32_t len, const uint32_t* colr, uint32_t* rev, uint32_t* out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int32_t* pr_r = g.pred;
+    int32_t r = __builtin_amdgcn_readfirstlane((int)end_rank);
+    uint32_t k = 0;
+    int acc = 0;
+    while (r != -1 && k < len) {
+        const uint32_t cb = (uint32_t)r & ~63u, idx = min(cb + lane, (uint32_t)r);
+        const int p = pr_r[idx], c = (int)colr[idx];
+        while (r >= (int32_t)cb && k < len) {
+            const int l = r - (int32_t)cb;
+            const int cl = __builtin_amdgcn_readlane(c, l);
+            acc = lane == (k & 63u) ? cl : acc;
+            k++;
+            if ((k & 63u) == 0) rev[k - 64 + lane] = (uint32_t)acc;
+            r = __builtin_amdgcn_readlane(p, l);
+        }
+    }
+    if (lane < (k & 63u)) rev[(k & ~63u) + lane] = (uint32_t)acc;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    for (uint32_t q = lane; q < k; q += 64) out[q] = rev[k - 1 - q];
+}
+
+// The row text of one call, grid-wide: a wavefront takes 64 consecutive bases of one row. Columns rise strictly along a row, so lane i
+// writes the gaps between the previous base's column and its own, then its base: one nearly contiguous span per wavefront, every byte of
+// the output written exactly once (no fill pass). The gaps before a row's first base and after its last one can be long: the whole
+// wavefront writes those. A row without bases (an empty sequence) is one chunk that writes ncols gaps.
+__global__ __launch_bounds__(256) void k_msa_rows(const MRow* rows, const uint2* chunks, const uint32_t n_chunks, const uint32_t* base_col, const uint8_t* codes,
+                                                  const uint32_t* cns_col, const char* cns, char* out) {
+    const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (w >= n_chunks) return;
+    const uint2 ch = chunks[w];
+    const MRow R = rows[ch.x];
+    const uint32_t* col = (R.is_cns ? cns_col : base_col) + R.src;
+    char* row = out + R.dst;
+    const uint32_t i = ch.y + lane;
+    if (i < R.len) {
+        const uint32_t c = col[i];
+        const uint32_t from = i ? col[i - 1] + 1u : c;   // (the gaps before the first base: below, by all lanes)
+        if (c < R.ncols && from <= c) {                   // (always true for the columns run_set leaves: the guard keeps a store inside the row)
+            for (uint32_t q = from; q < c; q++) row[q] = '-';
+            row[c] = R.is_cns ? cns[R.src + i] : "ACGT"[codes[R.src + i] & 3];
+        }
+    }
+    if (ch.y == 0 && R.len) { const uint32_t c0 = min(col[0], R.ncols); for (uint32_t q = lane; q < c0; q += 64) row[q] = '-'; }
+    if (ch.y + 64 >= R.len) {
+        const uint32_t after = R.len ? col[R.len - 1] + 1u : 0u;
+        for (uint32_t q = after + lane; q < R.ncols; q += 64) row[q] = '-';
+    }
+}
+
+template <int NT, int CPL, bool AFF = false, bool MSA = false>
 __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Shared& sh, int* s_wtot, uint32_t* s_scan) {
     const uint32_t t = threadIdx.x;
     const MSet S = a.sets[set];
@@ -421,16 +533,31 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
         __syncthreads();
         V = sh.V; E = sh.E;
         if (sh.fail) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
+        if (MSA) for (uint32_t i = t; i < L; i += NT) a.base_col[b + i] = path[i];   // (node ids never change: a rerun set rewrites its part)
         order_rows<NT>(g, V, s_scan);
     }
-    if (t < 64) {
+    if (MSA) {
+        // columns by rank into the DFS stack's pool (free after the last sort), then every base of the set from its node to its column
+        uint32_t* colr = g.stack;
+        const uint32_t ncols = msa_columns<NT>(g, V, colr, s_scan);
+        const uint64_t b0 = a.soff[S.seq_begin];
+        for (uint64_t i = t; i < S.sum_len; i += NT) a.base_col[b0 + i] = colr[g.node2rank[a.base_col[b0 + i]]];
+        if (t < 64) {
+            uint32_t len = 0, end_rank = 0;
+            if (non_empty) {
+                len = consensus_wave_end(g, V, a.cns + S.cns_off, &end_rank);
+                if (a.cns_col) consensus_columns(g, end_rank, len, colr, (uint32_t*)g.aln_pos, a.cns_col + S.cns_off);
+            }
+            if (t == 0) { a.cns_len[set] = len; a.n_cols[set] = ncols; a.cells[set] = cells; a.status[set] = MS_OK; }
+        }
+    } else if (t < 64) {
         const uint32_t len = non_empty ? consensus_wave(g, V, a.cns + S.cns_off) : 0u;
         if (t == 0) { a.cns_len[set] = len; a.cells[set] = cells; a.status[set] = MS_OK; }
     }
     __syncthreads();   // the slot is free for the next set
 }
 
-template <int NT, int CPL>
+template <int NT, int CPL, bool MSA = false>
 __global__ __launch_bounds__(NT) void k_poa_modes(MArgs a) {
     __shared__ Shared sh;
     __shared__ int s_wtot[NT / 64];
@@ -442,11 +569,11 @@ __global__ __launch_bounds__(NT) void k_poa_modes(MArgs a) {
         const uint32_t q = sh.item;
         __syncthreads();
         if (q >= a.n_items) return;
-        run_set<NT, CPL>(a, a.order[q], slot, sh, s_wtot, s_scan);
+        run_set<NT, CPL, false, MSA>(a, a.order[q], slot, sh, s_wtot, s_scan);
     }
 }
 
-template <int NT, int CPL>
+template <int NT, int CPL, bool MSA = false>
 __global__ __launch_bounds__(NT) void k_poa_affine(MArgs a) {
     __shared__ Shared sh;
     __shared__ int s_wtot[NT / 64];
@@ -458,46 +585,29 @@ __global__ __launch_bounds__(NT) void k_poa_affine(MArgs a) {
         const uint32_t q = sh.item;
         __syncthreads();
         if (q >= a.n_items) return;
-        run_set<NT, CPL, true>(a, a.order[q], slot, sh, s_wtot, s_scan);
+        run_set<NT, CPL, true, MSA>(a, a.order[q], slot, sh, s_wtot, s_scan);
     }
 }
 
-// the instances: workgroup lanes x columns per lane; a set goes to the first whose NT x CPL columns hold its longest sequence + 1
-struct Inst { int nt, cpl; const void* fn; };
+// the instances: workgroup lanes x columns per lane; a set goes to the first whose NT x CPL columns hold its longest sequence + 1.
+// Each has a twin that also records the MSA (a template flag: a consensus-only call runs the code it ran before the MSA existed).
+struct Inst { int nt, cpl; const void* fn; const void* fn_msa; };
 const Inst kInst[] = {
-    {64, 16, (const void*)k_poa_modes<64, 16>},
-    {256, 16, (const void*)k_poa_modes<256, 16>},
-    {256, 32, (const void*)k_poa_modes<256, 32>},
-    {1024, 32, (const void*)k_poa_modes<1024, 32>},
+    {64, 16, (const void*)k_poa_modes<64, 16>, (const void*)k_poa_modes<64, 16, true>},
+    {256, 16, (const void*)k_poa_modes<256, 16>, (const void*)k_poa_modes<256, 16, true>},
+    {256, 32, (const void*)k_poa_modes<256, 32>, (const void*)k_poa_modes<256, 32, true>},
+    {1024, 32, (const void*)k_poa_modes<1024, 32>, (const void*)k_poa_modes<1024, 32, true>},
 };
 constexpr int N_INST = sizeof(kInst) / sizeof(kInst[0]);
 constexpr uint32_t MAX_LEN = 1024 * 32 - 1;
 // the affine instances keep two accumulators per column (diagonal and F): 16 columns per lane throughout, more lanes instead
 const Inst kInstAffine[N_INST] = {
-    {64, 16, (const void*)k_poa_affine<64, 16>},
-    {256, 16, (const void*)k_poa_affine<256, 16>},
-    {512, 16, (const void*)k_poa_affine<512, 16>},
-    {1024, 16, (const void*)k_poa_affine<1024, 16>},
+    {64, 16, (const void*)k_poa_affine<64, 16>, (const void*)k_poa_affine<64, 16, true>},
+    {256, 16, (const void*)k_poa_affine<256, 16>, (const void*)k_poa_affine<256, 16, true>},
+    {512, 16, (const void*)k_poa_affine<512, 16>, (const void*)k_poa_affine<512, 16, true>},
+    {1024, 16, (const void*)k_poa_affine<1024, 16>, (const void*)k_poa_affine<1024, 16, true>},
 };
 constexpr uint32_t MAX_LEN_AFFINE = 1024 * 16 - 1;
-
-void launch(int inst, uint32_t blocks, const MArgs& a, hipStream_t s) {
-    switch (inst) {
-        case 0: k_poa_modes<64, 16><<<blocks, 64, 0, s>>>(a); break;
-        case 1: k_poa_modes<256, 16><<<blocks, 256, 0, s>>>(a); break;
-        case 2: k_poa_modes<256, 32><<<blocks, 256, 0, s>>>(a); break;
-        default: k_poa_modes<1024, 32><<<blocks, 1024, 0, s>>>(a); break;
-    }
-}
-
-void launch_affine(int inst, uint32_t blocks, const MArgs& a, hipStream_t s) {
-    switch (inst) {
-        case 0: k_poa_affine<64, 16><<<blocks, 64, 0, s>>>(a); break;
-        case 1: k_poa_affine<256, 16><<<blocks, 256, 0, s>>>(a); break;
-        case 2: k_poa_affine<512, 16><<<blocks, 512, 0, s>>>(a); break;
-        default: k_poa_affine<1024, 16><<<blocks, 1024, 0, s>>>(a); break;
-    }
-}
 
 template <class T> struct Buf {   // device buffer of one call
     T* p = nullptr;
@@ -515,7 +625,8 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
     const Inst* const inst = aff ? kInstAffine : kInst;
     const uint32_t max_len = aff ? MAX_LEN_AFFINE : MAX_LEN;
     const uint64_t cell_bytes = aff ? 8 : 4;   // affine: an (H, F) pair per cell
-    const std::string who = aff ? "hx_poa_sequences_affine" : "hx_poa_sequences_mode";
+    const bool msa = a.msa != 0;
+    const std::string who = msa ? "hx_poa_msa" : aff ? "hx_poa_sequences_affine" : "hx_poa_sequences_mode";
     const uint64_t nseq = a.set_off[ns], nb = a.seq_off[nseq];
     std::vector<MSet> sets(ns);
     std::vector<uint64_t> cns_off((size_t)ns + 1, 0);
@@ -545,6 +656,12 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
     MCHK(hipMemcpyAsync(d_soff.p, a.seq_off, (nseq + 1) * 8, hipMemcpyHostToDevice, s));
     MCHK(hipMemsetAsync(d_cns_len.p, 0, std::max<size_t>(1, ns) * 4, s));
     MCHK(hipMemsetAsync(d_cells.p, 0, std::max<size_t>(1, ns) * 8, s));
+    Buf<uint32_t> d_base_col, d_n_cols, d_cns_col;   // MSA calls only
+    if (msa) {
+        MCHK(d_base_col.alloc(nb)); MCHK(d_n_cols.alloc(ns));
+        MCHK(hipMemsetAsync(d_n_cols.p, 0, std::max<size_t>(1, ns) * 4, s));
+        if (a.include_consensus) MCHK(d_cns_col.alloc(cns_off[ns]));
+    }
 
     // H is sized from an estimate of the graph's final size (noisy copies add about a tenth of their length each); a set that outgrows its
     // slot comes back and is rerun with twice the room (or the room for what it had when it stopped, doubled), the worst case at most
@@ -585,7 +702,7 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
             if (first && a.slot_kb_cap) sb = std::max(pmax, std::min<uint64_t>(sb, (uint64_t)a.slot_kb_cap << 10));   // (test switch: forces the overflow and rerun)
             sb = al256(sb);
             int occ = 0;
-            MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, inst[k].fn, inst[k].nt, 0));
+            MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, msa ? inst[k].fn_msa : inst[k].fn, inst[k].nt, 0));
             const uint64_t resident = (uint64_t)std::max(1, occ) * (uint64_t)n_cu;
             const uint64_t fit = budget / sb;
             if (fit == 0) { err = who + ": set " + std::to_string(big) + " needs " + std::to_string(sb) + " bytes of workspace, more than the budget of " + std::to_string(budget) + " (option poa_workspace_gb)"; return -1; }
@@ -608,9 +725,10 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
         for (int k = 0; k < N_INST; k++) {
             if (by[k].empty()) continue;
             MArgs q{d_sets.p, d_order.p + base[k], (uint32_t)by[k].size(), d_counter.p + k, d_codes.p, d_soff.p, (uint8_t*)ws.p, slot[k],
-                    a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p, a.gap_extend};
-            if (aff) launch_affine(k, nslots[k], q, s); else launch(k, nslots[k], q, s);
-            MCHK(hipGetLastError());
+                    a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p, a.gap_extend,
+                    d_base_col.p, d_n_cols.p, d_cns_col.p};
+            void* kargs[] = {&q};
+            MCHK(hipLaunchKernel(msa ? inst[k].fn_msa : inst[k].fn, dim3(nslots[k]), dim3((uint32_t)inst[k].nt), kargs, 0, s));
             o.launches++;
             if (a.debug) fprintf(stderr, "[hx] POA modes%s: %zu sets on %u workgroups of %d lanes x %d columns, slots of %.1f MB\n", aff ? " (affine)" : "", by[k].size(), nslots[k], inst[k].nt, inst[k].cpl, slot[k] / 1e6);
         }
@@ -644,6 +762,53 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
         o.cns_off[i + 1] = o.cns.size();
         o.cells += cells[i];
     }
+    if (!msa) return 0;
+
+    // the MSA text: now that the columns of every set are known, the rows' places (set i = rows x n_cols bytes, row-major), one descriptor per
+    // row and one work item per 64 bases of a row for k_msa_rows
+    o.msa_cols.assign(ns, 0);
+    MCHK(hipMemcpy(o.msa_cols.data(), d_n_cols.p, ns * 4, hipMemcpyDeviceToHost));
+    o.msa_rows.assign(ns, 0);
+    o.msa_off.assign((size_t)ns + 1, 0);
+    std::vector<MRow> rows;
+    std::vector<uint2> chunks;
+    auto add_row = [&](uint64_t src, uint64_t dst, uint32_t n, uint32_t ncols, uint32_t is_cns) {
+        const uint32_t r = (uint32_t)rows.size();
+        rows.push_back(MRow{src, dst, n, ncols, is_cns, 0});
+        for (uint32_t f = 0; f == 0 || f < n; f += 64) chunks.push_back(make_uint2(r, f));
+    };
+    for (uint32_t i = 0; i < ns; i++) {
+        const uint32_t nc = o.msa_cols[i];
+        uint64_t dst = o.msa_off[i];
+        if (nc) {   // (no column: no non-empty sequence, nothing to write)
+            for (uint64_t k = a.set_off[i]; k < a.set_off[i + 1]; k++, dst += nc) add_row(a.seq_off[k], dst, (uint32_t)(a.seq_off[k + 1] - a.seq_off[k]), nc, 0);
+            if (a.include_consensus) { add_row(cns_off[i], dst, len[i], nc, 1); dst += nc; }
+        }
+        o.msa_rows[i] = sets[i].nseq + (a.include_consensus ? 1u : 0u);
+        o.msa_off[i + 1] = o.msa_off[i] + (uint64_t)o.msa_rows[i] * nc;
+    }
+    if (rows.size() >= 0xffffffffULL || chunks.size() >= 0xffffffffULL / 64) { err = who + ": too many rows"; return -1; }
+    const uint64_t out_bytes = o.msa_off[ns];
+    o.msa.resize(out_bytes);
+    if (out_bytes == 0) return 0;
+    Buf<MRow> d_rows; Buf<uint2> d_chunks; Buf<char> d_out;
+    MCHK(d_rows.alloc(rows.size())); MCHK(d_chunks.alloc(chunks.size()));
+    {
+        const hipError_t e = d_out.alloc(out_bytes);
+        if (e != hipSuccess) { err = who + ": the " + std::to_string(out_bytes) + " bytes of the alignment text could not be allocated on the device: " + hipGetErrorString(e); return -1; }
+    }
+    MCHK(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * sizeof(MRow), hipMemcpyHostToDevice, s));
+    MCHK(hipMemcpyAsync(d_chunks.p, chunks.data(), chunks.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
+    MCHK(hipEventRecord(e0, s));
+    k_msa_rows<<<(uint32_t)((chunks.size() + 3) / 4), 256, 0, s>>>(d_rows.p, d_chunks.p, (uint32_t)chunks.size(), d_base_col.p, d_codes.p, d_cns_col.p, d_cns.p, d_out.p);
+    MCHK(hipGetLastError());
+    MCHK(hipEventRecord(e1, s));
+    MCHK(hipEventSynchronize(e1));
+    float rows_ms = 0;
+    MCHK(hipEventElapsedTime(&rows_ms, e0, e1));
+    o.msa_rows_ms = rows_ms; o.kernel_ms += rows_ms; o.launches++;
+    o.msa_moved_bytes = out_bytes + 4 * (nb + (a.include_consensus ? o.cns.size() : 0));
+    MCHK(hipMemcpy(&o.msa[0], d_out.p, out_bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -71,6 +71,18 @@ class PoaAffineParams(C.Structure):
     _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("type", C.c_int32)]
 
 
+class PoaMsaParams(C.Structure):
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("type", C.c_int32),
+                ("include_consensus", C.c_int32)]
+
+
+class MsaOut(C.Structure):
+    _fields_ = [("n_set", C.c_uint32), ("n_rows", u32p), ("n_cols", u32p), ("msa_off", u64p), ("msa", C.POINTER(C.c_char)),
+                ("cns_off", u64p), ("cns", C.POINTER(C.c_char)),
+                ("dp_cells", C.c_uint64), ("seq_bases", C.c_uint64), ("n_aligned", C.c_uint64),
+                ("rows_kernel_ms", C.c_double), ("rows_kernel_bytes", C.c_uint64)]
+
+
 class Backend(C.Structure):
     _fields_ = [("ctx", C.c_void_p)] + [(k, C.c_void_p) for k in
                                         ("chain_reads", "edge_support", "edge_coords", "poa_batch", "free_chain",
@@ -132,3 +144,14 @@ def cns_to_list(c):
     off = arr(c.cns_off, c.n_edge + 1, np.uint64)
     raw = C.string_at(c.cns, int(off[-1])) if c.n_edge else b""
     return [raw[int(off[i]):int(off[i + 1])].decode() for i in range(c.n_edge)]
+
+
+def msa_to_lists(o):
+    """(rows per set, consensus per set) of an MsaOut"""
+    n = o.n_set
+    off, coff = arr(o.msa_off, n + 1, np.uint64), arr(o.cns_off, n + 1, np.uint64)
+    nr, nc = arr(o.n_rows, n, np.uint32), arr(o.n_cols, n, np.uint32)
+    raw = C.string_at(o.msa, int(off[-1])) if n else b""
+    craw = C.string_at(o.cns, int(coff[-1])) if n else b""
+    rows = [[raw[int(off[i]) + r * int(nc[i]):int(off[i]) + (r + 1) * int(nc[i])].decode() for r in range(int(nr[i]))] for i in range(n)]
+    return rows, [craw[int(coff[i]):int(coff[i + 1])].decode() for i in range(n)]

@@ -15,7 +15,7 @@ _lib = None
 SYMBOLS = ["hx_last_error", "hx_device_count", "hx_ctx_create", "hx_ctx_destroy", "hx_upload", "hx_set_read_shard", "hx_set_prefiltered",
            "hx_chain_reads", "hx_edge_support", "hx_edge_coords", "hx_poa_batch", "hx_free_chain", "hx_free_edges",
            "hx_free_coords", "hx_free_cns", "hx_edge_emit", "hx_edge_records_bytes", "hx_edge_records_export",
-           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
+           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
            "hx_set_option", "hx_get_option", "hx_option_names", "hx_poa_memory_stats", "hx_poa_release_workspace", "hx_poa_prune_stats", "hx_group_set_timeout", "hx_group_inject_fault", "hx_poa_reserve", "hx_poa_host_times", "hx_poa_arena_stats", "hx_group_rccl_ranks",
            "hx_group_create", "hx_group_destroy", "hx_group_size", "hx_group_ctx", "hx_group_transport", "hx_edge_merge", "hx_group_backend_fill", "hx_group_exchange_stats"]
 
@@ -45,6 +45,8 @@ def lib():
         L.hx_poa_sequences.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.POINTER(T.PoaParams), C.POINTER(T.CnsOut)]
         L.hx_poa_sequences_mode.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.POINTER(T.PoaModeParams), C.POINTER(T.CnsOut)]
         L.hx_poa_sequences_affine.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.POINTER(T.PoaAffineParams), C.POINTER(T.CnsOut)]
+        L.hx_poa_msa.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.POINTER(T.PoaMsaParams), C.POINTER(T.MsaOut)]
+        L.hx_free_msa.argtypes = [C.c_void_p, C.POINTER(T.MsaOut)]
         L.hx_free_chain.argtypes = [C.c_void_p, C.POINTER(T.ChainOut)]
         L.hx_free_edges.argtypes = [C.c_void_p, C.POINTER(T.EdgesOut)]
         L.hx_free_coords.argtypes = [C.c_void_p, C.POINTER(T.CoordsOut)]
@@ -329,6 +331,30 @@ class HipContext:
         st = {"dp_cells": o.dp_cells, "seq_bases": o.seq_bases, "n_aligned": o.n_aligned}
         lib().hx_free_cns(self._h, C.byref(o))
         return (r, st) if stats else r
+
+    def poa_msa(self, sets, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=None, include_consensus=False, stats=False):
+        """the multiple sequence alignment of every set (spoa's generate_multiple_sequence_alignment): per set the list of its rows, one
+        per given sequence in the given order (an empty sequence: a row of gaps) and, with include_consensus, the consensus as the last
+        row; all rows of a set have its number of columns. gap_extend None (or equal to gap_open) is the linear gap model. With
+        stats=True returns (rows, consensus strings, counters): dp_cells, seq_bases, n_aligned as poa_sequences_affine has them, and
+        rows_kernel_ms / rows_kernel_bytes of the kernel that writes the row text."""
+        import numpy as np
+        if type not in T.POA_TYPES:
+            raise ValueError(f"unknown alignment type {type!r} (sw, nw, ov)")
+        set_off = np.zeros(len(sets) + 1, dtype=np.uint64)
+        seqs = [q for st in sets for q in st]
+        for i, st in enumerate(sets):
+            set_off[i + 1] = set_off[i] + len(st)
+        seq_off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        for i, q in enumerate(seqs):
+            seq_off[i + 1] = seq_off[i] + len(q)
+        o = T.MsaOut()
+        mp = T.PoaMsaParams(match, mismatch, gap_open, gap_open if gap_extend is None else gap_extend, T.POA_TYPES[type], int(bool(include_consensus)))
+        self._chk(lib().hx_poa_msa(self._h, len(sets), set_off.ctypes.data_as(T.u64p), seq_off.ctypes.data_as(T.u64p), "".join(seqs).encode(), C.byref(mp), C.byref(o)))
+        rows, cns = T.msa_to_lists(o)
+        st = {"dp_cells": o.dp_cells, "seq_bases": o.seq_bases, "n_aligned": o.n_aligned, "rows_kernel_ms": o.rows_kernel_ms, "rows_kernel_bytes": o.rows_kernel_bytes}
+        lib().hx_free_msa(self._h, C.byref(o))
+        return (rows, cns, st) if stats else rows
 
     def poa_phase_cycles(self):
         a, b = (C.c_uint64 * 6)(), (C.c_uint64 * 6)()

@@ -101,10 +101,21 @@ int hx_poa_sequences_mode(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, con
  *                     the general path: a cell holds H and F, sequences of up to 16383 bases. Errors: gap_open >= 0, gap_extend > 0,
  *                     gap_extend < gap_open (refused, not reinterpreted: what spoa does with such scores cannot be checked here), unknown type. */
 int hx_poa_sequences_affine(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_affine_params*, hx_cns_out* out);
+/*   hx_poa_msa        the multiple sequence alignment of every set beside its consensus (spoa's generate_multiple_sequence_alignment; DESIGN.md
+ *                     "General POA path", "MSA output"): one gapped row per GIVEN sequence, in the given order, all of the set's n_cols columns
+ *                     wide, and with include_consensus the consensus as one more, last row. Columns are spoa's: the nodes in rank order, aligned
+ *                     nodes sharing one. An empty sequence gives a row of gaps; a set without a non-empty sequence has n_cols = 0. Letters other
+ *                     than ACGT are read as A, as everywhere, and rows show what was read. Scores, types, errors and limits are
+ *                     hx_poa_sequences_affine's (gap_extend == gap_open: the linear instances, sequences of up to 32767 bases); every type,
+ *                     HX_POA_NW too, runs the general path (the tuned global path keeps no node per base). Options poa_modes_slot_kb and
+ *                     poa_workspace_gb act as on the other entries. Like the rest of the general path it is NOT pinned against spoa itself
+ *                     (the library is not available to the tests): the tests hold it to a CPU restatement of spoa's rule. */
+int hx_poa_msa(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_msa_params*, hx_msa_out* out);
 void hx_free_chain(hx_ctx*, hx_chain_out*);
 void hx_free_edges(hx_ctx*, hx_edges_out*);
 void hx_free_coords(hx_ctx*, hx_coords_out*);
 void hx_free_cns(hx_ctx*, hx_cns_out*);
+void hx_free_msa(hx_ctx*, hx_msa_out*);
 
 /* multi-GPU exchange of the edge-support multiset (one all-gather between hx_chain_reads and the sort):
  *   hx_edge_emit            emit this shard's records (unsorted) on the device, returns their number

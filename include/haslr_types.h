@@ -144,6 +144,32 @@ typedef struct {
     int32_t type; /* hx_poa_type */
 } hx_poa_affine_params;
 
+/* hx_poa_msa: hx_poa_sequences_affine's scores and type (gap_extend == gap_open is the linear model), and whether the consensus is
+ * the last row of every set. */
+typedef struct {
+    int32_t match, mismatch, gap_open, gap_extend;
+    int32_t type; /* hx_poa_type */
+    int32_t include_consensus; /* 0 / 1 */
+} hx_poa_msa_params;
+
+/* Multiple sequence alignment of every set (spoa's generate_multiple_sequence_alignment): set i is n_rows[i] rows of n_cols[i]
+ * characters (ACGT and '-'), row-major without terminators, at msa + msa_off[i]. One row per GIVEN sequence, in the given order (an
+ * empty sequence: a row of gaps), then the consensus row when it was asked for; a set without a non-empty sequence has no column.
+ * The consensus strings and the work counters are hx_cns_out's. */
+typedef struct {
+    uint32_t n_set;
+    uint32_t* n_rows;  /* n_set */
+    uint32_t* n_cols;  /* n_set */
+    uint64_t* msa_off; /* n_set+1; msa_off[i+1] - msa_off[i] = n_rows[i] * n_cols[i] */
+    char* msa;
+    uint64_t* cns_off; /* n_set+1 */
+    char* cns;
+    uint64_t dp_cells, seq_bases, n_aligned;
+    /* the kernel that writes the rows, on its own: its time by device events and the bytes it has to move (text + 4 per base read) */
+    double rows_kernel_ms;
+    uint64_t rows_kernel_bytes;
+} hx_msa_out;
+
 #ifdef __cplusplus
 }
 #endif

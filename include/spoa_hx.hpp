@@ -32,6 +32,14 @@
 // every launch instead of one. spoa::hx::consensus_batch() below is the entry to use from new code: all edges in one call (that is what
 // haslr_amd's own pipeline does through hx_poa_batch). spoa::hx::stats() tells how many device calls served how many sets.
 //
+// The second output of a spoa graph, the multiple sequence alignment, is there too: Graph::generate_multiple_sequence_alignment(dst,
+// include_consensus) with spoa's signature sends the recorded sequences through hx_poa_msa (every alignment type runs the general path
+// there) and replaces dst by one gapped row per added sequence, in the order they were added, plus the consensus as the last row when asked
+// for. As in spoa, add_alignment ignores an empty sequence, so it has no row (the C-ABI and spoa::hx::msa_batch give a row of gaps for an
+// empty member of a set). An MSA call is NOT flat-combined with other threads' calls: it takes the device's mutex like consensus_batch and
+// is one device call of its own; spoa::hx::msa_batch() takes many sets in one call. Like kSW, kOV and the affine engines, the MSA is held to
+// a CPU restatement of spoa's rule by the tests, not to spoa itself, which is not available to them.
+//
 // This is product code. It is never used to build oracle/_ref (a reference build must not be made with stand-in
 // headers): tests/test_spoa_header.py compiles a small caller written against the five symbols, nothing else.
 #ifndef HASLR_SPOA_HX_HPP
@@ -176,6 +184,40 @@ inline std::vector<std::string> consensus_batch(const std::vector<std::vector<st
     return consensus_batch(p, type, m, n, g, e);
 }
 
+// the multiple sequence alignment of every set in ONE device call (hx_poa_msa): per set one gapped row per sequence, in order, all of
+// the set's column count wide, and with include_consensus the consensus as one more, last row. e == g is the linear gap model. The C-ABI's
+// rule holds here: an empty sequence in a set gives a row of gaps (Graph below never records one, as spoa ignores it).
+inline std::vector<std::vector<std::string>> msa_batch(const std::vector<const std::vector<std::string>*>& sets, AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8,
+                                                       std::int8_t e = -8, bool include_consensus = false) {
+    std::vector<std::uint64_t> set_off{0}, seq_off{0};
+    std::string bases;
+    for (const auto* st : sets) {
+        for (const auto& s : *st) { bases += s; seq_off.push_back(bases.size()); }
+        set_off.push_back(seq_off.size() - 1);
+    }
+    const hx_poa_msa_params mp{m, n, g, e, static_cast<std::int32_t>(type), include_consensus ? 1 : 0};
+    hx_msa_out out;
+    Device& d = device();
+    std::lock_guard<std::mutex> lock(d.mu);
+    hx_ctx* ctx = context_locked(d);
+    if (hx_poa_msa(ctx, (std::uint32_t)sets.size(), set_off.data(), seq_off.data(), bases.c_str(), &mp, &out) != 0)
+        throw std::runtime_error(std::string("spoa_hx: ") + hx_last_error());
+    std::vector<std::vector<std::string>> res(sets.size());
+    for (std::size_t i = 0; i < sets.size(); i++)
+        for (std::uint32_t r = 0; r < out.n_rows[i]; r++) {
+            const char* p = out.msa + out.msa_off[i] + (std::uint64_t)r * out.n_cols[i];
+            res[i].emplace_back(p, p + out.n_cols[i]);
+        }
+    hx_free_msa(ctx, &out);
+    return res;
+}
+inline std::vector<std::vector<std::string>> msa_batch(const std::vector<std::vector<std::string>>& sets, AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8,
+                                                       std::int8_t e = -8, bool include_consensus = false) {
+    std::vector<const std::vector<std::string>*> p;
+    for (const auto& st : sets) p.push_back(&st);
+    return msa_batch(p, type, m, n, g, e, include_consensus);
+}
+
 // one set on behalf of one caller thread, combined with whatever other threads have queued (see "Threads" above)
 inline std::string consensus_combined(const std::vector<std::string>& seqs, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) {
     Device& d = device();
@@ -279,6 +321,13 @@ public:
     std::string generate_consensus() {
         if (sequences_.empty()) return std::string();
         return hx::consensus_combined(sequences_, type_, m_, n_, g_, e_);
+    }
+    // spoa::Graph::generate_multiple_sequence_alignment(dst, include_consensus = false): dst is replaced by one row per added sequence
+    // (and the consensus row). A device call of its own, not combined with other threads' calls.
+    void generate_multiple_sequence_alignment(std::vector<std::string>& dst, bool include_consensus = false) {
+        dst.clear();
+        if (sequences_.empty()) return;
+        dst = std::move(hx::msa_batch(std::vector<const std::vector<std::string>*>{&sequences_}, type_, m_, n_, g_, e_, include_consensus)[0]);
     }
 
 private:

@@ -8,7 +8,10 @@ For every mode: sets, cells (sum of V x L, the full matrices spoa computes), ker
 --repeats runs), GCUPS; for context the tuned kNW path on the same sets, and the CPU restatement (tests/poa_modes_ref.cpp) on 16 threads over
 a sample of the sets (GCUPS of the sample). Every row also runs the affine kernel on the same sets (hx_poa_sequences_affine with
 --affine-scores, default 5 -4 -8 -6): same figures, the affine / linear ratio of the median kernel times, and the sample compared with the
-affine restatement (tests/poa_affine_ref.cpp). Prints one JSON line."""
+affine restatement (tests/poa_affine_ref.cpp). And every row asks for the multiple sequence alignment of the same sets (hx_poa_msa, linear
+scores, with the consensus row): kernel time against the consensus-only general path ("over_general": ratio of the medians, and the
+smallest and largest ratio the repeats allow), the kernel that writes the row text on its own (time by device events, the bytes it has to
+move = text + 4 per base read, GB/s), and the sample compared with the MSA restatement (tests/poa_msa_ref.cpp). Prints one JSON line."""
 import argparse
 import json
 import os
@@ -89,6 +92,7 @@ def main():
     ap.add_argument("--affine-scores", type=int, nargs=4, default=[5, -4, -8, -6], metavar=("M", "N", "G", "E"), help="match, mismatch, gap open, gap extend of the affine rows")
     a = ap.parse_args()
     from haslr_amd import hip
+    import msalib
     import parlib
     import pmrlib
     rng = np.random.default_rng(a.seed)
@@ -100,6 +104,7 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         ref = pmrlib.ModesRef(d)
         aref = parlib.AffineRef(d)
+        mref = msalib.MsaRef(d)
         for name, (mode, sets) in loads.items():
             r = {"mode": mode, "sets": len(sets)}
             for path, opts in (("general", {"poa_general": 1}), ("tuned_nw", {})):
@@ -128,6 +133,24 @@ def main():
             with ThreadPoolExecutor(16) as ex:
                 out = list(ex.map(lambda st: aref.consensus(st, mode, *a.affine_scores), sample))
             r["affine_sample_equal"] = ctx.poa_sequences_affine(sample, mode, *a.affine_scores) == out
+            rows_ms, moved = [], 0
+
+            def msa_call():
+                nonlocal moved
+                st = ctx.poa_msa(sets, mode, include_consensus=True, stats=True)[2]
+                rows_ms.append(st["rows_kernel_ms"])
+                moved = st["rows_kernel_bytes"]
+            ms = gpu_time(ctx, msa_call, a.repeats)
+            med, gen = float(np.median(ms)), r["general"]
+            rmed = float(np.median(rows_ms[1:]))
+            r["msa"] = {"kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
+                        "over_general": round(med / gen["kernel_ms_median"], 4), "over_general_min": round(min(ms) / gen["kernel_ms_max"], 4),
+                        "over_general_max": round(max(ms) / gen["kernel_ms_min"], 4),
+                        "rows_kernel": {"ms_median": round(rmed, 4), "ms_min": round(min(rows_ms[1:]), 4), "ms_max": round(max(rows_ms[1:]), 4),
+                                        "bytes": int(moved), "gb_per_s": round(moved / rmed / 1e6, 1)}}
+            with ThreadPoolExecutor(16) as ex:
+                out = list(ex.map(lambda st: mref.rows(st, mode, include_consensus=True), sample))
+            r["msa_sample_equal"] = ctx.poa_msa(sample, mode, include_consensus=True) == out
             res[name] = r
     ctx.close()
     print(json.dumps(res))
