@@ -507,6 +507,41 @@ extern "C" int hx_poa_msa(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, c
     return 0;
 }
 
+// the consensus under per-base weights with coverage and profile: the general path's instances that keep the node of every base (all
+// three types), the weighted ones when weights are given
+extern "C" int hx_poa_weighted(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_weighted_params* wp, hx_wcns_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!wp) return fail("hx_poa_weighted: no parameters");
+    if (check_affine_call("hx_poa_weighted", wp->gap_open, wp->gap_extend, wp->type, set_off[n_sets])) return -1;
+    if (weights)
+        for (uint32_t i = 0; i < n_sets; i++)
+            for (uint64_t k = set_off[i]; k < set_off[i + 1]; k++)
+                for (uint64_t p = seq_off[k]; p < seq_off[k + 1]; p++)
+                    if (weights[p] == 0)
+                        return fail("hx_poa_weighted: set " + std::to_string(i) + ", sequence " + std::to_string(k - set_off[i]) + ", position " + std::to_string(p - seq_off[k]) + ": a weight of 0 is not accepted (weights are 1..255)");
+    HIPCHK(hipSetDevice(c->device));
+    hxk::PoaModesArgs a{n_sets, set_off, seq_off, bases, wp->match, wp->mismatch, wp->gap_open, wp->type, (uint32_t)std::max(0, c->opt.poa_modes_slot_kb), c->opt.poa_workspace_gb, c->opt.debug};
+    a.gap_extend = wp->gap_extend; a.affine = wp->gap_extend != wp->gap_open || c->opt.poa_affine;
+    a.weighted = 1; a.weights = weights; a.want_coverage = wp->want_coverage != 0; a.want_profile = wp->want_profile != 0;
+    std::vector<uint8_t> ones;
+    if (!weights && c->opt.poa_weighted) { ones.assign(std::max<uint64_t>(1, seq_off[set_off[n_sets]]), 1); a.weights = ones.data(); }
+    hxk::PoaModesOut o;
+    std::string err;
+    if (hxk::poa_modes_run(c->stream, c->poa_modes_ws, a, o, err)) return fail(err);
+    c->tm.ms[3] += o.kernel_ms; c->tm.launches[3] += o.launches;
+    auto dup = [](const void* p, size_t bytes) { void* q = malloc(std::max<size_t>(1, bytes)); memcpy(q, p, bytes); return q; };
+    out->n_set = n_sets;
+    out->cns_off = (uint64_t*)dup(o.cns_off.data(), ((size_t)n_sets + 1) * 8);
+    out->cns = (char*)dup(o.cns.data(), o.cns.size());
+    if (a.want_coverage || a.want_profile) out->coverage = (uint32_t*)dup(o.cov.data(), o.cov.size() * 4);
+    if (a.want_profile) out->profile = (uint32_t*)dup(o.prof.data(), o.prof.size() * 4);
+    out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
+    out->cov_kernel_ms = o.cov_ms; out->cov_kernel_bytes = o.cov_moved_bytes;
+    if (c->opt.debug) fprintf(stderr, "[hx] POA weighted call%s: %u sets, %.3g cells, kernels %.2f ms (coverage %.3f ms), %u sets rerun in a larger slot\n", a.affine ? " (affine)" : "", n_sets, (double)o.cells, o.kernel_ms, o.cov_ms, o.retried);
+    return 0;
+}
+
+extern "C" void hx_free_wcns(hx_ctx*, hx_wcns_out* o) { free(o->cns_off); free(o->cns); free(o->coverage); free(o->profile); memset(o, 0, sizeof(*o)); }
 extern "C" void hx_free_cns(hx_ctx*, hx_cns_out* o) { free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }
 extern "C" void hx_free_msa(hx_ctx*, hx_msa_out* o) { free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa); free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }
 

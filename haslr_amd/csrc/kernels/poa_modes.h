@@ -29,6 +29,10 @@ struct PoaModesArgs {
     int affine = 0;                      // 1: the affine instances (a cell is an (H, F) pair, sequences of up to 16383 bases)
     int msa = 0;                         // 1: the MSA instances, and the alignment text in PoaModesOut (hx_poa_msa)
     int include_consensus = 0;           // MSA calls: the consensus is the last row of every set
+    int weighted = 0;                    // 1: hx_poa_weighted (the instances that keep the node of every base; errors name that entry)
+    const uint8_t* weights = nullptr;    // weighted calls: a weight per base of `bases`, 1..255 (the caller has checked), or null: all 1
+    int want_coverage = 0;               // weighted calls: the coverage of every consensus base in PoaModesOut
+    int want_profile = 0;                // weighted calls: and the four letter counts of its column
 };
 
 struct PoaModesOut {
@@ -44,6 +48,10 @@ struct PoaModesOut {
     std::string msa;
     double msa_rows_ms = 0;              // the row-writing kernel alone (it is part of kernel_ms)
     uint64_t msa_moved_bytes = 0;        // what it has to move: the text + 4 bytes per base read
+    // weighted calls: per consensus base (cns's layout) its coverage, and four letter counts (A, C, G, T) when asked for
+    std::vector<uint32_t> cov, prof;
+    double cov_ms = 0;                   // the coverage kernels alone, with the clearing of their counters (part of kernel_ms)
+    uint64_t cov_moved_bytes = 0;        // what they have to move
 };
 
 // 0 = ok, else -1 with the reason in err

@@ -20,6 +20,11 @@
 // The multiple sequence alignment of a set (hx_poa_msa; DESIGN.md "MSA output") comes from the same workgroup under a template flag: it keeps
 // the node of every base that add_alignment reports, turns nodes into columns after the last sort, and a second, grid-wide kernel
 // (k_msa_rows) writes the row text once the host knows the sizes.
+//
+// Per-base weights and consensus coverage (hx_poa_weighted; DESIGN.md "Base weights and coverage") are one more template flag on top of the
+// MSA one: after add_alignment all lanes add w[i-1] + w[i] - 2 to the edge between the nodes of bases i-1 and i (add_alignment gave it 2), so
+// the heaviest bundle sees spoa's weighted edges; two grid-wide kernels (k_cov_hist, k_cov_gather) count the bases per column and letter and
+// pick the counts at the consensus bases' columns.
 #include <algorithm>
 #include <chrono>
 #include <numeric>
@@ -53,6 +58,7 @@ struct MArgs {
     // MSA instances only: per base of the call (global offset) its node, rewritten to its column when the set is done; columns per set;
     // column of every consensus base beside cns (null: not asked for)
     uint32_t *base_col, *n_cols, *cns_col;
+    const uint8_t* wts;   // weighted instances only: the weight of every base of the call (1..255), beside codes
 };
 
 // one row of the MSA text: its columns (rising) start at cols[src], its letters at codes[src] (a sequence) or cns[src] (the consensus row)
@@ -495,7 +501,64 @@ __global__ __launch_bounds__(256) void k_msa_rows(const MRow* rows, const uint2*
     }
 }
 
-template <int NT, int CPL, bool AFF = false, bool MSA = false>
+// ---- base weights and coverage (DESIGN.md "General POA path", "Base weights and coverage") ----
+// spoa's weighted add_alignment, applied beside the unit-weight one: the sequence walks the edge path[i-1] -> path[i] for every pair of
+// consecutive bases (prefix chain, aligned part, suffix chain alike) and add_alignment has given each of them 2; what is missing to spoa's
+// w[i-1] + w[i] is added here, by all lanes. The nodes of one sequence are distinct (its columns rise strictly), so no two lanes meet on an
+// edge. The edge is looked up in the out-list of path[i-1], as add_edge does.
+template <int NT>
+__device__ void weigh_path(G& g, const uint32_t* path, const uint8_t* w, const uint32_t L) {
+    for (uint32_t i = threadIdx.x + 1; i < L; i += NT) {
+        const int32_t extra = (int32_t)w[i - 1] + (int32_t)w[i] - 2;
+        if (extra == 0) continue;
+        const uint32_t to = path[i];
+        for (uint32_t e = g.out_head[path[i - 1]]; e != NONE; e = g.e_next_out[e])
+            if (g.e_to[e] == to) { g.e_w[e] += extra; break; }
+    }
+}
+
+// one sequence of >= 2 bases (k_cov_hist: src = its first base, hoff = the first column of its set among all columns of the call) or one
+// consensus (k_cov_gather: src = its place beside the device's consensus text, dst = its place in the output)
+struct CRow { uint64_t src, dst, hoff; uint32_t len, ncols; };
+
+// The number of bases per column (stride 1) or per column and letter (stride 4) of one call, grid-wide: a wavefront takes 64 consecutive
+// bases of one sequence. Columns rise strictly along a sequence, so the lanes of a wavefront never meet on a counter; different sequences
+// of a set do, hence the atomic.
+__global__ __launch_bounds__(256) void k_cov_hist(const CRow* rows, const uint2* chunks, const uint32_t n_chunks, const uint32_t* base_col, const uint8_t* codes,
+                                                  const uint32_t stride, uint32_t* hist) {
+    const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (w >= n_chunks) return;
+    const uint2 ch = chunks[w];
+    const CRow R = rows[ch.x];
+    const uint32_t i = ch.y + lane;
+    if (i >= R.len) return;
+    const uint32_t c = base_col[R.src + i];
+    if (c >= R.ncols) return;   // (never true for the columns run_set leaves: the guard keeps the add inside the set's counters)
+    atomicAdd(&hist[(R.hoff + c) * stride + (stride == 4 ? (uint32_t)(codes[R.src + i] & 3) : 0u)], 1u);
+}
+
+// coverage (and the four letter counts) of every consensus base: the counters of its column. A wavefront takes 64 consecutive bases of
+// one consensus; cov / prof are in the output's layout (consensus strings back to back).
+__global__ __launch_bounds__(256) void k_cov_gather(const CRow* rows, const uint2* chunks, const uint32_t n_chunks, const uint32_t* cns_col, const uint32_t* hist,
+                                                    const uint32_t stride, uint32_t* cov, uint32_t* prof) {
+    const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (w >= n_chunks) return;
+    const uint2 ch = chunks[w];
+    const CRow R = rows[ch.x];
+    const uint32_t i = ch.y + lane;
+    if (i >= R.len) return;
+    const uint32_t c = cns_col[R.src + i];
+    uint32_t n[4] = {0, 0, 0, 0};
+    if (c < R.ncols) {
+        const uint32_t* h = hist + (R.hoff + c) * stride;
+        n[0] = h[0];
+        if (stride == 4) { n[1] = h[1]; n[2] = h[2]; n[3] = h[3]; }
+    }
+    cov[R.dst + i] = n[0] + n[1] + n[2] + n[3];
+    if (prof) { uint32_t* p = prof + 4 * (R.dst + i); p[0] = n[0]; p[1] = n[1]; p[2] = n[2]; p[3] = n[3]; }
+}
+
+template <int NT, int CPL, bool AFF = false, bool MSA = false, bool WTS = false>
 __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Shared& sh, int* s_wtot, uint32_t* s_scan) {
     const uint32_t t = threadIdx.x;
     const MSet S = a.sets[set];
@@ -534,6 +597,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
         V = sh.V; E = sh.E;
         if (sh.fail) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
         if (MSA) for (uint32_t i = t; i < L; i += NT) a.base_col[b + i] = path[i];   // (node ids never change: a rerun set rewrites its part)
+        if (WTS) weigh_path<NT>(g, path, a.wts + b, L);   // (order_rows reads e_w behind its barriers)
         order_rows<NT>(g, V, s_scan);
     }
     if (MSA) {
@@ -557,7 +621,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     __syncthreads();   // the slot is free for the next set
 }
 
-template <int NT, int CPL, bool MSA = false>
+template <int NT, int CPL, bool MSA = false, bool WTS = false>
 __global__ __launch_bounds__(NT) void k_poa_modes(MArgs a) {
     __shared__ Shared sh;
     __shared__ int s_wtot[NT / 64];
@@ -569,11 +633,11 @@ __global__ __launch_bounds__(NT) void k_poa_modes(MArgs a) {
         const uint32_t q = sh.item;
         __syncthreads();
         if (q >= a.n_items) return;
-        run_set<NT, CPL, false, MSA>(a, a.order[q], slot, sh, s_wtot, s_scan);
+        run_set<NT, CPL, false, MSA, WTS>(a, a.order[q], slot, sh, s_wtot, s_scan);
     }
 }
 
-template <int NT, int CPL, bool MSA = false>
+template <int NT, int CPL, bool MSA = false, bool WTS = false>
 __global__ __launch_bounds__(NT) void k_poa_affine(MArgs a) {
     __shared__ Shared sh;
     __shared__ int s_wtot[NT / 64];
@@ -585,27 +649,28 @@ __global__ __launch_bounds__(NT) void k_poa_affine(MArgs a) {
         const uint32_t q = sh.item;
         __syncthreads();
         if (q >= a.n_items) return;
-        run_set<NT, CPL, true, MSA>(a, a.order[q], slot, sh, s_wtot, s_scan);
+        run_set<NT, CPL, true, MSA, WTS>(a, a.order[q], slot, sh, s_wtot, s_scan);
     }
 }
 
 // the instances: workgroup lanes x columns per lane; a set goes to the first whose NT x CPL columns hold its longest sequence + 1.
-// Each has a twin that also records the MSA (a template flag: a consensus-only call runs the code it ran before the MSA existed).
-struct Inst { int nt, cpl; const void* fn; const void* fn_msa; };
+// Each has a twin that also records the MSA (a template flag: a consensus-only call runs the code it ran before the MSA existed), and a
+// second twin that records the MSA and applies base weights (hx_poa_weighted with weights; coverage needs the node of every base anyway).
+struct Inst { int nt, cpl; const void* fn; const void* fn_msa; const void* fn_w; };
 const Inst kInst[] = {
-    {64, 16, (const void*)k_poa_modes<64, 16>, (const void*)k_poa_modes<64, 16, true>},
-    {256, 16, (const void*)k_poa_modes<256, 16>, (const void*)k_poa_modes<256, 16, true>},
-    {256, 32, (const void*)k_poa_modes<256, 32>, (const void*)k_poa_modes<256, 32, true>},
-    {1024, 32, (const void*)k_poa_modes<1024, 32>, (const void*)k_poa_modes<1024, 32, true>},
+    {64, 16, (const void*)k_poa_modes<64, 16>, (const void*)k_poa_modes<64, 16, true>, (const void*)k_poa_modes<64, 16, true, true>},
+    {256, 16, (const void*)k_poa_modes<256, 16>, (const void*)k_poa_modes<256, 16, true>, (const void*)k_poa_modes<256, 16, true, true>},
+    {256, 32, (const void*)k_poa_modes<256, 32>, (const void*)k_poa_modes<256, 32, true>, (const void*)k_poa_modes<256, 32, true, true>},
+    {1024, 32, (const void*)k_poa_modes<1024, 32>, (const void*)k_poa_modes<1024, 32, true>, (const void*)k_poa_modes<1024, 32, true, true>},
 };
 constexpr int N_INST = sizeof(kInst) / sizeof(kInst[0]);
 constexpr uint32_t MAX_LEN = 1024 * 32 - 1;
 // the affine instances keep two accumulators per column (diagonal and F): 16 columns per lane throughout, more lanes instead
 const Inst kInstAffine[N_INST] = {
-    {64, 16, (const void*)k_poa_affine<64, 16>, (const void*)k_poa_affine<64, 16, true>},
-    {256, 16, (const void*)k_poa_affine<256, 16>, (const void*)k_poa_affine<256, 16, true>},
-    {512, 16, (const void*)k_poa_affine<512, 16>, (const void*)k_poa_affine<512, 16, true>},
-    {1024, 16, (const void*)k_poa_affine<1024, 16>, (const void*)k_poa_affine<1024, 16, true>},
+    {64, 16, (const void*)k_poa_affine<64, 16>, (const void*)k_poa_affine<64, 16, true>, (const void*)k_poa_affine<64, 16, true, true>},
+    {256, 16, (const void*)k_poa_affine<256, 16>, (const void*)k_poa_affine<256, 16, true>, (const void*)k_poa_affine<256, 16, true, true>},
+    {512, 16, (const void*)k_poa_affine<512, 16>, (const void*)k_poa_affine<512, 16, true>, (const void*)k_poa_affine<512, 16, true, true>},
+    {1024, 16, (const void*)k_poa_affine<1024, 16>, (const void*)k_poa_affine<1024, 16, true>, (const void*)k_poa_affine<1024, 16, true, true>},
 };
 constexpr uint32_t MAX_LEN_AFFINE = 1024 * 16 - 1;
 
@@ -626,7 +691,10 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
     const uint32_t max_len = aff ? MAX_LEN_AFFINE : MAX_LEN;
     const uint64_t cell_bytes = aff ? 8 : 4;   // affine: an (H, F) pair per cell
     const bool msa = a.msa != 0;
-    const std::string who = msa ? "hx_poa_msa" : aff ? "hx_poa_sequences_affine" : "hx_poa_sequences_mode";
+    const bool wtd = a.weighted != 0;                        // hx_poa_weighted: the node of every base is kept, as for the MSA
+    const bool cols = msa || wtd;
+    const bool want_cov = wtd && (a.want_coverage || a.want_profile);
+    const std::string who = wtd ? "hx_poa_weighted" : msa ? "hx_poa_msa" : aff ? "hx_poa_sequences_affine" : "hx_poa_sequences_mode";
     const uint64_t nseq = a.set_off[ns], nb = a.seq_off[nseq];
     std::vector<MSet> sets(ns);
     std::vector<uint64_t> cns_off((size_t)ns + 1, 0);
@@ -656,12 +724,18 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
     MCHK(hipMemcpyAsync(d_soff.p, a.seq_off, (nseq + 1) * 8, hipMemcpyHostToDevice, s));
     MCHK(hipMemsetAsync(d_cns_len.p, 0, std::max<size_t>(1, ns) * 4, s));
     MCHK(hipMemsetAsync(d_cells.p, 0, std::max<size_t>(1, ns) * 8, s));
-    Buf<uint32_t> d_base_col, d_n_cols, d_cns_col;   // MSA calls only
-    if (msa) {
+    Buf<uint32_t> d_base_col, d_n_cols, d_cns_col;   // MSA and weighted calls only
+    if (cols) {
         MCHK(d_base_col.alloc(nb)); MCHK(d_n_cols.alloc(ns));
         MCHK(hipMemsetAsync(d_n_cols.p, 0, std::max<size_t>(1, ns) * 4, s));
-        if (a.include_consensus) MCHK(d_cns_col.alloc(cns_off[ns]));
+        if (msa ? a.include_consensus != 0 : want_cov) MCHK(d_cns_col.alloc(cns_off[ns]));
     }
+    Buf<uint8_t> d_wts;                              // weighted calls with weights only: a byte per base
+    if (wtd && a.weights) {
+        MCHK(d_wts.alloc(nb));
+        MCHK(hipMemcpyAsync(d_wts.p, a.weights, nb, hipMemcpyHostToDevice, s));
+    }
+    auto fn_of = [&](int k) { return d_wts.p ? inst[k].fn_w : cols ? inst[k].fn_msa : inst[k].fn; };
 
     // H is sized from an estimate of the graph's final size (noisy copies add about a tenth of their length each); a set that outgrows its
     // slot comes back and is rerun with twice the room (or the room for what it had when it stopped, doubled), the worst case at most
@@ -702,7 +776,7 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
             if (first && a.slot_kb_cap) sb = std::max(pmax, std::min<uint64_t>(sb, (uint64_t)a.slot_kb_cap << 10));   // (test switch: forces the overflow and rerun)
             sb = al256(sb);
             int occ = 0;
-            MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, msa ? inst[k].fn_msa : inst[k].fn, inst[k].nt, 0));
+            MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_of(k), inst[k].nt, 0));
             const uint64_t resident = (uint64_t)std::max(1, occ) * (uint64_t)n_cu;
             const uint64_t fit = budget / sb;
             if (fit == 0) { err = who + ": set " + std::to_string(big) + " needs " + std::to_string(sb) + " bytes of workspace, more than the budget of " + std::to_string(budget) + " (option poa_workspace_gb)"; return -1; }
@@ -726,9 +800,9 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
             if (by[k].empty()) continue;
             MArgs q{d_sets.p, d_order.p + base[k], (uint32_t)by[k].size(), d_counter.p + k, d_codes.p, d_soff.p, (uint8_t*)ws.p, slot[k],
                     a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p, a.gap_extend,
-                    d_base_col.p, d_n_cols.p, d_cns_col.p};
+                    d_base_col.p, d_n_cols.p, d_cns_col.p, d_wts.p};
             void* kargs[] = {&q};
-            MCHK(hipLaunchKernel(msa ? inst[k].fn_msa : inst[k].fn, dim3(nslots[k]), dim3((uint32_t)inst[k].nt), kargs, 0, s));
+            MCHK(hipLaunchKernel(fn_of(k), dim3(nslots[k]), dim3((uint32_t)inst[k].nt), kargs, 0, s));
             o.launches++;
             if (a.debug) fprintf(stderr, "[hx] POA modes%s: %zu sets on %u workgroups of %d lanes x %d columns, slots of %.1f MB\n", aff ? " (affine)" : "", by[k].size(), nslots[k], inst[k].nt, inst[k].cpl, slot[k] / 1e6);
         }
@@ -761,6 +835,64 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
         o.cns.append(cns.data() + cns_off[i], len[i]);
         o.cns_off[i + 1] = o.cns.size();
         o.cells += cells[i];
+    }
+    if (want_cov) {
+        // coverage and profile: now that the columns of every set are known, one counter per column (four with the profile: one per
+        // letter) for the whole call, filled from the bases of the sequences of >= 2 bases (k_cov_hist), then read at the columns of the
+        // consensus bases (k_cov_gather). Built here, after the last round: a set that was rerun is counted once.
+        const uint32_t stride = a.want_profile ? 4u : 1u;
+        std::vector<uint32_t> ncols(ns);
+        MCHK(hipMemcpy(ncols.data(), d_n_cols.p, ns * 4, hipMemcpyDeviceToHost));
+        std::vector<CRow> rows, crows;
+        std::vector<uint2> chunks, cchunks;
+        uint64_t hoff = 0, hist_bases = 0;
+        for (uint32_t i = 0; i < ns; i++) {
+            for (uint64_t k = a.set_off[i]; k < a.set_off[i + 1]; k++) {
+                const uint32_t L = (uint32_t)(a.seq_off[k + 1] - a.seq_off[k]);
+                if (L < 2) continue;   // (spoa counts the sequence labels of a node's edges: a sequence of one base has none)
+                for (uint32_t f = 0; f < L; f += 64) chunks.push_back(make_uint2((uint32_t)rows.size(), f));
+                rows.push_back(CRow{a.seq_off[k], 0, hoff, L, ncols[i]});
+                hist_bases += L;
+            }
+            if (len[i]) {
+                for (uint32_t f = 0; f < len[i]; f += 64) cchunks.push_back(make_uint2((uint32_t)crows.size(), f));
+                crows.push_back(CRow{cns_off[i], o.cns_off[i], hoff, len[i], ncols[i]});
+            }
+            hoff += ncols[i];
+        }
+        if (rows.size() >= 0xffffffffULL || crows.size() >= 0xffffffffULL || chunks.size() >= 0xffffffffULL / 64 || cchunks.size() >= 0xffffffffULL / 64) { err = who + ": too many sequences"; return -1; }
+        const uint64_t nc = o.cns.size();
+        o.cov.assign(nc, 0);
+        if (a.want_profile) o.prof.assign(4 * nc, 0);
+        if (nc) {
+            Buf<CRow> d_rows, d_crows; Buf<uint2> d_chunks, d_cchunks; Buf<uint32_t> d_hist, d_cov, d_prof;
+            MCHK(d_rows.alloc(rows.size())); MCHK(d_crows.alloc(crows.size())); MCHK(d_chunks.alloc(chunks.size())); MCHK(d_cchunks.alloc(cchunks.size()));
+            MCHK(d_hist.alloc(hoff * stride)); MCHK(d_cov.alloc(nc));
+            if (a.want_profile) MCHK(d_prof.alloc(4 * nc));
+            MCHK(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * sizeof(CRow), hipMemcpyHostToDevice, s));
+            MCHK(hipMemcpyAsync(d_crows.p, crows.data(), crows.size() * sizeof(CRow), hipMemcpyHostToDevice, s));
+            MCHK(hipMemcpyAsync(d_chunks.p, chunks.data(), chunks.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
+            MCHK(hipMemcpyAsync(d_cchunks.p, cchunks.data(), cchunks.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
+            MCHK(hipEventRecord(e0, s));
+            MCHK(hipMemsetAsync(d_hist.p, 0, std::max<uint64_t>(1, hoff * stride) * 4, s));
+            if (!chunks.empty()) {
+                k_cov_hist<<<(uint32_t)((chunks.size() + 3) / 4), 256, 0, s>>>(d_rows.p, d_chunks.p, (uint32_t)chunks.size(), d_base_col.p, d_codes.p, stride, d_hist.p);
+                MCHK(hipGetLastError());
+                o.launches++;
+            }
+            k_cov_gather<<<(uint32_t)((cchunks.size() + 3) / 4), 256, 0, s>>>(d_crows.p, d_cchunks.p, (uint32_t)cchunks.size(), d_cns_col.p, d_hist.p, stride, d_cov.p, d_prof.p);
+            MCHK(hipGetLastError());
+            MCHK(hipEventRecord(e1, s));
+            MCHK(hipEventSynchronize(e1));
+            float cov_ms = 0;
+            MCHK(hipEventElapsedTime(&cov_ms, e0, e1));
+            o.cov_ms = cov_ms; o.kernel_ms += cov_ms; o.launches++;
+            // what the two kernels and the clearing of the counters must move: a column (and a letter) read per counted base, the
+            // counters written twice and read once where a consensus base stands, a column read and the counts written per consensus base
+            o.cov_moved_bytes = hist_bases * (4 + (stride == 4 ? 1 : 0)) + 2 * hoff * stride * 4 + nc * (4 + 4 * stride + 4 + (a.want_profile ? 16 : 0));
+            MCHK(hipMemcpy(o.cov.data(), d_cov.p, nc * 4, hipMemcpyDeviceToHost));
+            if (a.want_profile) MCHK(hipMemcpy(o.prof.data(), d_prof.p, 4 * nc * 4, hipMemcpyDeviceToHost));
+        }
     }
     if (!msa) return 0;
 

@@ -146,6 +146,34 @@ def cns_to_list(c):
     return [raw[int(off[i]):int(off[i + 1])].decode() for i in range(c.n_edge)]
 
 
+class PoaWeightedParams(C.Structure):
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("type", C.c_int32),
+                ("want_coverage", C.c_int32), ("want_profile", C.c_int32)]
+
+
+class WcnsOut(C.Structure):
+    _fields_ = [("n_set", C.c_uint32), ("cns_off", u64p), ("cns", C.POINTER(C.c_char)), ("coverage", u32p), ("profile", u32p),
+                ("dp_cells", C.c_uint64), ("seq_bases", C.c_uint64), ("n_aligned", C.c_uint64),
+                ("cov_kernel_ms", C.c_double), ("cov_kernel_bytes", C.c_uint64)]
+
+
+def wcns_to_lists(o):
+    """(consensus per set, coverage per set or None, profile per set or None) of a WcnsOut; a profile is a list of [A, C, G, T] counts"""
+    n = o.n_set
+    off = arr(o.cns_off, n + 1, np.uint64)
+    tot = int(off[-1]) if n else 0
+    raw = C.string_at(o.cns, tot) if n else b""
+    cns = [raw[int(off[i]):int(off[i + 1])].decode() for i in range(n)]
+    cov = prof = None
+    if o.coverage:
+        c = arr(o.coverage, tot, np.uint32).tolist() if tot else []
+        cov = [c[int(off[i]):int(off[i + 1])] for i in range(n)]
+    if o.profile:
+        p = arr(o.profile, 4 * tot, np.uint32).reshape(-1, 4).tolist() if tot else []
+        prof = [p[int(off[i]):int(off[i + 1])] for i in range(n)]
+    return cns, cov, prof
+
+
 def msa_to_lists(o):
     """(rows per set, consensus per set) of an MsaOut"""
     n = o.n_set

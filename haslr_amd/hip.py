@@ -15,7 +15,7 @@ _lib = None
 SYMBOLS = ["hx_last_error", "hx_device_count", "hx_ctx_create", "hx_ctx_destroy", "hx_upload", "hx_set_read_shard", "hx_set_prefiltered",
            "hx_chain_reads", "hx_edge_support", "hx_edge_coords", "hx_poa_batch", "hx_free_chain", "hx_free_edges",
            "hx_free_coords", "hx_free_cns", "hx_edge_emit", "hx_edge_records_bytes", "hx_edge_records_export",
-           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
+           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
            "hx_set_option", "hx_get_option", "hx_option_names", "hx_poa_memory_stats", "hx_poa_release_workspace", "hx_poa_prune_stats", "hx_group_set_timeout", "hx_group_inject_fault", "hx_poa_reserve", "hx_poa_host_times", "hx_poa_arena_stats", "hx_group_rccl_ranks",
            "hx_group_create", "hx_group_destroy", "hx_group_size", "hx_group_ctx", "hx_group_transport", "hx_edge_merge", "hx_group_backend_fill", "hx_group_exchange_stats"]
 
@@ -47,6 +47,8 @@ def lib():
         L.hx_poa_sequences_affine.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.POINTER(T.PoaAffineParams), C.POINTER(T.CnsOut)]
         L.hx_poa_msa.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.POINTER(T.PoaMsaParams), C.POINTER(T.MsaOut)]
         L.hx_free_msa.argtypes = [C.c_void_p, C.POINTER(T.MsaOut)]
+        L.hx_poa_weighted.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaWeightedParams), C.POINTER(T.WcnsOut)]
+        L.hx_free_wcns.argtypes = [C.c_void_p, C.POINTER(T.WcnsOut)]
         L.hx_free_chain.argtypes = [C.c_void_p, C.POINTER(T.ChainOut)]
         L.hx_free_edges.argtypes = [C.c_void_p, C.POINTER(T.EdgesOut)]
         L.hx_free_coords.argtypes = [C.c_void_p, C.POINTER(T.CoordsOut)]
@@ -355,6 +357,64 @@ class HipContext:
         st = {"dp_cells": o.dp_cells, "seq_bases": o.seq_bases, "n_aligned": o.n_aligned, "rows_kernel_ms": o.rows_kernel_ms, "rows_kernel_bytes": o.rows_kernel_bytes}
         lib().hx_free_msa(self._h, C.byref(o))
         return (rows, cns, st) if stats else rows
+
+    def poa_weighted(self, sets, weights=None, qualities=None, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=None, coverage=False, profile=False,
+                     stats=False):
+        """the consensus of every set under per-base weights (spoa's add_alignment with weights or a quality string), and the coverage of
+        every consensus base (spoa's generate_consensus(dst)). weights: nested like sets, one integer in 1..255 per base (a list or an integer array per sequence); qualities: nested
+        like sets, one string per sequence, weight = character - 33 (spoa's rule); neither: every weight is 1. A sequence adds w[i-1] + w[i]
+        to every graph edge between its bases i-1 and i. A weight of 0 (the quality '!') or one outside 1..255 is an error: callers with
+        real FASTQ clamp their qualities to '"' (weight 1) or more themselves. A length that does not match its sequence is a ValueError.
+        gap_extend None (or equal to gap_open) is the linear gap model. coverage=True: per set a list with, for every consensus base, the
+        number of sequences of two or more bases that have a base in its column (a sequence of one base counts nowhere, as in spoa: the
+        coverage can be 0); profile=True: per set a list of [A, C, G, T] counts of those sequences by their letter in the column. Returns
+        the list of consensus strings when nothing else is asked for, else a tuple (consensus, coverage if asked, profile if asked,
+        counters if stats): dp_cells, seq_bases, n_aligned as poa_sequences_affine has them, and cov_kernel_ms / cov_kernel_bytes of the
+        coverage kernels."""
+        import numpy as np
+        if type not in T.POA_TYPES:
+            raise ValueError(f"unknown alignment type {type!r} (sw, nw, ov)")
+        if weights is not None and qualities is not None:
+            raise ValueError("give weights or qualities, not both")
+        given = weights if weights is not None else qualities
+        wbytes = None
+        if given is not None:
+            if len(given) != len(sets):
+                raise ValueError(f"{len(given)} sets of weights for {len(sets)} sets of sequences")
+            flat = bytearray()
+            for i, (st, ws) in enumerate(zip(sets, given)):
+                if len(ws) != len(st):
+                    raise ValueError(f"set {i}: {len(ws)} lists of weights for {len(st)} sequences")
+                for k, (q, w) in enumerate(zip(st, ws)):
+                    if len(w) != len(q):
+                        raise ValueError(f"set {i}, sequence {k}: {len(w)} weights for {len(q)} bases")
+                    if qualities is not None:
+                        vals = np.array([ord(ch) for ch in w], dtype=np.int64) - 33
+                        bad = np.nonzero((vals < 1) | (vals > 93))[0]
+                    else:
+                        vals = np.asarray(w, dtype=np.int64)
+                        bad = np.nonzero((vals < 1) | (vals > 255))[0]
+                    if bad.size:
+                        p = int(bad[0])
+                        what = f"the quality character {w[p]!r} gives" if qualities is not None else "a weight of"
+                        raise ValueError(f"set {i}, sequence {k}, position {p}: {what} {int(vals[p])}, which is not accepted (weights are 1..255, qualities '\"'..'~')")
+                    flat += vals.astype(np.uint8).tobytes()
+            wbytes = bytes(flat) or b"\0"
+        set_off = np.zeros(len(sets) + 1, dtype=np.uint64)
+        seqs = [q for st in sets for q in st]
+        for i, st in enumerate(sets):
+            set_off[i + 1] = set_off[i] + len(st)
+        seq_off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        for i, q in enumerate(seqs):
+            seq_off[i + 1] = seq_off[i] + len(q)
+        o = T.WcnsOut()
+        wp = T.PoaWeightedParams(match, mismatch, gap_open, gap_open if gap_extend is None else gap_extend, T.POA_TYPES[type], int(bool(coverage)), int(bool(profile)))
+        self._chk(lib().hx_poa_weighted(self._h, len(sets), set_off.ctypes.data_as(T.u64p), seq_off.ctypes.data_as(T.u64p), "".join(seqs).encode(), wbytes, C.byref(wp), C.byref(o)))
+        cns, cov, prof = T.wcns_to_lists(o)
+        st = {"dp_cells": o.dp_cells, "seq_bases": o.seq_bases, "n_aligned": o.n_aligned, "cov_kernel_ms": o.cov_kernel_ms, "cov_kernel_bytes": o.cov_kernel_bytes}
+        lib().hx_free_wcns(self._h, C.byref(o))
+        res = [cns] + ([cov] if coverage else []) + ([prof] if profile else []) + ([st] if stats else [])
+        return cns if len(res) == 1 else tuple(res)
 
     def poa_phase_cycles(self):
         a, b = (C.c_uint64 * 6)(), (C.c_uint64 * 6)()

@@ -58,8 +58,9 @@ void hx_ctx_destroy(hx_ctx*);
  *                    poa_own_bucket_first, poa_resident_first, poa_far_shift) and test switches that force rare paths (poa_poll_limit, poa_max_indeg, poa_node_est_pct,
  *                    poa_far_rows, poa_ring_zero, poa_slots, poa_slots_pct, poa_batches, poa_force_cm, coords_lds_supp), and two of the
  *                    general POA path (hx_poa_sequences_mode): poa_general (1: HX_POA_NW runs the general path too) and poa_modes_slot_kb (cap of
- *                    its first round of workspace slots, forcing the rerun of sets in larger ones), and poa_affine (1: hx_poa_sequences_affine
- *                    with gap_extend == gap_open runs the affine kernel instead of the linear paths).
+ *                    its first round of workspace slots, forcing the rerun of sets in larger ones), poa_affine (1: hx_poa_sequences_affine
+ *                    with gap_extend == gap_open runs the affine kernel instead of the linear paths), and poa_weighted (1: hx_poa_weighted
+ *                    without weights runs the weighted kernels on weights of 1 instead of the unit-weight ones).
  *                    Results never depend on any of them. */
 int hx_set_option(hx_ctx*, const char* name, const char* value);
 int hx_get_option(const hx_ctx*, const char* name, double* value);
@@ -111,11 +112,28 @@ int hx_poa_sequences_affine(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, c
  *                     poa_workspace_gb act as on the other entries. Like the rest of the general path it is NOT pinned against spoa itself
  *                     (the library is not available to the tests): the tests hold it to a CPU restatement of spoa's rule. */
 int hx_poa_msa(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_msa_params*, hx_msa_out* out);
+/*   hx_poa_weighted   the consensus under per-base weights, and the coverage of every consensus base (spoa's add_alignment with a weight, a
+ *                     quality string or a vector of weights, and generate_consensus(dst); DESIGN.md "General POA path", "Base weights and
+ *                     coverage"). weights has one byte per base, parallel to bases, or is NULL (every weight 1). A sequence adds
+ *                     w[i-1] + w[i] to every graph edge it walks between its bases i-1 and i, so with weights of 1 every edge gains the 2 of
+ *                     the other entries. Weights change nothing but the edge weights the heaviest bundle reads: the alignments, the nodes and
+ *                     the columns of the set are those of unit weights. A weight is 1..255: (i) the score of a consensus path is at most the
+ *                     sum of all edge weights, at most 2 x 255 x (2^21 - 2) = 1 069 546 500, so the int32 scores of the consensus code stay
+ *                     exact for every set the path accepts; (ii) a weight of 0 is refused, not reinterpreted: a zero-weight edge out of a
+ *                     source node gives a real node the score -1 that marks "not visited", branch completion then takes it for dead, and with
+ *                     all weights 0 spoa's own loop does not end. The error names set, sequence and position. Coverage and profile:
+ *                     haslr_types.h; a sequence of one base counts nowhere, as in spoa (it has no edge to carry its label). Scores, types,
+ *                     errors and length limits are hx_poa_sequences_affine's; every type, HX_POA_NW too, runs the general path. Options
+ *                     poa_modes_slot_kb and poa_workspace_gb act as on the other entries; option poa_weighted (1) sends a call without
+ *                     weights through the weighted instances on weights of 1 (same results). Not pinned against spoa, like the rest of the
+ *                     general path: the tests hold it to a CPU restatement of spoa's rule. */
+int hx_poa_weighted(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_weighted_params*, hx_wcns_out* out);
 void hx_free_chain(hx_ctx*, hx_chain_out*);
 void hx_free_edges(hx_ctx*, hx_edges_out*);
 void hx_free_coords(hx_ctx*, hx_coords_out*);
 void hx_free_cns(hx_ctx*, hx_cns_out*);
 void hx_free_msa(hx_ctx*, hx_msa_out*);
+void hx_free_wcns(hx_ctx*, hx_wcns_out*);
 
 /* multi-GPU exchange of the edge-support multiset (one all-gather between hx_chain_reads and the sort):
  *   hx_edge_emit            emit this shard's records (unsorted) on the device, returns their number

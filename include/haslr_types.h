@@ -170,6 +170,32 @@ typedef struct {
     uint64_t rows_kernel_bytes;
 } hx_msa_out;
 
+/* hx_poa_weighted: hx_poa_sequences_affine's scores and type (gap_extend == gap_open is the linear model), and what is wanted beside
+ * the consensus. */
+typedef struct {
+    int32_t match, mismatch, gap_open, gap_extend;
+    int32_t type;          /* hx_poa_type */
+    int32_t want_coverage; /* 0 / 1: the coverage of every consensus base */
+    int32_t want_profile;  /* 0 / 1: and the four letter counts of its column (the coverage is filled in as well) */
+} hx_poa_weighted_params;
+
+/* Consensus of every set under per-base weights, with the coverage of every consensus base (spoa's generate_consensus(dst)): the
+ * number of sequences of two or more bases that have a base in the consensus base's column of the alignment. coverage has one entry per
+ * consensus base, at the base's offset in cns; profile has four (A, C, G, T: the sequences counted in the coverage by their letter in
+ * that column; the rest of the set's sequences have a gap there). Both are NULL unless asked for. The consensus strings and the work
+ * counters are hx_cns_out's. */
+typedef struct {
+    uint32_t n_set;
+    uint64_t* cns_off;  /* n_set+1 */
+    char* cns;
+    uint32_t* coverage; /* cns_off[n_set], or NULL */
+    uint32_t* profile;  /* 4 * cns_off[n_set], or NULL */
+    uint64_t dp_cells, seq_bases, n_aligned;
+    /* the kernels that count and gather the coverage, on their own: their time by device events and the bytes they have to move */
+    double cov_kernel_ms;
+    uint64_t cov_kernel_bytes;
+} hx_wcns_out;
+
 #ifdef __cplusplus
 }
 #endif

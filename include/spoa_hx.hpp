@@ -16,11 +16,12 @@
 // the work happens in generate_consensus(): align_sequence_with_graph() returns a token (an Alignment holding one
 // (-1, ticket) pair, not a list of node/position pairs), add_alignment() appends the sequence that goes with a token,
 // generate_consensus() sends the recorded sequences, in order, through hx_poa_sequences_mode (the engine's alignment type and
-// three scores, linear gap, unit weights; an engine made with five scores, gap open below gap extend, goes through
-// hx_poa_sequences_affine) and returns what spoa's generate_consensus returns for them.
+// three scores, linear gap; an engine made with five scores, gap open below gap extend, goes through
+// hx_poa_sequences_affine) and returns what spoa's generate_consensus returns for them. A graph that was given weights or qualities, or
+// is asked for the coverage, goes through hx_poa_weighted instead (below).
 // All three of spoa's alignment types are taken: kNW (global, what the reference uses) runs the tuned global path, kSW (local) and
 // kOV (overlap) the general path of the library (DESIGN.md "General POA path"). What is supported beyond that is the reference's call
-// pattern: weight 1 only, every alignment added to the graph it was computed against, in the order it was computed. spoa 1.1.3 exits on invalid input; this header throws std::runtime_error with the
+// pattern: every alignment added to the graph it was computed against, in the order it was computed. spoa 1.1.3 exits on invalid input; this header throws std::runtime_error with the
 // library's message instead (there is no CPU fallback: without a HIP device every consensus fails loudly).
 //
 // Threads: the reference calls from gopt.num_threads pthreads, each with its own engine and graph (asm_cal_cns_seq_MT, Assemble.cpp:562-605).
@@ -39,6 +40,15 @@
 // empty member of a set). An MSA call is NOT flat-combined with other threads' calls: it takes the device's mutex like consensus_batch and
 // is one device call of its own; spoa::hx::msa_batch() takes many sets in one call. Like kSW, kOV and the affine engines, the MSA is held to
 // a CPU restatement of spoa's rule by the tests, not to spoa itself, which is not available to them.
+//
+// Base weights and coverage: add_alignment has spoa 1.1.3's three overloads - one weight for every base of the sequence (default 1), a
+// quality string (weight = character - 33) and a vector of weights, one per base - and generate_consensus(dst) fills dst with the coverage
+// of every consensus base. A weight is 1..255 (include/haslr_hip.h, hx_poa_weighted, says why 0 is refused and not reinterpreted); a size
+// that does not match the sequence, a weight of 0 or above 255, and a quality character outside '"'..'~' throw std::invalid_argument.
+// Callers with real FASTQ clamp their qualities to '"' or more themselves. A graph that has only seen weight 1 and is asked for the plain
+// consensus keeps the route above (flat combining, the tuned kNW path); a graph with any other weight, or a call of
+// generate_consensus(dst), is one device call of its own through hx_poa_weighted, as the MSA call is. spoa::hx::weighted_batch() takes
+// many sets in one call. Held to a CPU restatement of spoa's rule by the tests, like the MSA.
 //
 // This is product code. It is never used to build oracle/_ref (a reference build must not be made with stand-in
 // headers): tests/test_spoa_header.py compiles a small caller written against the five symbols, nothing else.
@@ -218,6 +228,61 @@ inline std::vector<std::vector<std::string>> msa_batch(const std::vector<std::ve
     return msa_batch(p, type, m, n, g, e, include_consensus);
 }
 
+// the consensus of every set under per-base weights in ONE device call (hx_poa_weighted), with the coverage of every consensus base and
+// the four letter counts (A, C, G, T) of its column when asked for. weights: one vector per set with one vector per sequence with one
+// weight (1..255) per base, or empty: every weight is 1. e == g is the linear gap model.
+struct Weighted {
+    std::vector<std::string> consensus;
+    std::vector<std::vector<std::uint32_t>> coverage;   // per set, one per consensus base (empty unless asked for)
+    std::vector<std::vector<std::uint32_t>> profile;    // per set, four per consensus base (empty unless asked for)
+};
+inline Weighted weighted_batch(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights,
+                               AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, bool coverage = true, bool profile = false) {
+    if (!weights.empty() && weights.size() != sets.size()) throw std::invalid_argument("spoa_hx: weighted_batch needs one set of weights per set of sequences, or none");
+    std::vector<std::uint64_t> set_off{0}, seq_off{0};
+    std::string bases;
+    std::vector<std::uint8_t> w;
+    for (std::size_t i = 0; i < sets.size(); i++) {
+        const auto& st = *sets[i];
+        if (!weights.empty() && weights[i]->size() != st.size()) throw std::invalid_argument("spoa_hx: weighted_batch: a set has another number of weight vectors than of sequences");
+        for (std::size_t k = 0; k < st.size(); k++) {
+            bases += st[k]; seq_off.push_back(bases.size());
+            if (weights.empty()) continue;
+            const auto& wk = (*weights[i])[k];
+            if (wk.size() != st[k].size()) throw std::invalid_argument("spoa_hx: weighted_batch: a sequence has another number of weights than of bases");
+            w.insert(w.end(), wk.begin(), wk.end());
+        }
+        set_off.push_back(seq_off.size() - 1);
+    }
+    if (!weights.empty() && w.empty()) w.push_back(1);   // (no base at all: a pointer that is not null, nothing behind it is read)
+    const hx_poa_weighted_params wp{m, n, g, e, static_cast<std::int32_t>(type), coverage ? 1 : 0, profile ? 1 : 0};
+    hx_wcns_out out;
+    Device& d = device();
+    std::lock_guard<std::mutex> lock(d.mu);
+    hx_ctx* ctx = context_locked(d);
+    if (hx_poa_weighted(ctx, (std::uint32_t)sets.size(), set_off.data(), seq_off.data(), bases.c_str(), weights.empty() ? nullptr : w.data(), &wp, &out) != 0)
+        throw std::runtime_error(std::string("spoa_hx: ") + hx_last_error());
+    Weighted res;
+    res.consensus.resize(sets.size());
+    if (coverage) res.coverage.resize(sets.size());
+    if (profile) res.profile.resize(sets.size());
+    for (std::size_t i = 0; i < sets.size(); i++) {
+        res.consensus[i].assign(out.cns + out.cns_off[i], out.cns + out.cns_off[i + 1]);
+        if (coverage) res.coverage[i].assign(out.coverage + out.cns_off[i], out.coverage + out.cns_off[i + 1]);
+        if (profile) res.profile[i].assign(out.profile + 4 * out.cns_off[i], out.profile + 4 * out.cns_off[i + 1]);
+    }
+    hx_free_wcns(ctx, &out);
+    return res;
+}
+inline Weighted weighted_batch(const std::vector<std::vector<std::string>>& sets, const std::vector<std::vector<std::vector<std::uint8_t>>>& weights, AlignmentType type,
+                               std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, bool coverage = true, bool profile = false) {
+    std::vector<const std::vector<std::string>*> p;
+    std::vector<const std::vector<std::vector<std::uint8_t>>*> q;
+    for (const auto& st : sets) p.push_back(&st);
+    for (const auto& ws : weights) q.push_back(&ws);
+    return weighted_batch(p, q, type, m, n, g, e, coverage, profile);
+}
+
 // one set on behalf of one caller thread, combined with whatever other threads have queued (see "Threads" above)
 inline std::string consensus_combined(const std::vector<std::string>& seqs, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) {
     Device& d = device();
@@ -309,18 +374,47 @@ inline std::string consensus_combined(const std::vector<std::string>& seqs, Alig
 
 class Graph {
 public:
-    // spoa::Graph::add_alignment(alignment, sequence, weight = 1)
+    // spoa::Graph::add_alignment(alignment, sequence, weight = 1): the same weight for every base
     void add_alignment(const Alignment& alignment, const std::string& sequence, std::uint32_t weight = 1) {
-        if (weight != 1) throw std::invalid_argument("spoa_hx: only unit weights are supported (the reference uses the default)");
-        if (alignment.size() != 1 || alignment[0].first != -1 || (std::uint32_t)alignment[0].second != ticket_)
-            throw std::invalid_argument("spoa_hx: add_alignment needs the alignment that align_sequence_with_graph last returned for this graph");
-        ticket_++;
-        if (!sequence.empty()) sequences_.push_back(sequence);   // spoa ignores an empty sequence (the reference never passes one, Assemble.cpp:537)
+        if (weight < 1 || weight > 255) throw std::invalid_argument("spoa_hx: a weight must be 1..255, not " + std::to_string(weight));
+        record(alignment, sequence, std::vector<std::uint8_t>(sequence.size(), (std::uint8_t)weight));
+    }
+    // spoa::Graph::add_alignment(alignment, sequence, quality): weight = quality character - 33
+    void add_alignment(const Alignment& alignment, const std::string& sequence, const std::string& quality) {
+        if (quality.size() != sequence.size()) throw std::invalid_argument("spoa_hx: the quality string has " + std::to_string(quality.size()) + " characters, the sequence " + std::to_string(sequence.size()) + " bases");
+        std::vector<std::uint8_t> w(quality.size());
+        for (std::size_t i = 0; i < quality.size(); i++) {
+            const int v = (int)(unsigned char)quality[i] - 33;
+            if (v < 1 || v > 93) throw std::invalid_argument("spoa_hx: the quality character at position " + std::to_string(i) + " gives the weight " + std::to_string(v) + " (accepted: '\"'..'~', weights 1..93)");
+            w[i] = (std::uint8_t)v;
+        }
+        record(alignment, sequence, w);
+    }
+    // spoa::Graph::add_alignment(alignment, sequence, weights): one weight per base
+    void add_alignment(const Alignment& alignment, const std::string& sequence, const std::vector<std::uint32_t>& weights) {
+        if (weights.size() != sequence.size()) throw std::invalid_argument("spoa_hx: " + std::to_string(weights.size()) + " weights for a sequence of " + std::to_string(sequence.size()) + " bases");
+        std::vector<std::uint8_t> w(weights.size());
+        for (std::size_t i = 0; i < weights.size(); i++) {
+            if (weights[i] < 1 || weights[i] > 255) throw std::invalid_argument("spoa_hx: the weight at position " + std::to_string(i) + " is " + std::to_string(weights[i]) + " (accepted: 1..255)");
+            w[i] = (std::uint8_t)weights[i];
+        }
+        record(alignment, sequence, w);
     }
     // spoa::Graph::generate_consensus()
     std::string generate_consensus() {
         if (sequences_.empty()) return std::string();
-        return hx::consensus_combined(sequences_, type_, m_, n_, g_, e_);
+        if (!weighted_) return hx::consensus_combined(sequences_, type_, m_, n_, g_, e_);
+        return hx::weighted_batch(std::vector<const std::vector<std::string>*>{&sequences_}, std::vector<const std::vector<std::vector<std::uint8_t>>*>{&weights_}, type_, m_, n_, g_, e_, false, false).consensus[0];
+    }
+    // spoa::Graph::generate_consensus(dst): dst is replaced by the coverage of every consensus base. A device call of its own.
+    std::string generate_consensus(std::vector<std::uint32_t>& dst) {
+        dst.clear();
+        if (sequences_.empty()) return std::string();
+        hx::Weighted r = hx::weighted_batch(std::vector<const std::vector<std::string>*>{&sequences_},
+                                            weighted_ ? std::vector<const std::vector<std::vector<std::uint8_t>>*>{&weights_} : std::vector<const std::vector<std::vector<std::uint8_t>>*>{},
+                                            type_, m_, n_, g_, e_, true, false);
+        dst.swap(r.coverage[0]);
+        return r.consensus[0];
     }
     // spoa::Graph::generate_multiple_sequence_alignment(dst, include_consensus = false): dst is replaced by one row per added sequence
     // (and the consensus row). A device call of its own, not combined with other threads' calls.
@@ -332,7 +426,18 @@ public:
 
 private:
     friend class AlignmentEngine;
+    void record(const Alignment& alignment, const std::string& sequence, const std::vector<std::uint8_t>& w) {
+        if (alignment.size() != 1 || alignment[0].first != -1 || (std::uint32_t)alignment[0].second != ticket_)
+            throw std::invalid_argument("spoa_hx: add_alignment needs the alignment that align_sequence_with_graph last returned for this graph");
+        ticket_++;
+        if (sequence.empty()) return;   // spoa ignores an empty sequence (the reference never passes one, Assemble.cpp:537)
+        sequences_.push_back(sequence);
+        weights_.push_back(w);
+        for (std::uint8_t v : w) if (v != 1) weighted_ = true;
+    }
     std::vector<std::string> sequences_;
+    std::vector<std::vector<std::uint8_t>> weights_;   // parallel to sequences_
+    bool weighted_ = false;                            // some base has another weight than 1
     std::uint32_t ticket_ = 0;
     AlignmentType type_ = AlignmentType::kNW;
     std::int8_t m_ = 5, n_ = -4, g_ = -8, e_ = -8;

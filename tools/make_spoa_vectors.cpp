@@ -9,19 +9,27 @@
 // general POA path (hx_poa_sequences_mode, DESIGN.md "General POA path"): they go to tests/golden/spoa_modes/<type>_<name>.json.
 // With a gap_extend the engine is spoa's five-score one (gap = gap open; affine gaps, hx_poa_sequences_affine): those vectors go to
 // tests/golden/spoa_affine/<type>_<name>.json and carry "gap_extend".
+// A sequence line may carry weights after a blank: "ACGT q IIII" (a quality string: add_alignment(alignment, sequence, quality)) or
+// "ACGT v 3,1,40,2" (a vector of weights: add_alignment(alignment, sequence, weights)). Vectors of a run in which some line does pin base
+// weights and coverage (hx_poa_weighted, DESIGN.md "Base weights and coverage"): they go to tests/golden/spoa_weighted/<type>_<name>.json
+// and carry per case the "weights" of every sequence (numbers, 1 where the line had none) and the "coverage" of every consensus base
+// (generate_consensus(dst)). The directory is the slot for them; nothing is committed into it yet.
 //
 // Input: one case per paragraph - ">name", then one ACGT sequence per line (alignment order), a blank line between cases.
 // The five calls are exactly the reference's (Assemble.cpp:499,500,539,540,554): kNW unless a type is given, linear gap, sequences added
-// in order, unit weights.
+// in order, unit weights unless a line gives others.
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
+#include <sstream>
 #include <string>
 #include <vector>
 
 #include "spoa/spoa.hpp"
 
-static std::string consensus_of(const std::vector<std::string>& seqs, int type, int m, int n, int g, bool affine, int e) {
+struct Weights { char how = 0; std::string quality; std::vector<uint32_t> values; };   // how: 0 (none), 'q' or 'v'
+
+static std::string consensus_of(const std::vector<std::string>& seqs, const std::vector<Weights>& wts, int type, int m, int n, int g, bool affine, int e, std::vector<uint32_t>* coverage) {
     auto engine = affine ? spoa::createAlignmentEngine(static_cast<spoa::AlignmentType>(type), (int8_t)m, (int8_t)n, (int8_t)g, (int8_t)e)
                          : spoa::createAlignmentEngine(static_cast<spoa::AlignmentType>(type), (int8_t)m, (int8_t)n, (int8_t)g);
     auto graph = spoa::createGraph();
@@ -29,10 +37,14 @@ static std::string consensus_of(const std::vector<std::string>& seqs, int type, 
     for (const std::string& s : seqs) {
         if (s.empty()) continue;   // Assemble.cpp:537 skips empty sub-sequences
         auto alignment = engine->align_sequence_with_graph(s, graph);
-        graph->add_alignment(alignment, s);
+        const Weights& w = wts[(size_t)(&s - &seqs[0])];
+        if (w.how == 'q') graph->add_alignment(alignment, s, w.quality);
+        else if (w.how == 'v') graph->add_alignment(alignment, s, w.values);
+        else graph->add_alignment(alignment, s);
         used++;
     }
-    return used ? graph->generate_consensus() : std::string();   // Assemble.cpp:544-551
+    if (!used) return std::string();   // Assemble.cpp:544-551
+    return coverage ? graph->generate_consensus(*coverage) : graph->generate_consensus();
 }
 
 int main(int argc, char** argv) {
@@ -44,12 +56,23 @@ int main(int argc, char** argv) {
     const int e = affine ? atoi(argv[5]) : g;
     const char* algo[3] = {"kSW", "kNW", "kOV"};
     std::vector<std::pair<std::string, std::vector<std::string>>> cases;
+    std::vector<std::vector<Weights>> weights;   // parallel to cases
+    bool weighted = false;
     std::string line;
     while (std::getline(std::cin, line)) {
         if (!line.empty() && line.back() == '\r') line.pop_back();
         if (line.empty()) continue;
-        if (line[0] == '>') cases.push_back({line.substr(1), {}});
-        else if (!cases.empty()) cases.back().second.push_back(line == "-" ? std::string() : line);   // "-" = an empty sequence
+        if (line[0] == '>') { cases.push_back({line.substr(1), {}}); weights.emplace_back(); }
+        else if (!cases.empty()) {
+            std::istringstream in(line);
+            std::string seq, how, arg;
+            in >> seq >> how >> arg;
+            Weights w;
+            if (how == "q") { w.how = 'q'; w.quality = arg; weighted = true; }
+            else if (how == "v") { w.how = 'v'; std::istringstream v(arg); std::string tok; while (std::getline(v, tok, ',')) w.values.push_back((uint32_t)atoi(tok.c_str())); weighted = true; }
+            cases.back().second.push_back(seq == "-" ? std::string() : seq);   // "-" = an empty sequence
+            weights.back().push_back(w);
+        }
     }
     printf("{\"spoa_version\": \"1.1.3\", \"match\": %d, \"mismatch\": %d, \"gap\": %d, ", m, n, g);
     if (affine) printf("\"gap_extend\": %d, ", e);
@@ -57,7 +80,25 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < cases.size(); i++) {
         printf("%s\n  {\"name\": \"%s\", \"sequences\": [", i ? "," : "", cases[i].first.c_str());
         for (size_t k = 0; k < cases[i].second.size(); k++) printf("%s\"%s\"", k ? ", " : "", cases[i].second[k].c_str());
-        printf("], \"consensus\": \"%s\"}", consensus_of(cases[i].second, type, m, n, g, affine, e).c_str());
+        if (weighted) {
+            printf("], \"weights\": [");
+            for (size_t k = 0; k < cases[i].second.size(); k++) {
+                const Weights& w = weights[i][k];
+                printf("%s[", k ? ", " : "");
+                for (size_t q = 0; q < cases[i].second[k].size(); q++)
+                    printf("%s%u", q ? ", " : "", w.how == 'q' ? (unsigned)(w.quality[q] - 33) : w.how == 'v' ? (unsigned)w.values[q] : 1u);
+                printf("]");
+            }
+        }
+        std::vector<uint32_t> coverage;
+        const std::string cns = consensus_of(cases[i].second, weights[i], type, m, n, g, affine, e, weighted ? &coverage : nullptr);
+        printf("], \"consensus\": \"%s\"", cns.c_str());
+        if (weighted) {
+            printf(", \"coverage\": [");
+            for (size_t q = 0; q < coverage.size(); q++) printf("%s%u", q ? ", " : "", (unsigned)coverage[q]);
+            printf("]");
+        }
+        printf("}");
     }
     printf("\n ]}\n");
     return 0;

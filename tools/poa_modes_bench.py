@@ -11,7 +11,10 @@ a sample of the sets (GCUPS of the sample). Every row also runs the affine kerne
 affine restatement (tests/poa_affine_ref.cpp). And every row asks for the multiple sequence alignment of the same sets (hx_poa_msa, linear
 scores, with the consensus row): kernel time against the consensus-only general path ("over_general": ratio of the medians, and the
 smallest and largest ratio the repeats allow), the kernel that writes the row text on its own (time by device events, the bytes it has to
-move = text + 4 per base read, GB/s), and the sample compared with the MSA restatement (tests/poa_msa_ref.cpp). Prints one JSON line."""
+move = text + 4 per base read, GB/s), and the sample compared with the MSA restatement (tests/poa_msa_ref.cpp). And every row runs the
+weighted entry on the same sets (hx_poa_weighted, linear scores, seeded quality-like weights in 1..60, with coverage and profile): kernel
+time against the consensus-only general path ("over_general", as for the MSA), the coverage kernels on their own (time by device events,
+the bytes they have to move, GB/s), and the sample compared with the weighted restatement (tests/poa_weighted_ref.cpp). Prints one JSON line."""
 import argparse
 import json
 import os
@@ -95,6 +98,7 @@ def main():
     import msalib
     import parlib
     import pmrlib
+    import wgtlib
     rng = np.random.default_rng(a.seed)
     loads = {"a_sw": ("sw", workload_a(rng, a.sets_a, True)), "a_nw": ("nw", workload_a(rng, a.sets_a, False))}
     loads["a_ov"] = ("ov", loads["a_nw"][1])
@@ -105,6 +109,8 @@ def main():
         ref = pmrlib.ModesRef(d)
         aref = parlib.AffineRef(d)
         mref = msalib.MsaRef(d)
+        wref = wgtlib.WeightedRef(d)
+        wrng = np.random.default_rng(a.seed + 1000)   # (a generator of its own: the workloads are those of the earlier lines)
         for name, (mode, sets) in loads.items():
             r = {"mode": mode, "sets": len(sets)}
             for path, opts in (("general", {"poa_general": 1}), ("tuned_nw", {})):
@@ -151,6 +157,28 @@ def main():
             with ThreadPoolExecutor(16) as ex:
                 out = list(ex.map(lambda st: mref.rows(st, mode, include_consensus=True), sample))
             r["msa_sample_equal"] = ctx.poa_msa(sample, mode, include_consensus=True) == out
+            wts = [[wrng.integers(1, 61, len(q), dtype=np.uint8) for q in st] for st in sets]
+            cov_ms, moved = [], 0
+
+            def weighted_call():
+                nonlocal moved
+                st = ctx.poa_weighted(sets, wts, type=mode, coverage=True, profile=True, stats=True)[3]
+                cov_ms.append(st["cov_kernel_ms"])
+                moved = st["cov_kernel_bytes"]
+            ms = gpu_time(ctx, weighted_call, a.repeats)
+            med = float(np.median(ms))
+            cmed = float(np.median(cov_ms[1:]))
+            r["weighted"] = {"kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
+                             "over_general": round(med / gen["kernel_ms_median"], 4), "over_general_min": round(min(ms) / gen["kernel_ms_max"], 4),
+                             "over_general_max": round(max(ms) / gen["kernel_ms_min"], 4),
+                             "coverage_kernels": {"ms_median": round(cmed, 4), "ms_min": round(min(cov_ms[1:]), 4), "ms_max": round(max(cov_ms[1:]), 4),
+                                                  "bytes": int(moved), "gb_per_s": round(moved / cmed / 1e6, 1)}}
+            swts = [[w.tolist() for w in ws] for ws in wts[:a.cpu_sample]]
+            with ThreadPoolExecutor(16) as ex:
+                out = list(ex.map(lambda k: wref.weighted(sample[k], swts[k], mode), range(len(sample))))
+            got = ctx.poa_weighted(sample, swts, type=mode, coverage=True, profile=True)
+            r["weighted_sample_equal"] = list(zip(*got)) == [(w.consensus, w.coverage, w.profile) for w in out]
+            r["weighted_sample_changed"] = sum(c != u for c, u in zip(got[0], ctx.poa_weighted(sample, type=mode)))
             res[name] = r
     ctx.close()
     print(json.dumps(res))
