@@ -428,21 +428,42 @@ extern "C" int hx_poa_sequences(hx_ctx* c, uint32_t n_sets, const uint64_t* set_
     return rc;
 }
 
-// the general path (kernels/poa_modes.hip) for one call: linear instances, or the affine ones with gap = gap open
-static int poa_general_call(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, int32_t match, int32_t mismatch, int32_t gap,
-                            int32_t gap_extend, int affine, int32_t type, hx_cns_out* out) {
+// ---- the general path (kernels/poa_modes.hip). Its entry points differ in what they validate and in the outputs they hand over; the call itself is one.
+// The request of an entry point `who` (the name its errors carry), as far as every entry has it; the entry adds its own flags.
+static hxk::PoaModesArgs general_args(const char* who, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, int32_t match, int32_t mismatch,
+                                      int32_t gap_open, int32_t gap_extend, int32_t type, int affine) {
+    hxk::PoaModesArgs a;
+    a.who = who; a.n_sets = n_sets; a.set_off = set_off; a.seq_off = seq_off; a.bases = bases;
+    a.match = match; a.mismatch = mismatch; a.gap = gap_open; a.gap_extend = gap_extend; a.type = type; a.affine = affine;
+    return a;
+}
+
+// runs a validated request with the context's options, books its time and prints the debug line (tag: what that line calls the entry)
+static int poa_general_run(hx_ctx* c, const char* tag, hxk::PoaModesArgs& a, hxk::PoaModesOut& o) {
     HIPCHK(hipSetDevice(c->device));
-    hxk::PoaModesArgs a{n_sets, set_off, seq_off, bases, match, mismatch, gap, type, (uint32_t)std::max(0, c->opt.poa_modes_slot_kb), c->opt.poa_workspace_gb, c->opt.debug};
-    a.gap_extend = gap_extend; a.affine = affine;
-    hxk::PoaModesOut o;
+    a.slot_kb_cap = (uint32_t)std::max(0, c->opt.poa_modes_slot_kb); a.workspace_gb = c->opt.poa_workspace_gb; a.debug = c->opt.debug;
     std::string err;
     if (hxk::poa_modes_run(c->stream, c->poa_modes_ws, a, o, err)) return fail(err);
     c->tm.ms[3] += o.kernel_ms; c->tm.launches[3] += o.launches;
-    out->n_edge = n_sets;
-    out->cns_off = (uint64_t*)malloc(((size_t)n_sets + 1) * 8); memcpy(out->cns_off, o.cns_off.data(), ((size_t)n_sets + 1) * 8);
-    out->cns = (char*)malloc(std::max<size_t>(1, o.cns.size())); memcpy(out->cns, o.cns.data(), o.cns.size());
+    if (c->opt.debug) {
+        char rows[48] = "", part[48] = "";   // what an MSA or a weighted call adds to the line
+        if (a.msa) { snprintf(rows, sizeof rows, "%zu bytes of rows, ", o.msa.size()); snprintf(part, sizeof part, " (rows %.3f ms)", o.msa_rows_ms); }
+        if (a.weighted) snprintf(part, sizeof part, " (coverage %.3f ms)", o.cov_ms);
+        fprintf(stderr, "[hx] POA %s call%s: %u sets, %.3g cells, %skernels %.2f ms%s, %u sets rerun in a larger slot\n", tag, a.affine ? " (affine)" : "", a.n_sets, (double)o.cells, rows, o.kernel_ms, part, o.retried);
+    }
+    return 0;
+}
+
+// a malloc'ed copy for an output struct (freed by hx_free_*)
+template <class T> static T* dup(const T* p, size_t n) { void* q = malloc(std::max<size_t>(1, n * sizeof(T))); memcpy(q, p, n * sizeof(T)); return (T*)q; }
+
+static int poa_general_call(hx_ctx* c, hxk::PoaModesArgs a, hx_cns_out* out) {
+    hxk::PoaModesOut o;
+    if (poa_general_run(c, "modes", a, o)) return -1;
+    out->n_edge = a.n_sets;
+    out->cns_off = dup(o.cns_off.data(), (size_t)a.n_sets + 1);
+    out->cns = dup(o.cns.data(), o.cns.size());
     out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
-    if (c->opt.debug) fprintf(stderr, "[hx] POA modes call%s: %u sets, %.3g cells, kernels %.2f ms, %u sets rerun in a larger slot\n", affine ? " (affine)" : "", n_sets, (double)o.cells, o.kernel_ms, o.retried);
     return 0;
 }
 
@@ -454,10 +475,10 @@ extern "C" int hx_poa_sequences_mode(hx_ctx* c, uint32_t n_sets, const uint64_t*
     if (set_off[n_sets] >= 0x7fffffffULL) return fail("hx_poa_sequences_mode: too many sequences");
     const hx_poa_params pp{mp->match, mp->mismatch, mp->gap};
     if (mp->type == HX_POA_NW && !c->opt.poa_general) return hx_poa_sequences(c, n_sets, set_off, seq_off, bases, &pp, out);   // the tuned global path
-    return poa_general_call(c, n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap, mp->gap, 0, mp->type, out);
+    return poa_general_call(c, general_args("hx_poa_sequences_mode", n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap, mp->gap, mp->type, 0), out);
 }
 
-// what hx_poa_sequences_affine and hx_poa_msa ask of their scores, type and sequence count (0 = fine)
+// what hx_poa_sequences_affine, hx_poa_msa and hx_poa_weighted ask of their scores, type and sequence count (0 = fine)
 static int check_affine_call(const std::string& who, int32_t gap_open, int32_t gap_extend, int32_t type, uint64_t n_seq) {
     if (gap_open >= 0) return fail(who + ": the gap open score must be negative, not " + std::to_string(gap_open));
     if (gap_extend > 0) return fail(who + ": the gap extend score must not be positive, not " + std::to_string(gap_extend));
@@ -476,7 +497,7 @@ extern "C" int hx_poa_sequences_affine(hx_ctx* c, uint32_t n_sets, const uint64_
         const hx_poa_mode_params mp{ap->match, ap->mismatch, ap->gap_open, ap->type};
         return hx_poa_sequences_mode(c, n_sets, set_off, seq_off, bases, &mp, out);
     }
-    return poa_general_call(c, n_sets, set_off, seq_off, bases, ap->match, ap->mismatch, ap->gap_open, ap->gap_extend, 1, ap->type, out);
+    return poa_general_call(c, general_args("hx_poa_sequences_affine", n_sets, set_off, seq_off, bases, ap->match, ap->mismatch, ap->gap_open, ap->gap_extend, ap->type, 1), out);
 }
 
 // the multiple sequence alignment of every set: the general path's MSA instances (all three types: the tuned kNW path keeps no node per
@@ -485,25 +506,19 @@ extern "C" int hx_poa_msa(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, c
     memset(out, 0, sizeof(*out));
     if (!mp) return fail("hx_poa_msa: no parameters");
     if (check_affine_call("hx_poa_msa", mp->gap_open, mp->gap_extend, mp->type, set_off[n_sets])) return -1;
-    HIPCHK(hipSetDevice(c->device));
-    hxk::PoaModesArgs a{n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap_open, mp->type, (uint32_t)std::max(0, c->opt.poa_modes_slot_kb), c->opt.poa_workspace_gb, c->opt.debug};
-    a.gap_extend = mp->gap_extend; a.affine = mp->gap_extend != mp->gap_open || c->opt.poa_affine;
+    hxk::PoaModesArgs a = general_args("hx_poa_msa", n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap_open, mp->gap_extend, mp->type, mp->gap_extend != mp->gap_open || c->opt.poa_affine);
     a.msa = 1; a.include_consensus = mp->include_consensus != 0;
     hxk::PoaModesOut o;
-    std::string err;
-    if (hxk::poa_modes_run(c->stream, c->poa_modes_ws, a, o, err)) return fail(err);
-    c->tm.ms[3] += o.kernel_ms; c->tm.launches[3] += o.launches;
-    auto dup = [](const void* p, size_t bytes) { void* q = malloc(std::max<size_t>(1, bytes)); memcpy(q, p, bytes); return q; };
+    if (poa_general_run(c, "MSA", a, o)) return -1;
     out->n_set = n_sets;
-    out->n_rows = (uint32_t*)dup(o.msa_rows.data(), (size_t)n_sets * 4);
-    out->n_cols = (uint32_t*)dup(o.msa_cols.data(), (size_t)n_sets * 4);
-    out->msa_off = (uint64_t*)dup(o.msa_off.data(), ((size_t)n_sets + 1) * 8);
-    out->msa = (char*)dup(o.msa.data(), o.msa.size());
-    out->cns_off = (uint64_t*)dup(o.cns_off.data(), ((size_t)n_sets + 1) * 8);
-    out->cns = (char*)dup(o.cns.data(), o.cns.size());
+    out->n_rows = dup(o.msa_rows.data(), n_sets);
+    out->n_cols = dup(o.msa_cols.data(), n_sets);
+    out->msa_off = dup(o.msa_off.data(), (size_t)n_sets + 1);
+    out->msa = dup(o.msa.data(), o.msa.size());
+    out->cns_off = dup(o.cns_off.data(), (size_t)n_sets + 1);
+    out->cns = dup(o.cns.data(), o.cns.size());
     out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
     out->rows_kernel_ms = o.msa_rows_ms; out->rows_kernel_bytes = o.msa_moved_bytes;
-    if (c->opt.debug) fprintf(stderr, "[hx] POA MSA call%s: %u sets, %.3g cells, %zu bytes of rows, kernels %.2f ms (rows %.3f ms), %u sets rerun in a larger slot\n", a.affine ? " (affine)" : "", n_sets, (double)o.cells, o.msa.size(), o.kernel_ms, o.msa_rows_ms, o.retried);
     return 0;
 }
 
@@ -519,25 +534,19 @@ extern "C" int hx_poa_weighted(hx_ctx* c, uint32_t n_sets, const uint64_t* set_o
                 for (uint64_t p = seq_off[k]; p < seq_off[k + 1]; p++)
                     if (weights[p] == 0)
                         return fail("hx_poa_weighted: set " + std::to_string(i) + ", sequence " + std::to_string(k - set_off[i]) + ", position " + std::to_string(p - seq_off[k]) + ": a weight of 0 is not accepted (weights are 1..255)");
-    HIPCHK(hipSetDevice(c->device));
-    hxk::PoaModesArgs a{n_sets, set_off, seq_off, bases, wp->match, wp->mismatch, wp->gap_open, wp->type, (uint32_t)std::max(0, c->opt.poa_modes_slot_kb), c->opt.poa_workspace_gb, c->opt.debug};
-    a.gap_extend = wp->gap_extend; a.affine = wp->gap_extend != wp->gap_open || c->opt.poa_affine;
+    hxk::PoaModesArgs a = general_args("hx_poa_weighted", n_sets, set_off, seq_off, bases, wp->match, wp->mismatch, wp->gap_open, wp->gap_extend, wp->type, wp->gap_extend != wp->gap_open || c->opt.poa_affine);
     a.weighted = 1; a.weights = weights; a.want_coverage = wp->want_coverage != 0; a.want_profile = wp->want_profile != 0;
     std::vector<uint8_t> ones;
     if (!weights && c->opt.poa_weighted) { ones.assign(std::max<uint64_t>(1, seq_off[set_off[n_sets]]), 1); a.weights = ones.data(); }
     hxk::PoaModesOut o;
-    std::string err;
-    if (hxk::poa_modes_run(c->stream, c->poa_modes_ws, a, o, err)) return fail(err);
-    c->tm.ms[3] += o.kernel_ms; c->tm.launches[3] += o.launches;
-    auto dup = [](const void* p, size_t bytes) { void* q = malloc(std::max<size_t>(1, bytes)); memcpy(q, p, bytes); return q; };
+    if (poa_general_run(c, "weighted", a, o)) return -1;
     out->n_set = n_sets;
-    out->cns_off = (uint64_t*)dup(o.cns_off.data(), ((size_t)n_sets + 1) * 8);
-    out->cns = (char*)dup(o.cns.data(), o.cns.size());
-    if (a.want_coverage || a.want_profile) out->coverage = (uint32_t*)dup(o.cov.data(), o.cov.size() * 4);
-    if (a.want_profile) out->profile = (uint32_t*)dup(o.prof.data(), o.prof.size() * 4);
+    out->cns_off = dup(o.cns_off.data(), (size_t)n_sets + 1);
+    out->cns = dup(o.cns.data(), o.cns.size());
+    if (a.want_coverage || a.want_profile) out->coverage = dup(o.cov.data(), o.cov.size());
+    if (a.want_profile) out->profile = dup(o.prof.data(), o.prof.size());
     out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
     out->cov_kernel_ms = o.cov_ms; out->cov_kernel_bytes = o.cov_moved_bytes;
-    if (c->opt.debug) fprintf(stderr, "[hx] POA weighted call%s: %u sets, %.3g cells, kernels %.2f ms (coverage %.3f ms), %u sets rerun in a larger slot\n", a.affine ? " (affine)" : "", n_sets, (double)o.cells, o.kernel_ms, o.cov_ms, o.retried);
     return 0;
 }
 

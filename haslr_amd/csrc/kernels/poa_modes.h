@@ -18,18 +18,19 @@ struct PoaModesWs {   // the path's workspace: one device allocation, grows to t
 };
 
 struct PoaModesArgs {
-    uint32_t n_sets;
-    const uint64_t *set_off, *seq_off;   // hx_poa_sequences' layout
-    const char* bases;
-    int32_t match, mismatch, gap, type;  // type: 0 kSW, 1 kNW, 2 kOV (spoa::AlignmentType)
-    uint32_t slot_kb_cap;                // first round only: workspace slots of at most this many KB (0: no cap); sets that overflow are rerun in larger slots
-    double workspace_gb;                 // cap of the workspace (0: 40 % of the free device memory)
-    int debug;
+    const char* who = "";                // the entry point of the C-ABI that asks: the name every error text begins with
+    uint32_t n_sets = 0;
+    const uint64_t *set_off = nullptr, *seq_off = nullptr;   // hx_poa_sequences' layout
+    const char* bases = nullptr;
+    int32_t match = 0, mismatch = 0, gap = 0, type = 0;      // type: 0 kSW, 1 kNW, 2 kOV (spoa::AlignmentType)
+    uint32_t slot_kb_cap = 0;            // first round only: workspace slots of at most this many KB (0: no cap); sets that overflow are rerun in larger slots
+    double workspace_gb = 0;             // cap of the workspace (0: 40 % of the free device memory)
+    int debug = 0;
     int32_t gap_extend = 0;              // affine calls: gap is the gap open score, this the gap extend score (gap <= gap_extend <= 0)
     int affine = 0;                      // 1: the affine instances (a cell is an (H, F) pair, sequences of up to 16383 bases)
     int msa = 0;                         // 1: the MSA instances, and the alignment text in PoaModesOut (hx_poa_msa)
     int include_consensus = 0;           // MSA calls: the consensus is the last row of every set
-    int weighted = 0;                    // 1: hx_poa_weighted (the instances that keep the node of every base; errors name that entry)
+    int weighted = 0;                    // 1: hx_poa_weighted (the instances that keep the node of every base)
     const uint8_t* weights = nullptr;    // weighted calls: a weight per base of `bases`, 1..255 (the caller has checked), or null: all 1
     int want_coverage = 0;               // weighted calls: the coverage of every consensus base in PoaModesOut
     int want_profile = 0;                // weighted calls: and the four letter counts of its column

@@ -1,0 +1,162 @@
+// poa_modes_out.inl - what the general POA path (kernels/poa_modes.hip) writes beside the consensus text: the columns of the multiple sequence
+// alignment and its row text, the base weights on the graph's edges, and the coverage of the consensus bases. Included inside that file's
+// anonymous namespace, after MRow and block_excl_sum.
+
+// ---- MSA output (DESIGN.md "General POA path", "MSA output") ----
+// The columns of spoa's generate_multiple_sequence_alignment on the final rank order (order_rows leaves aligned nodes contiguous): rank r
+// opens a column iff none of its node's aligned nodes has a smaller rank, and the column of a rank is the number of openers up to it, less
+// one. colr (by rank) receives them; returns the number of columns. All lanes.
+template <int NT>
+__device__ uint32_t msa_columns(const G& g, const uint32_t V, uint32_t* colr, uint32_t* s_scan) {
+    const uint32_t t = threadIdx.x;
+    uint32_t carry = 0;
+    for (uint32_t b = 0; b < V; b += NT) {
+        const uint32_t r = b + t;
+        uint32_t opens = 0;
+        if (r < V) {
+            const uint32_t n = g.rank2node[r], na = g.n_aligned[n];
+            opens = 1;
+            for (uint32_t k = 0; k < na; k++) if (g.node2rank[g.aligned[3 * n + k]] < r) opens = 0;
+        }
+        uint32_t tot;
+        const uint32_t pre = block_excl_sum<NT>(opens, s_scan, &tot);
+        if (r < V) colr[r] = carry + pre + opens - 1u;   // (rank 0 always opens: never below 0)
+        carry += tot;
+    }
+    __syncthreads();
+    return carry;
+}
+
+// consensus_wave of poa_graph.inl that also hands back the rank the walk back starts from: the ranks of the consensus nodes are that rank and
+// its chain of g.pred. A copy: with consensus_wave as a wrapper over this one, k_poa's objects no longer come out byte for byte as before.
+__device__ uint32_t consensus_wave_end(G& g, const uint32_t V, char* out, uint32_t* end_rank) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t best, nbest;
+    bundle_pass(g, V, 0, false, -1, best, nbest);
+    if (best == NONE) best = g.node2rank[0];
+    for (uint32_t round = 0; !(g.row_meta[best] & 4u) && round <= V; round++) {
+        const uint32_t n0 = g.rank2node[best];
+        if (lane == 0)
+            for (uint32_t e = g.out_head[n0]; e != NONE; e = g.e_next_out[e])
+                for (uint32_t oe = g.in_head[g.e_to[e]]; oe != NONE; oe = g.e_next_in[oe])
+                    if (g.e_from[oe] != n0) g.score[g.node2rank[g.e_from[oe]]] = -1;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        uint32_t nb;
+        bundle_pass(g, V, best + 1, true, 0, nb, nbest);
+        best = nb == NONE ? g.node2rank[0] : nb;
+    }
+    *end_rank = best;
+    return bundle_backtrack(g, best, out);
+}
+
+// the columns of the len consensus bases, by the first wavefront: bundle_backtrack's walk (64 ranks around the walk fetched at once, the
+// walk inside them on v_readlane) with the rank's column in place of its base; back to front in rev, then turned round by all lanes
+__device__ void consensus_columns(const G& g, const uint32_t end_rank, const uint32_t len, const uint32_t* colr, uint32_t* rev, uint32_t* out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int32_t* pr_r = g.pred;
+    int32_t r = __builtin_amdgcn_readfirstlane((int)end_rank);
+    uint32_t k = 0;
+    int acc = 0;
+    while (r != -1 && k < len) {
+        const uint32_t cb = (uint32_t)r & ~63u, idx = min(cb + lane, (uint32_t)r);
+        const int p = pr_r[idx], c = (int)colr[idx];
+        while (r >= (int32_t)cb && k < len) {
+            const int l = r - (int32_t)cb;
+            const int cl = __builtin_amdgcn_readlane(c, l);
+            acc = lane == (k & 63u) ? cl : acc;
+            k++;
+            if ((k & 63u) == 0) rev[k - 64 + lane] = (uint32_t)acc;
+            r = __builtin_amdgcn_readlane(p, l);
+        }
+    }
+    if (lane < (k & 63u)) rev[(k & ~63u) + lane] = (uint32_t)acc;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    for (uint32_t q = lane; q < k; q += 64) out[q] = rev[k - 1 - q];
+}
+
+// The row text of one call, grid-wide: a wavefront takes 64 consecutive bases of one row. Columns rise strictly along a row, so lane i
+// writes the gaps between the previous base's column and its own, then its base: one nearly contiguous span per wavefront, every byte of
+// the output written exactly once (no fill pass). The gaps before a row's first base and after its last one can be long: the whole
+// wavefront writes those. A row without bases (an empty sequence) is one chunk that writes ncols gaps.
+__global__ __launch_bounds__(256) void k_msa_rows(const MRow* rows, const uint2* chunks, const uint32_t n_chunks, const uint32_t* base_col, const uint8_t* codes,
+                                                  const uint32_t* cns_col, const char* cns, char* out) {
+    const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (w >= n_chunks) return;
+    const uint2 ch = chunks[w];
+    const MRow R = rows[ch.x];
+    const uint32_t* col = (R.is_cns ? cns_col : base_col) + R.src;
+    char* row = out + R.dst;
+    const uint32_t i = ch.y + lane;
+    if (i < R.len) {
+        const uint32_t c = col[i];
+        const uint32_t from = i ? col[i - 1] + 1u : c;   // (the gaps before the first base: below, by all lanes)
+        if (c < R.ncols && from <= c) {                   // (always true for the columns run_set leaves: the guard keeps a store inside the row)
+            for (uint32_t q = from; q < c; q++) row[q] = '-';
+            row[c] = R.is_cns ? cns[R.src + i] : "ACGT"[codes[R.src + i] & 3];
+        }
+    }
+    if (ch.y == 0 && R.len) { const uint32_t c0 = min(col[0], R.ncols); for (uint32_t q = lane; q < c0; q += 64) row[q] = '-'; }
+    if (ch.y + 64 >= R.len) {
+        const uint32_t after = R.len ? col[R.len - 1] + 1u : 0u;
+        for (uint32_t q = after + lane; q < R.ncols; q += 64) row[q] = '-';
+    }
+}
+
+// ---- base weights and coverage (DESIGN.md "General POA path", "Base weights and coverage") ----
+// spoa's weighted add_alignment, applied beside the unit-weight one: the sequence walks the edge path[i-1] -> path[i] for every pair of
+// consecutive bases (prefix chain, aligned part, suffix chain alike) and add_alignment has given each of them 2; what is missing to spoa's
+// w[i-1] + w[i] is added here, by all lanes. The nodes of one sequence are distinct (its columns rise strictly), so no two lanes meet on an
+// edge. The edge is looked up in the out-list of path[i-1], as add_edge does.
+template <int NT>
+__device__ void weigh_path(G& g, const uint32_t* path, const uint8_t* w, const uint32_t L) {
+    for (uint32_t i = threadIdx.x + 1; i < L; i += NT) {
+        const int32_t extra = (int32_t)w[i - 1] + (int32_t)w[i] - 2;
+        if (extra == 0) continue;
+        const uint32_t to = path[i];
+        for (uint32_t e = g.out_head[path[i - 1]]; e != NONE; e = g.e_next_out[e])
+            if (g.e_to[e] == to) { g.e_w[e] += extra; break; }
+    }
+}
+
+// one sequence of >= 2 bases (k_cov_hist: src = its first base, hoff = the first column of its set among all columns of the call) or one
+// consensus (k_cov_gather: src = its place beside the device's consensus text, dst = its place in the output)
+struct CRow { uint64_t src, dst, hoff; uint32_t len, ncols; };
+
+// The number of bases per column (stride 1) or per column and letter (stride 4) of one call, grid-wide: a wavefront takes 64 consecutive
+// bases of one sequence. Columns rise strictly along a sequence, so the lanes of a wavefront never meet on a counter; different sequences
+// of a set do, hence the atomic.
+__global__ __launch_bounds__(256) void k_cov_hist(const CRow* rows, const uint2* chunks, const uint32_t n_chunks, const uint32_t* base_col, const uint8_t* codes,
+                                                  const uint32_t stride, uint32_t* hist) {
+    const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (w >= n_chunks) return;
+    const uint2 ch = chunks[w];
+    const CRow R = rows[ch.x];
+    const uint32_t i = ch.y + lane;
+    if (i >= R.len) return;
+    const uint32_t c = base_col[R.src + i];
+    if (c >= R.ncols) return;   // (never true for the columns run_set leaves: the guard keeps the add inside the set's counters)
+    atomicAdd(&hist[(R.hoff + c) * stride + (stride == 4 ? (uint32_t)(codes[R.src + i] & 3) : 0u)], 1u);
+}
+
+// coverage (and the four letter counts) of every consensus base: the counters of its column. A wavefront takes 64 consecutive bases of
+// one consensus; cov / prof are in the output's layout (consensus strings back to back).
+__global__ __launch_bounds__(256) void k_cov_gather(const CRow* rows, const uint2* chunks, const uint32_t n_chunks, const uint32_t* cns_col, const uint32_t* hist,
+                                                    const uint32_t stride, uint32_t* cov, uint32_t* prof) {
+    const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (w >= n_chunks) return;
+    const uint2 ch = chunks[w];
+    const CRow R = rows[ch.x];
+    const uint32_t i = ch.y + lane;
+    if (i >= R.len) return;
+    const uint32_t c = cns_col[R.src + i];
+    uint32_t n[4] = {0, 0, 0, 0};
+    if (c < R.ncols) {
+        const uint32_t* h = hist + (R.hoff + c) * stride;
+        n[0] = h[0];
+        if (stride == 4) { n[1] = h[1]; n[2] = h[2]; n[3] = h[3]; }
+    }
+    cov[R.dst + i] = n[0] + n[1] + n[2] + n[3];
+    if (prof) { uint32_t* p = prof + 4 * (R.dst + i); p[0] = n[0]; p[1] = n[1]; p[2] = n[2]; p[3] = n[3]; }
+}

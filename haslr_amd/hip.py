@@ -109,6 +109,29 @@ def env_options(environ=None):
     return {k[3:].lower(): v for k, v in environ.items() if k.startswith("HX_") and k[3:].lower() in names}
 
 
+def _flatten_sets(sets):
+    """the C-ABI's layout of sets of strings: (n_sets, set_off, seq_off, bases), the leading arguments of the hx_poa_sequences* family"""
+    import numpy as np
+    seqs = [q for st in sets for q in st]
+    set_off = np.zeros(len(sets) + 1, dtype=np.uint64)
+    for i, st in enumerate(sets):
+        set_off[i + 1] = set_off[i] + len(st)
+    seq_off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    for i, q in enumerate(seqs):
+        seq_off[i + 1] = seq_off[i] + len(q)
+    return len(sets), set_off.ctypes.data_as(T.u64p), seq_off.ctypes.data_as(T.u64p), "".join(seqs).encode()
+
+
+def _check_type(type):
+    if type not in T.POA_TYPES:
+        raise ValueError(f"unknown alignment type {type!r} (sw, nw, ov)")
+
+
+def _counters(o, *more):
+    """the counters every consensus output struct carries, and the named extra fields of o"""
+    return {k: getattr(o, k) for k in ("dp_cells", "seq_bases", "n_aligned") + more}
+
+
 class HipContext:
     """One GPU: resident inputs + the four hot-path operators."""
 
@@ -256,7 +279,7 @@ class HipContext:
         o = T.CnsOut()
         pp = T.PoaParams(match, mismatch, gap)
         self._chk(lib().hx_poa_batch(self._h, C.byref(pp), C.byref(o)))
-        r = T.cns_to_list(o), {"dp_cells": o.dp_cells, "seq_bases": o.seq_bases, "n_aligned": o.n_aligned}
+        r = T.cns_to_list(o), _counters(o)
         lib().hx_free_cns(self._h, C.byref(o))
         return r
 
@@ -279,16 +302,8 @@ class HipContext:
 
     def poa_sequences(self, sets, match=5, mismatch=-4, gap=-8):
         """consensus of every set of plain ACGT strings (aligned in the given order); nothing has to be resident"""
-        import numpy as np
-        set_off = np.zeros(len(sets) + 1, dtype=np.uint64)
-        seqs = [q for st in sets for q in st]
-        for i, st in enumerate(sets):
-            set_off[i + 1] = set_off[i] + len(st)
-        seq_off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        for i, q in enumerate(seqs):
-            seq_off[i + 1] = seq_off[i] + len(q)
         o, pp = T.CnsOut(), T.PoaParams(match, mismatch, gap)
-        self._chk(lib().hx_poa_sequences(self._h, len(sets), set_off.ctypes.data_as(T.u64p), seq_off.ctypes.data_as(T.u64p), "".join(seqs).encode(), C.byref(pp), C.byref(o)))
+        self._chk(lib().hx_poa_sequences(self._h, *_flatten_sets(sets), C.byref(pp), C.byref(o)))
         r = T.cns_to_list(o)
         lib().hx_free_cns(self._h, C.byref(o))
         return r
@@ -296,20 +311,11 @@ class HipContext:
     def poa_sequences_mode(self, sets, type="nw", match=5, mismatch=-4, gap=-8, stats=False):
         """poa_sequences with spoa's alignment type: "sw" (local), "nw" (global: the tuned path unless option poa_general is set) or "ov"
         (overlap). Returns the consensus strings, and with stats=True also the call's counters (dp_cells, seq_bases, n_aligned)."""
-        import numpy as np
-        if type not in T.POA_TYPES:
-            raise ValueError(f"unknown alignment type {type!r} (sw, nw, ov)")
-        set_off = np.zeros(len(sets) + 1, dtype=np.uint64)
-        seqs = [q for st in sets for q in st]
-        for i, st in enumerate(sets):
-            set_off[i + 1] = set_off[i] + len(st)
-        seq_off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        for i, q in enumerate(seqs):
-            seq_off[i + 1] = seq_off[i] + len(q)
+        _check_type(type)
         o, mp = T.CnsOut(), T.PoaModeParams(match, mismatch, gap, T.POA_TYPES[type])
-        self._chk(lib().hx_poa_sequences_mode(self._h, len(sets), set_off.ctypes.data_as(T.u64p), seq_off.ctypes.data_as(T.u64p), "".join(seqs).encode(), C.byref(mp), C.byref(o)))
+        self._chk(lib().hx_poa_sequences_mode(self._h, *_flatten_sets(sets), C.byref(mp), C.byref(o)))
         r = T.cns_to_list(o)
-        st = {"dp_cells": o.dp_cells, "seq_bases": o.seq_bases, "n_aligned": o.n_aligned}
+        st = _counters(o)
         lib().hx_free_cns(self._h, C.byref(o))
         return (r, st) if stats else r
 
@@ -317,20 +323,11 @@ class HipContext:
         """poa_sequences_mode with affine gaps: a gap of k bases costs gap_open + (k - 1) gap_extend (gap_open < 0, gap_open <= gap_extend
         <= 0). gap_extend == gap_open is the linear model and runs poa_sequences_mode's paths unless option poa_affine is set. Returns the
         consensus strings, and with stats=True also the call's counters (dp_cells, seq_bases, n_aligned)."""
-        import numpy as np
-        if type not in T.POA_TYPES:
-            raise ValueError(f"unknown alignment type {type!r} (sw, nw, ov)")
-        set_off = np.zeros(len(sets) + 1, dtype=np.uint64)
-        seqs = [q for st in sets for q in st]
-        for i, st in enumerate(sets):
-            set_off[i + 1] = set_off[i] + len(st)
-        seq_off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        for i, q in enumerate(seqs):
-            seq_off[i + 1] = seq_off[i] + len(q)
+        _check_type(type)
         o, ap = T.CnsOut(), T.PoaAffineParams(match, mismatch, gap_open, gap_extend, T.POA_TYPES[type])
-        self._chk(lib().hx_poa_sequences_affine(self._h, len(sets), set_off.ctypes.data_as(T.u64p), seq_off.ctypes.data_as(T.u64p), "".join(seqs).encode(), C.byref(ap), C.byref(o)))
+        self._chk(lib().hx_poa_sequences_affine(self._h, *_flatten_sets(sets), C.byref(ap), C.byref(o)))
         r = T.cns_to_list(o)
-        st = {"dp_cells": o.dp_cells, "seq_bases": o.seq_bases, "n_aligned": o.n_aligned}
+        st = _counters(o)
         lib().hx_free_cns(self._h, C.byref(o))
         return (r, st) if stats else r
 
@@ -340,21 +337,12 @@ class HipContext:
         row; all rows of a set have its number of columns. gap_extend None (or equal to gap_open) is the linear gap model. With
         stats=True returns (rows, consensus strings, counters): dp_cells, seq_bases, n_aligned as poa_sequences_affine has them, and
         rows_kernel_ms / rows_kernel_bytes of the kernel that writes the row text."""
-        import numpy as np
-        if type not in T.POA_TYPES:
-            raise ValueError(f"unknown alignment type {type!r} (sw, nw, ov)")
-        set_off = np.zeros(len(sets) + 1, dtype=np.uint64)
-        seqs = [q for st in sets for q in st]
-        for i, st in enumerate(sets):
-            set_off[i + 1] = set_off[i] + len(st)
-        seq_off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        for i, q in enumerate(seqs):
-            seq_off[i + 1] = seq_off[i] + len(q)
+        _check_type(type)
         o = T.MsaOut()
         mp = T.PoaMsaParams(match, mismatch, gap_open, gap_open if gap_extend is None else gap_extend, T.POA_TYPES[type], int(bool(include_consensus)))
-        self._chk(lib().hx_poa_msa(self._h, len(sets), set_off.ctypes.data_as(T.u64p), seq_off.ctypes.data_as(T.u64p), "".join(seqs).encode(), C.byref(mp), C.byref(o)))
+        self._chk(lib().hx_poa_msa(self._h, *_flatten_sets(sets), C.byref(mp), C.byref(o)))
         rows, cns = T.msa_to_lists(o)
-        st = {"dp_cells": o.dp_cells, "seq_bases": o.seq_bases, "n_aligned": o.n_aligned, "rows_kernel_ms": o.rows_kernel_ms, "rows_kernel_bytes": o.rows_kernel_bytes}
+        st = _counters(o, "rows_kernel_ms", "rows_kernel_bytes")
         lib().hx_free_msa(self._h, C.byref(o))
         return (rows, cns, st) if stats else rows
 
@@ -372,8 +360,7 @@ class HipContext:
         counters if stats): dp_cells, seq_bases, n_aligned as poa_sequences_affine has them, and cov_kernel_ms / cov_kernel_bytes of the
         coverage kernels."""
         import numpy as np
-        if type not in T.POA_TYPES:
-            raise ValueError(f"unknown alignment type {type!r} (sw, nw, ov)")
+        _check_type(type)
         if weights is not None and qualities is not None:
             raise ValueError("give weights or qualities, not both")
         given = weights if weights is not None else qualities
@@ -400,18 +387,11 @@ class HipContext:
                         raise ValueError(f"set {i}, sequence {k}, position {p}: {what} {int(vals[p])}, which is not accepted (weights are 1..255, qualities '\"'..'~')")
                     flat += vals.astype(np.uint8).tobytes()
             wbytes = bytes(flat) or b"\0"
-        set_off = np.zeros(len(sets) + 1, dtype=np.uint64)
-        seqs = [q for st in sets for q in st]
-        for i, st in enumerate(sets):
-            set_off[i + 1] = set_off[i] + len(st)
-        seq_off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        for i, q in enumerate(seqs):
-            seq_off[i + 1] = seq_off[i] + len(q)
         o = T.WcnsOut()
         wp = T.PoaWeightedParams(match, mismatch, gap_open, gap_open if gap_extend is None else gap_extend, T.POA_TYPES[type], int(bool(coverage)), int(bool(profile)))
-        self._chk(lib().hx_poa_weighted(self._h, len(sets), set_off.ctypes.data_as(T.u64p), seq_off.ctypes.data_as(T.u64p), "".join(seqs).encode(), wbytes, C.byref(wp), C.byref(o)))
+        self._chk(lib().hx_poa_weighted(self._h, *_flatten_sets(sets), wbytes, C.byref(wp), C.byref(o)))
         cns, cov, prof = T.wcns_to_lists(o)
-        st = {"dp_cells": o.dp_cells, "seq_bases": o.seq_bases, "n_aligned": o.n_aligned, "cov_kernel_ms": o.cov_kernel_ms, "cov_kernel_bytes": o.cov_kernel_bytes}
+        st = _counters(o, "cov_kernel_ms", "cov_kernel_bytes")
         lib().hx_free_wcns(self._h, C.byref(o))
         res = [cns] + ([cov] if coverage else []) + ([prof] if profile else []) + ([st] if stats else [])
         return cns if len(res) == 1 else tuple(res)

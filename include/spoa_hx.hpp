@@ -116,82 +116,76 @@ inline Stats stats() {
     return Stats{d.calls, d.sets};
 }
 
-// consensus of every set of sequences (set = the sub-sequences of one edge in alignment order) in ONE device call
-inline std::vector<std::string> consensus_batch(const std::vector<const std::vector<std::string>*>& sets, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8) {
+namespace detail {
+using Sets = std::vector<const std::vector<std::string>*>;
+inline Sets pointers(const std::vector<std::vector<std::string>>& sets) {
+    Sets p;
+    for (const auto& st : sets) p.push_back(&st);
+    return p;
+}
+// the C-ABI's layout of sets of strings (hx_poa_sequences in haslr_hip.h)
+struct Flat {
     std::vector<std::uint64_t> set_off{0}, seq_off{0};
     std::string bases;
-    for (const auto* st : sets) {
-        for (const auto& s : *st) { bases += s; seq_off.push_back(bases.size()); }
-        set_off.push_back(seq_off.size() - 1);
+    explicit Flat(const Sets& sets) {
+        for (const auto* st : sets) {
+            for (const auto& s : *st) { bases += s; seq_off.push_back(bases.size()); }
+            set_off.push_back(seq_off.size() - 1);
+        }
     }
-    const hx_poa_params pp{m, n, g};
-    hx_cns_out out;
+    std::uint32_t n_sets() const { return (std::uint32_t)(set_off.size() - 1); }
+};
+// call(ctx) under the device's mutex; throws the library's message when it fails, else returns take(ctx), still under the mutex
+template <class Call, class Take>
+auto locked_call(Call call, Take take) -> decltype(take((hx_ctx*)nullptr)) {
     Device& d = device();
     std::lock_guard<std::mutex> lock(d.mu);
     hx_ctx* ctx = context_locked(d);
-    if (hx_poa_sequences(ctx, (std::uint32_t)sets.size(), set_off.data(), seq_off.data(), bases.c_str(), &pp, &out) != 0)
-        throw std::runtime_error(std::string("spoa_hx: ") + hx_last_error());
-    std::vector<std::string> res(sets.size());
-    for (std::size_t i = 0; i < sets.size(); i++) res[i].assign(out.cns + out.cns_off[i], out.cns + out.cns_off[i + 1]);
-    hx_free_cns(ctx, &out);
+    if (call(ctx) != 0) throw std::runtime_error(std::string("spoa_hx: ") + hx_last_error());
+    return take(ctx);
+}
+inline std::vector<std::string> strings_of(const hx_cns_out& out) {
+    std::vector<std::string> res(out.n_edge);
+    for (std::size_t i = 0; i < res.size(); i++) res[i].assign(out.cns + out.cns_off[i], out.cns + out.cns_off[i + 1]);
     return res;
 }
+// the consensus strings of one hx_poa_sequences* call: call(ctx, &out)
+template <class Call>
+std::vector<std::string> consensus_call(Call call) {
+    hx_cns_out out;
+    return locked_call([&](hx_ctx* ctx) { return call(ctx, &out); },
+                       [&](hx_ctx* ctx) -> std::vector<std::string> { std::vector<std::string> res = strings_of(out); hx_free_cns(ctx, &out); return res; });
+}
+}  // namespace detail
+
+// consensus of every set of sequences (set = the sub-sequences of one edge in alignment order) in ONE device call
+inline std::vector<std::string> consensus_batch(const std::vector<const std::vector<std::string>*>& sets, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8) {
+    const detail::Flat f(sets);
+    const hx_poa_params pp{m, n, g};
+    return detail::consensus_call([&](hx_ctx* ctx, hx_cns_out* out) { return hx_poa_sequences(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), &pp, out); });
+}
 inline std::vector<std::string> consensus_batch(const std::vector<std::vector<std::string>>& sets, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8) {
-    std::vector<const std::vector<std::string>*> p;
-    for (const auto& st : sets) p.push_back(&st);
-    return consensus_batch(p, m, n, g);
+    return consensus_batch(detail::pointers(sets), m, n, g);
 }
 // ... with spoa's alignment type (the overloads above are kNW)
 inline std::vector<std::string> consensus_batch(const std::vector<const std::vector<std::string>*>& sets, AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8) {
-    std::vector<std::uint64_t> set_off{0}, seq_off{0};
-    std::string bases;
-    for (const auto* st : sets) {
-        for (const auto& s : *st) { bases += s; seq_off.push_back(bases.size()); }
-        set_off.push_back(seq_off.size() - 1);
-    }
+    const detail::Flat f(sets);
     const hx_poa_mode_params mp{m, n, g, static_cast<std::int32_t>(type)};
-    hx_cns_out out;
-    Device& d = device();
-    std::lock_guard<std::mutex> lock(d.mu);
-    hx_ctx* ctx = context_locked(d);
-    if (hx_poa_sequences_mode(ctx, (std::uint32_t)sets.size(), set_off.data(), seq_off.data(), bases.c_str(), &mp, &out) != 0)
-        throw std::runtime_error(std::string("spoa_hx: ") + hx_last_error());
-    std::vector<std::string> res(sets.size());
-    for (std::size_t i = 0; i < sets.size(); i++) res[i].assign(out.cns + out.cns_off[i], out.cns + out.cns_off[i + 1]);
-    hx_free_cns(ctx, &out);
-    return res;
+    return detail::consensus_call([&](hx_ctx* ctx, hx_cns_out* out) { return hx_poa_sequences_mode(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), &mp, out); });
 }
 inline std::vector<std::string> consensus_batch(const std::vector<std::vector<std::string>>& sets, AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8) {
-    std::vector<const std::vector<std::string>*> p;
-    for (const auto& st : sets) p.push_back(&st);
-    return consensus_batch(p, type, m, n, g);
+    return consensus_batch(detail::pointers(sets), type, m, n, g);
 }
 
 // ... with affine gaps: gap open g, gap extend e (g <= e <= 0; e == g is the linear model and takes the overloads above)
 inline std::vector<std::string> consensus_batch(const std::vector<const std::vector<std::string>*>& sets, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) {
     if (e == g) return consensus_batch(sets, type, m, n, g);
-    std::vector<std::uint64_t> set_off{0}, seq_off{0};
-    std::string bases;
-    for (const auto* st : sets) {
-        for (const auto& s : *st) { bases += s; seq_off.push_back(bases.size()); }
-        set_off.push_back(seq_off.size() - 1);
-    }
+    const detail::Flat f(sets);
     const hx_poa_affine_params ap{m, n, g, e, static_cast<std::int32_t>(type)};
-    hx_cns_out out;
-    Device& d = device();
-    std::lock_guard<std::mutex> lock(d.mu);
-    hx_ctx* ctx = context_locked(d);
-    if (hx_poa_sequences_affine(ctx, (std::uint32_t)sets.size(), set_off.data(), seq_off.data(), bases.c_str(), &ap, &out) != 0)
-        throw std::runtime_error(std::string("spoa_hx: ") + hx_last_error());
-    std::vector<std::string> res(sets.size());
-    for (std::size_t i = 0; i < sets.size(); i++) res[i].assign(out.cns + out.cns_off[i], out.cns + out.cns_off[i + 1]);
-    hx_free_cns(ctx, &out);
-    return res;
+    return detail::consensus_call([&](hx_ctx* ctx, hx_cns_out* out) { return hx_poa_sequences_affine(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), &ap, out); });
 }
 inline std::vector<std::string> consensus_batch(const std::vector<std::vector<std::string>>& sets, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) {
-    std::vector<const std::vector<std::string>*> p;
-    for (const auto& st : sets) p.push_back(&st);
-    return consensus_batch(p, type, m, n, g, e);
+    return consensus_batch(detail::pointers(sets), type, m, n, g, e);
 }
 
 // the multiple sequence alignment of every set in ONE device call (hx_poa_msa): per set one gapped row per sequence, in order, all of
@@ -199,33 +193,23 @@ inline std::vector<std::string> consensus_batch(const std::vector<std::vector<st
 // rule holds here: an empty sequence in a set gives a row of gaps (Graph below never records one, as spoa ignores it).
 inline std::vector<std::vector<std::string>> msa_batch(const std::vector<const std::vector<std::string>*>& sets, AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8,
                                                        std::int8_t e = -8, bool include_consensus = false) {
-    std::vector<std::uint64_t> set_off{0}, seq_off{0};
-    std::string bases;
-    for (const auto* st : sets) {
-        for (const auto& s : *st) { bases += s; seq_off.push_back(bases.size()); }
-        set_off.push_back(seq_off.size() - 1);
-    }
+    const detail::Flat f(sets);
     const hx_poa_msa_params mp{m, n, g, e, static_cast<std::int32_t>(type), include_consensus ? 1 : 0};
     hx_msa_out out;
-    Device& d = device();
-    std::lock_guard<std::mutex> lock(d.mu);
-    hx_ctx* ctx = context_locked(d);
-    if (hx_poa_msa(ctx, (std::uint32_t)sets.size(), set_off.data(), seq_off.data(), bases.c_str(), &mp, &out) != 0)
-        throw std::runtime_error(std::string("spoa_hx: ") + hx_last_error());
-    std::vector<std::vector<std::string>> res(sets.size());
-    for (std::size_t i = 0; i < sets.size(); i++)
-        for (std::uint32_t r = 0; r < out.n_rows[i]; r++) {
-            const char* p = out.msa + out.msa_off[i] + (std::uint64_t)r * out.n_cols[i];
-            res[i].emplace_back(p, p + out.n_cols[i]);
-        }
-    hx_free_msa(ctx, &out);
-    return res;
+    return detail::locked_call([&](hx_ctx* ctx) { return hx_poa_msa(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), &mp, &out); }, [&](hx_ctx* ctx) -> std::vector<std::vector<std::string>> {
+        std::vector<std::vector<std::string>> res(sets.size());
+        for (std::size_t i = 0; i < sets.size(); i++)
+            for (std::uint32_t r = 0; r < out.n_rows[i]; r++) {
+                const char* p = out.msa + out.msa_off[i] + (std::uint64_t)r * out.n_cols[i];
+                res[i].emplace_back(p, p + out.n_cols[i]);
+            }
+        hx_free_msa(ctx, &out);
+        return res;
+    });
 }
 inline std::vector<std::vector<std::string>> msa_batch(const std::vector<std::vector<std::string>>& sets, AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8,
                                                        std::int8_t e = -8, bool include_consensus = false) {
-    std::vector<const std::vector<std::string>*> p;
-    for (const auto& st : sets) p.push_back(&st);
-    return msa_batch(p, type, m, n, g, e, include_consensus);
+    return msa_batch(detail::pointers(sets), type, m, n, g, e, include_consensus);
 }
 
 // the consensus of every set under per-base weights in ONE device call (hx_poa_weighted), with the coverage of every consensus base and
@@ -239,48 +223,39 @@ struct Weighted {
 inline Weighted weighted_batch(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights,
                                AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, bool coverage = true, bool profile = false) {
     if (!weights.empty() && weights.size() != sets.size()) throw std::invalid_argument("spoa_hx: weighted_batch needs one set of weights per set of sequences, or none");
-    std::vector<std::uint64_t> set_off{0}, seq_off{0};
-    std::string bases;
+    const detail::Flat f(sets);
     std::vector<std::uint8_t> w;
-    for (std::size_t i = 0; i < sets.size(); i++) {
+    for (std::size_t i = 0; i < sets.size() && !weights.empty(); i++) {
         const auto& st = *sets[i];
-        if (!weights.empty() && weights[i]->size() != st.size()) throw std::invalid_argument("spoa_hx: weighted_batch: a set has another number of weight vectors than of sequences");
+        if (weights[i]->size() != st.size()) throw std::invalid_argument("spoa_hx: weighted_batch: a set has another number of weight vectors than of sequences");
         for (std::size_t k = 0; k < st.size(); k++) {
-            bases += st[k]; seq_off.push_back(bases.size());
-            if (weights.empty()) continue;
             const auto& wk = (*weights[i])[k];
             if (wk.size() != st[k].size()) throw std::invalid_argument("spoa_hx: weighted_batch: a sequence has another number of weights than of bases");
             w.insert(w.end(), wk.begin(), wk.end());
         }
-        set_off.push_back(seq_off.size() - 1);
     }
     if (!weights.empty() && w.empty()) w.push_back(1);   // (no base at all: a pointer that is not null, nothing behind it is read)
     const hx_poa_weighted_params wp{m, n, g, e, static_cast<std::int32_t>(type), coverage ? 1 : 0, profile ? 1 : 0};
     hx_wcns_out out;
-    Device& d = device();
-    std::lock_guard<std::mutex> lock(d.mu);
-    hx_ctx* ctx = context_locked(d);
-    if (hx_poa_weighted(ctx, (std::uint32_t)sets.size(), set_off.data(), seq_off.data(), bases.c_str(), weights.empty() ? nullptr : w.data(), &wp, &out) != 0)
-        throw std::runtime_error(std::string("spoa_hx: ") + hx_last_error());
-    Weighted res;
-    res.consensus.resize(sets.size());
-    if (coverage) res.coverage.resize(sets.size());
-    if (profile) res.profile.resize(sets.size());
-    for (std::size_t i = 0; i < sets.size(); i++) {
-        res.consensus[i].assign(out.cns + out.cns_off[i], out.cns + out.cns_off[i + 1]);
-        if (coverage) res.coverage[i].assign(out.coverage + out.cns_off[i], out.coverage + out.cns_off[i + 1]);
-        if (profile) res.profile[i].assign(out.profile + 4 * out.cns_off[i], out.profile + 4 * out.cns_off[i + 1]);
-    }
-    hx_free_wcns(ctx, &out);
-    return res;
+    return detail::locked_call([&](hx_ctx* ctx) { return hx_poa_weighted(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), weights.empty() ? nullptr : w.data(), &wp, &out); }, [&](hx_ctx* ctx) -> Weighted {
+        Weighted res;
+        res.consensus.resize(sets.size());
+        if (coverage) res.coverage.resize(sets.size());
+        if (profile) res.profile.resize(sets.size());
+        for (std::size_t i = 0; i < sets.size(); i++) {
+            res.consensus[i].assign(out.cns + out.cns_off[i], out.cns + out.cns_off[i + 1]);
+            if (coverage) res.coverage[i].assign(out.coverage + out.cns_off[i], out.coverage + out.cns_off[i + 1]);
+            if (profile) res.profile[i].assign(out.profile + 4 * out.cns_off[i], out.profile + 4 * out.cns_off[i + 1]);
+        }
+        hx_free_wcns(ctx, &out);
+        return res;
+    });
 }
 inline Weighted weighted_batch(const std::vector<std::vector<std::string>>& sets, const std::vector<std::vector<std::vector<std::uint8_t>>>& weights, AlignmentType type,
                                std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, bool coverage = true, bool profile = false) {
-    std::vector<const std::vector<std::string>*> p;
     std::vector<const std::vector<std::vector<std::uint8_t>>*> q;
-    for (const auto& st : sets) p.push_back(&st);
     for (const auto& ws : weights) q.push_back(&ws);
-    return weighted_batch(p, q, type, m, n, g, e, coverage, profile);
+    return weighted_batch(detail::pointers(sets), q, type, m, n, g, e, coverage, profile);
 }
 
 // one set on behalf of one caller thread, combined with whatever other threads have queued (see "Threads" above)
