@@ -230,6 +230,7 @@ struct hx_ctx {
     hxk::PoaModesWs poa_modes_ws;       // workspace of the general path (hx_poa_sequences_mode: kSW / kOV, and kNW under option poa_general; hx_poa_sequences_affine)
     std::mutex poa_arena_mu;            // hx_poa_reserve may run on a thread of its own beside the upload and the first stages
     double poa_host_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // host wall time of the last consensus call: plan, workspace, enqueue, device wait, collect, finish, (unused), total
+    uint64_t poa_retry[6] = {0, 0, 0, 0, 0, 0};         // edges the last consensus call ran again, per reason: far rows, in-degree, graph overflow, wide rows, sinks, stalled
     uint64_t poa_budget = 0;
     hxi::DV<hxk::PoaEdge> poa_edges;
     hxi::DV<hxk::PoaSeq> poa_seqs;

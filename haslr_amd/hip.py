@@ -16,7 +16,7 @@ SYMBOLS = ["hx_last_error", "hx_device_count", "hx_ctx_create", "hx_ctx_destroy"
            "hx_chain_reads", "hx_edge_support", "hx_edge_coords", "hx_poa_batch", "hx_free_chain", "hx_free_edges",
            "hx_free_coords", "hx_free_cns", "hx_edge_emit", "hx_edge_records_bytes", "hx_edge_records_export",
            "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
-           "hx_set_option", "hx_get_option", "hx_option_names", "hx_poa_memory_stats", "hx_poa_release_workspace", "hx_poa_prune_stats", "hx_group_set_timeout", "hx_group_inject_fault", "hx_poa_reserve", "hx_poa_host_times", "hx_poa_arena_stats", "hx_group_rccl_ranks",
+           "hx_set_option", "hx_get_option", "hx_option_names", "hx_poa_memory_stats", "hx_poa_release_workspace", "hx_poa_prune_stats", "hx_poa_retry_stats", "hx_group_set_timeout", "hx_group_inject_fault", "hx_poa_reserve", "hx_poa_host_times", "hx_poa_arena_stats", "hx_group_rccl_ranks",
            "hx_group_create", "hx_group_destroy", "hx_group_size", "hx_group_ctx", "hx_group_transport", "hx_edge_merge", "hx_group_backend_fill", "hx_group_exchange_stats"]
 
 
@@ -78,6 +78,8 @@ def lib():
         L.hx_poa_arena_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.hx_poa_arena_stats.restype = None
         L.hx_poa_prune_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64 * 4)]
+        L.hx_poa_retry_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64 * 6)]
+        L.hx_poa_retry_stats.restype = None
         L.hx_group_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_char_p, C.POINTER(C.c_void_p)]
         L.hx_group_set_timeout.argtypes = [C.c_void_p, C.c_double]
         L.hx_group_set_timeout.restype = None
@@ -214,6 +216,12 @@ class HipContext:
         o = (C.c_uint64 * 4)()
         lib().hx_poa_prune_stats(self._h, C.byref(o))
         return {"wave_rows": o[0], "wave_rows_skipped": o[1], "attempts_repeated": o[2], "alignments_with_threshold": o[3]}
+
+    def poa_retry_stats(self):
+        """edges the last consensus call of the tuned kNW path ran again, per reason (include/haslr_hip.h: hx_poa_retry_stats)"""
+        o = (C.c_uint64 * 6)()
+        lib().hx_poa_retry_stats(self._h, C.byref(o))
+        return dict(zip(("far_rows", "in_degree", "graph_overflow", "wide_rows", "sinks", "stalled"), o))
 
     def _chk(self, rc):
         if rc != 0:

@@ -105,8 +105,8 @@ int hx_poa_sequences_affine(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, c
 /*   hx_poa_msa        the multiple sequence alignment of every set beside its consensus (spoa's generate_multiple_sequence_alignment; DESIGN.md
  *                     "General POA path", "MSA output"): one gapped row per GIVEN sequence, in the given order, all of the set's n_cols columns
  *                     wide, and with include_consensus the consensus as one more, last row. Columns are spoa's: the nodes in rank order, aligned
- *                     nodes sharing one. An empty sequence gives a row of gaps; a set without a non-empty sequence has n_cols = 0. Letters other
- *                     than ACGT are read as A, as everywhere, and rows show what was read. Scores, types, errors and limits are
+ *                     nodes sharing one. An empty sequence gives a row of gaps; a set without a non-empty sequence has n_cols = 0. Lower case is read as
+ *                     upper case and letters other than ACGT as A, as everywhere, and rows show what was read. Scores, types, errors and limits are
  *                     hx_poa_sequences_affine's (gap_extend == gap_open: the linear instances, sequences of up to 32767 bases); every type,
  *                     HX_POA_NW too, runs the general path (the tuned global path keeps no node per base). Options poa_modes_slot_kb and
  *                     poa_workspace_gb act as on the other entries. Like the rest of the general path it is NOT pinned against spoa itself
@@ -211,6 +211,10 @@ void hx_poa_arena_stats(const hx_ctx*, uint64_t* capacity, uint64_t* allocations
 void hx_poa_memory_stats(const hx_ctx*, uint64_t* free_at_first_call, uint64_t* budget, uint64_t* last_call_workspace);
 /* pruning statistics of the last hx_poa_batch, summed over the pruned launches: [wave-rows, wave-rows skipped, attempts repeated, alignments with a threshold] */
 void hx_poa_prune_stats(const hx_ctx*, uint64_t* out4);
+/* edges (sets) the last consensus call of the tuned kNW path sent back from the kernel and ran again, counted once per round and reason: [far rows outgrew
+ * H, a node with more in-edges than the direction bytes' limit (option poa_max_indeg), graph outgrew its workspace, rows with more than 4 predecessors
+ * outgrew the wide-row pool, more sink rows than the launch keeps, members of a shared edge not resident together] */
+void hx_poa_retry_stats(const hx_ctx*, uint64_t* out6);
 /* POA work-group size: 0 = automatic (64..256 lanes per edge, ~8 DP columns per lane; gaps > 2047 columns are shared by several
  * work-groups), or force one work-group of 64/128/256/512/1024 lanes per edge (gaps up to 32767 bases) */
 void hx_set_poa_block(hx_ctx*, int threads);

@@ -6,18 +6,24 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 TYPES = {"sw": 0, "nw": 1, "ov": 2}
+# the tie-break mutants of the restatement (poa_modes_ref.cpp, PMR_MUTANT): each breaks one rule, for tests that ask whether their inputs tell the rules apart
+MUTANTS = {"last_end_cell": 1, "vertical_first": 2, "horizontal_first": 3, "last_predecessor": 4, "strict_bundle_tie": 5}
+STATS = ("tied", "max_candidates", "ties_above_8", "closure_above_32", "max_in_degree", "wide_rows", "max_sinks")
 
 
 class ModesRef:
-    def __init__(self, build_dir):
-        so = os.path.join(build_dir, "libpoa_modes_ref.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", os.path.join(HERE, "poa_modes_ref.cpp"), "-o", so])
+    def __init__(self, build_dir, mutant=None):
+        so = os.path.join(build_dir, "libpoa_modes_ref%s.so" % ("" if mutant is None else "_" + mutant))
+        define = [] if mutant is None else ["-DPMR_MUTANT=%d" % MUTANTS[mutant]]
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", *define, os.path.join(HERE, "poa_modes_ref.cpp"), "-o", so])
         L = C.CDLL(so)
         L.pmr_consensus.restype = C.c_void_p
         L.pmr_consensus.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
         L.pmr_last_alignment.restype = C.c_int32
         L.pmr_last_alignment.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32]
         L.pmr_free.argtypes = [C.c_void_p]
+        L.pmr_last_stats.restype = None
+        L.pmr_last_stats.argtypes = [C.POINTER(C.c_uint64 * 7)]
         self._L = L
 
     def consensus_cells(self, seqs, type="nw", match=5, mismatch=-4, gap=-8):
@@ -38,3 +44,14 @@ class ModesRef:
         a, b = (C.c_int32 * max(1, n))(), (C.c_int32 * max(1, n))()
         self._L.pmr_last_alignment(a, b, n)
         return [(a[k], b[k]) for k in range(n)]
+
+    def last_stats(self):
+        """what the last consensus of the calling thread met, as a dict over STATS (poa_modes_ref.cpp: pmr_last_stats)"""
+        o = (C.c_uint64 * 7)()
+        self._L.pmr_last_stats(C.byref(o))
+        return dict(zip(STATS, o))
+
+    def consensus_stats(self, seqs, type="nw", match=5, mismatch=-4, gap=-8):
+        """(consensus, sum of V * L, statistics)"""
+        s, cells = self.consensus_cells(seqs, type, match, mismatch, gap)
+        return s, cells, self.last_stats()

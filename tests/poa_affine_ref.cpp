@@ -105,7 +105,7 @@ extern "C" char* par_consensus(const char* const* seqs, uint32_t n, int32_t m, i
         const size_t L = strlen(seqs[k]);
         if (L == 0) continue;
         s.resize(L);
-        for (size_t i = 0; i < L; i++) { const char* p = strchr("ACGT", seqs[k][i]); s[i] = p ? (uint8_t)(p - "ACGT") : 0; }
+        for (size_t i = 0; i < L; i++) s[i] = read_code(seqs[k][i]);
         t_last_affine = align_affine(G, s.data(), (uint32_t)L, m, x, g, e, type, &c);
         G.add_alignment(t_last_affine.aln, s.data(), (uint32_t)L);
         non_empty++;

@@ -6,6 +6,14 @@
 //   pmr_consensus(seqs, n, m, x, g, type, cells)   consensus of the sequences in order (empty ones skipped); *cells += sum of V * L
 //   pmr_last_alignment(node, pos, cap)              the (node | -1, position | -1) pairs of the last alignment this thread made
 //   pmr_free(p)                                     frees a consensus
+//   pmr_last_stats(out7)                            what the last pmr_consensus of this thread met: [alignments whose best end cell is tied, the most
+//                                                   tied end cells, ties of more than 8, kNW ties whose closure U (the candidates' columns and everything
+//                                                   downstream of them, as kernels/poa.hip's tie shortcut and the oracle's ORC_POA_TIES statistic build it)
+//                                                   holds more than 32 nodes, the largest in-degree and the nodes with more than 4 in-edges of the final
+//                                                   graph, the most sinks an alignment saw]
+// PMR_MUTANT (compile time, tests only) breaks ONE tie-break rule, so that a test can show that its inputs tell the rules apart: 1 the LAST best end
+// cell instead of the first, 2 vertical before diagonal in the traceback, 3 horizontal first, 4 the LAST matching predecessor instead of the first,
+// 5 `<` instead of `<=` in the heaviest-bundle tie.
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -14,7 +22,17 @@
 #include <utility>
 #include <vector>
 
+#ifndef PMR_MUTANT
+#define PMR_MUTANT 0
+#endif
+
 namespace {
+
+// a letter as every entry point reads it: A C G T in either case are 0 1 2 3, anything else is 0 (the reference's table, Compressed_sequence.cpp:10-19, with "& 3")
+inline uint8_t read_code(char c) { return c == 'C' || c == 'c' ? 1 : c == 'G' || c == 'g' ? 2 : c == 'T' || c == 't' ? 3 : 0; }
+
+struct Stats { uint64_t tied = 0, max_cand = 0, ties_gt8 = 0, closure_gt32 = 0, max_indeg = 0, wide_rows = 0, max_sinks = 0; };
+thread_local Stats t_stats;
 
 enum { T_SW = 0, T_NW = 1, T_OV = 2 };
 constexpr int32_t NEG_INF = INT32_MIN / 2;
@@ -107,7 +125,7 @@ struct Graph {
             for (uint32_t e : in[n]) {
                 const uint32_t f = edges[e].from;
                 if (skip_dead && score[f] == -1) continue;
-                if (score[n] < edges[e].w || (score[n] == edges[e].w && score[pred[n]] <= score[f])) { score[n] = edges[e].w; pred[n] = (int32_t)f; }
+                if (score[n] < edges[e].w || (score[n] == edges[e].w && (PMR_MUTANT == 5 ? score[pred[n]] < score[f] : score[pred[n]] <= score[f]))) { score[n] = edges[e].w; pred[n] = (int32_t)f; }
             }
             if (pred[n] != -1) score[n] += score[pred[n]];
         };
@@ -135,6 +153,21 @@ struct Graph {
     }
 };
 
+// the tie shortcut's set U for the candidate nodes of a kNW end-node tie: their columns (a node and its aligned mates) and everything downstream, closed
+// under out-edges and aligned mates (growth stops past 4096 nodes, as in the oracle's statistic)
+size_t tie_closure(const Graph& G, const std::vector<uint32_t>& cand) {
+    std::vector<uint32_t> U;
+    std::vector<char> in_u(G.code.size(), 0);
+    auto addcol = [&](uint32_t x) {
+        if (in_u[x]) return;
+        in_u[x] = 1; U.push_back(x);
+        for (uint32_t a : G.aligned[x]) if (!in_u[a]) { in_u[a] = 1; U.push_back(a); }
+    };
+    for (uint32_t c : cand) addcol(c);
+    for (size_t q = 0; q < U.size() && U.size() <= 4096; q++) for (uint32_t e : G.outs[U[q]]) addcol(G.edges[e].to);
+    return U.size();
+}
+
 // the DP and traceback of one sequence against the graph in its current rank order; returns spoa's (node | -1, pos | -1) pairs, in order
 std::vector<std::pair<int32_t, int32_t>> align(const Graph& G, const uint8_t* s, uint32_t L, int32_t m, int32_t x, int32_t g, int type, uint64_t* cells) {
     std::vector<std::pair<int32_t, int32_t>> aln;
@@ -156,9 +189,12 @@ std::vector<std::pair<int32_t, int32_t>> align(const Graph& G, const uint8_t* s,
     int32_t best = type == T_SW ? 0 : NEG_INF;
     size_t bi = 0, bj = 0;
     bool found = false;
+    std::vector<uint32_t> tied;   // (statistics: the nodes of the candidate end cells that hold the best score so far)
+    uint64_t sinks = 0;
     for (size_t i = 1; i <= V; i++) {
         const uint32_t n = G.rank2node[i - 1];
         const bool sink = G.outs[n].empty();
+        sinks += sink;
         int32_t* row = &H[i * W];
         if (type == T_NW) { int32_t b = NEG_INF; for (size_t p : P[i]) b = std::max(b, H[p * W]); row[0] = b + g; }
         else row[0] = 0;
@@ -170,8 +206,16 @@ std::vector<std::pair<int32_t, int32_t>> align(const Graph& G, const uint8_t* s,
             if (type == T_SW) h = std::max(h, 0);
             row[j] = h;
             const bool cand = type == T_SW || (type == T_NW ? sink && j == L : (sink || j == L));
-            if (cand && h > best) { best = h; bi = i; bj = j; found = true; }
+            if (cand && found && h == best) tied.push_back(n);
+            if (cand && (h > best || (PMR_MUTANT == 1 && found && h == best))) { if (h > best) tied.assign(1, n); best = h; bi = i; bj = j; found = true; }
         }
+    }
+    t_stats.max_sinks = std::max<uint64_t>(t_stats.max_sinks, sinks);
+    if (found && tied.size() > 1) {
+        t_stats.tied++;
+        t_stats.max_cand = std::max<uint64_t>(t_stats.max_cand, tied.size());
+        t_stats.ties_gt8 += tied.size() > 8;
+        if (type == T_NW) t_stats.closure_gt32 += tie_closure(G, tied) > 32;
     }
     if (!found) return aln;   // kSW: no cell above 0
     size_t i = bi, j = bj;
@@ -180,12 +224,17 @@ std::vector<std::pair<int32_t, int32_t>> align(const Graph& G, const uint8_t* s,
         const int32_t h = H[i * W + j];
         size_t pi = i, pj = j;
         bool ok = false;
-        if (i != 0 && j != 0) {
+        auto diagonal = [&]() {
+            if (ok || i == 0 || j == 0) return;
             const int32_t sg = G.code[G.rank2node[i - 1]] == s[j - 1] ? m : x;
-            for (size_t p : P[i]) if (h == H[p * W + j - 1] + sg) { pi = p; pj = j - 1; ok = true; break; }
-        }
-        if (!ok && i != 0)
-            for (size_t p : P[i]) if (h == H[p * W + j] + g) { pi = p; pj = j; ok = true; break; }
+            for (size_t p : P[i]) if (h == H[p * W + j - 1] + sg) { pi = p; pj = j - 1; ok = true; if (PMR_MUTANT != 4) break; }
+        };
+        auto vertical = [&]() {
+            if (ok || i == 0) return;
+            for (size_t p : P[i]) if (h == H[p * W + j] + g) { pi = p; pj = j; ok = true; if (PMR_MUTANT != 4) break; }
+        };
+        if (PMR_MUTANT == 3 && i != 0 && j != 0 && h == H[i * W + j - 1] + g) { pj = j - 1; ok = true; }
+        if (PMR_MUTANT == 2) { vertical(); diagonal(); } else { diagonal(); vertical(); }
         if (!ok) { if (j == 0) break; pi = i; pj = j - 1; }   // (horizontal; j = 0 cannot happen on a consistent matrix)
         aln.emplace_back(pi == i ? -1 : (int32_t)G.rank2node[i - 1], pj == j ? -1 : (int32_t)(j - 1));
         i = pi; j = pj;
@@ -203,16 +252,18 @@ extern "C" char* pmr_consensus(const char* const* seqs, uint32_t n, int32_t m, i
     uint64_t c = 0;
     uint32_t non_empty = 0;
     std::vector<uint8_t> s;
+    t_stats = Stats();
     for (uint32_t k = 0; k < n; k++) {
         const size_t L = strlen(seqs[k]);
         if (L == 0) continue;
         s.resize(L);
-        for (size_t i = 0; i < L; i++) { const char* p = strchr("ACGT", seqs[k][i]); s[i] = p ? (uint8_t)(p - "ACGT") : 0; }
+        for (size_t i = 0; i < L; i++) s[i] = read_code(seqs[k][i]);
         t_last = align(G, s.data(), (uint32_t)L, m, x, g, type, &c);
         G.add_alignment(t_last, s.data(), (uint32_t)L);
         non_empty++;
     }
     const std::string out = non_empty ? G.consensus() : std::string();
+    for (const auto& in : G.in) { t_stats.max_indeg = std::max<uint64_t>(t_stats.max_indeg, in.size()); t_stats.wide_rows += in.size() > 4; }
     if (cells) *cells += c;
     char* r = (char*)malloc(out.size() + 1);
     memcpy(r, out.c_str(), out.size() + 1);
@@ -223,6 +274,12 @@ extern "C" int32_t pmr_last_alignment(int32_t* node, int32_t* pos, int32_t cap) 
     const int32_t n = (int32_t)t_last.size();
     for (int32_t k = 0; k < n && k < cap; k++) { node[k] = t_last[k].first; pos[k] = t_last[k].second; }
     return n;
+}
+
+extern "C" void pmr_last_stats(uint64_t* out7) {
+    const Stats& t = t_stats;
+    const uint64_t v[7] = {t.tied, t.max_cand, t.ties_gt8, t.closure_gt32, t.max_indeg, t.wide_rows, t.max_sinks};
+    memcpy(out7, v, sizeof(v));
 }
 
 extern "C" void pmr_free(char* p) { free(p); }

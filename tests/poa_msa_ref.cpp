@@ -104,7 +104,7 @@ extern "C" char* pma_msa(const char* const* seqs, uint32_t n, int32_t m, int32_t
         const size_t L = strlen(seqs[k]);
         if (L == 0) continue;
         s.resize(L);
-        for (size_t i = 0; i < L; i++) { const char* p = strchr("ACGT", seqs[k][i]); s[i] = p ? (uint8_t)(p - "ACGT") : 0; }
+        for (size_t i = 0; i < L; i++) s[i] = read_code(seqs[k][i]);
         const std::vector<std::pair<int32_t, int32_t>> aln = e == g ? align(G, s.data(), (uint32_t)L, m, x, g, type, &cells) : align_affine(G, s.data(), (uint32_t)L, m, x, g, e, type, &cells).aln;
         uint32_t n_after = 0;
         paths[k] = derive_path(G, aln, s.data(), (uint32_t)L, &n_after);
@@ -150,7 +150,7 @@ extern "C" char* pma_msa(const char* const* seqs, uint32_t n, int32_t m, int32_t
     for (uint32_t k = 0; k < n; k++) {
         std::string row(n_cols, '-');
         if (!rising(paths[k])) late |= F_RISING;
-        for (size_t i = 0; i < paths[k].size(); i++) row[col[paths[k][i]]] = seqs[k][i];
+        for (size_t i = 0; i < paths[k].size(); i++) row[col[paths[k][i]]] = "ACGT"[read_code(seqs[k][i])];   // (a row shows what was read: include/haslr_hip.h)
         out += row + "\n";
     }
     if (include_consensus) {

@@ -43,7 +43,7 @@ extern "C" char* pwr_weighted(const char* const* seqs, const uint8_t* const* wei
         const size_t L = strlen(seqs[k]);
         if (L == 0) continue;
         s.resize(L);
-        for (size_t i = 0; i < L; i++) { const char* p = strchr("ACGT", seqs[k][i]); s[i] = p ? (uint8_t)(p - "ACGT") : 0; }
+        for (size_t i = 0; i < L; i++) s[i] = read_code(seqs[k][i]);
         const std::vector<std::pair<int32_t, int32_t>> aln = e == g ? align(G, s.data(), (uint32_t)L, m, x, g, type, &cells) : align_affine(G, s.data(), (uint32_t)L, m, x, g, e, type, &cells).aln;
         uint32_t n_after = 0;
         paths[k] = derive_path(G, aln, s.data(), (uint32_t)L, &n_after);
