@@ -154,6 +154,7 @@ struct HxOptions {
     int poa_general = 0;           // hx_poa_sequences_mode with HX_POA_NW runs the general path (kernels/poa_modes.hip) instead of the tuned one: the cross-check of what the modes share with kNW
     int poa_affine = 0;            // hx_poa_sequences_affine with gap_extend == gap_open runs the affine instances of the general path instead of the linear paths: the cross-check of the affine kernel against the linear ones
     int poa_weighted = 0;          // hx_poa_weighted without weights runs the weighted instances of the general path on weights of 1 instead of the MSA twins: the cross-check of the weighted graph update against the unit-weight one
+    int poa_convex = 0;            // the convex entries with gap_extend2 <= gap_extend run the convex instances of the general path instead of the affine entries: the cross-check of the convex kernel against the affine one
     int poa_modes_slot_kb = 0;     // the general path's first round of slots holds at most this many KB (testing: forces the overflow and the rerun in a larger slot; 0 no cap)
 };
 

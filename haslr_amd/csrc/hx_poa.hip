@@ -432,12 +432,14 @@ extern "C" int hx_poa_sequences(hx_ctx* c, uint32_t n_sets, const uint64_t* set_
 }
 
 // ---- the general path (kernels/poa_modes.hip). Its entry points differ in what they validate and in the outputs they hand over; the call itself is one.
+// The scores of a call of the general path and its gap model (kernels/poa_modes.h: 0 linear, 1 affine, 2 convex); open2 / extend2 count under the convex model only
+struct GapScores { int32_t match, mismatch, open, extend, open2, extend2, type; int model; };
+
 // The request of an entry point `who` (the name its errors carry), as far as every entry has it; the entry adds its own flags.
-static hxk::PoaModesArgs general_args(const char* who, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, int32_t match, int32_t mismatch,
-                                      int32_t gap_open, int32_t gap_extend, int32_t type, int affine) {
+static hxk::PoaModesArgs general_args(const char* who, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const GapScores& sc) {
     hxk::PoaModesArgs a;
     a.who = who; a.n_sets = n_sets; a.set_off = set_off; a.seq_off = seq_off; a.bases = bases;
-    a.match = match; a.mismatch = mismatch; a.gap = gap_open; a.gap_extend = gap_extend; a.type = type; a.affine = affine;
+    a.match = sc.match; a.mismatch = sc.mismatch; a.gap = sc.open; a.gap_extend = sc.extend; a.gap_open2 = sc.open2; a.gap_extend2 = sc.extend2; a.type = sc.type; a.gap_model = sc.model;
     return a;
 }
 
@@ -452,7 +454,7 @@ static int poa_general_run(hx_ctx* c, const char* tag, hxk::PoaModesArgs& a, hxk
         char rows[48] = "", part[48] = "";   // what an MSA or a weighted call adds to the line
         if (a.msa) { snprintf(rows, sizeof rows, "%zu bytes of rows, ", o.msa.size()); snprintf(part, sizeof part, " (rows %.3f ms)", o.msa_rows_ms); }
         if (a.weighted) snprintf(part, sizeof part, " (coverage %.3f ms)", o.cov_ms);
-        fprintf(stderr, "[hx] POA %s call%s: %u sets, %.3g cells, %skernels %.2f ms%s, %u sets rerun in a larger slot\n", tag, a.affine ? " (affine)" : "", a.n_sets, (double)o.cells, rows, o.kernel_ms, part, o.retried);
+        fprintf(stderr, "[hx] POA %s call%s: %u sets, %.3g cells, %skernels %.2f ms%s, %u sets rerun in a larger slot\n", tag, a.gap_model == 2 ? " (convex)" : a.gap_model == 1 ? " (affine)" : "", a.n_sets, (double)o.cells, rows, o.kernel_ms, part, o.retried);
     }
     return 0;
 }
@@ -478,7 +480,7 @@ extern "C" int hx_poa_sequences_mode(hx_ctx* c, uint32_t n_sets, const uint64_t*
     if (set_off[n_sets] >= 0x7fffffffULL) return fail("hx_poa_sequences_mode: too many sequences");
     const hx_poa_params pp{mp->match, mp->mismatch, mp->gap};
     if (mp->type == HX_POA_NW && !c->opt.poa_general) return hx_poa_sequences(c, n_sets, set_off, seq_off, bases, &pp, out);   // the tuned global path
-    return poa_general_call(c, general_args("hx_poa_sequences_mode", n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap, mp->gap, mp->type, 0), out);
+    return poa_general_call(c, general_args("hx_poa_sequences_mode", n_sets, set_off, seq_off, bases, GapScores{mp->match, mp->mismatch, mp->gap, mp->gap, 0, 0, mp->type, 0}), out);
 }
 
 // what hx_poa_sequences_affine, hx_poa_msa and hx_poa_weighted ask of their scores, type and sequence count (0 = fine)
@@ -492,6 +494,20 @@ static int check_affine_call(const std::string& who, int32_t gap_open, int32_t g
     return 0;
 }
 
+// what the three convex entries ask on top of that: the second piece is a valid piece of its own and opens no cheaper than the first
+static int check_convex_call(const std::string& who, const hx_poa_convex_params& p, uint64_t n_seq) {
+    if (check_affine_call(who, p.gap_open, p.gap_extend, p.type, n_seq)) return -1;
+    if (p.gap_open2 >= 0) return fail(who + ": the second gap open score must be negative, not " + std::to_string(p.gap_open2));
+    if (p.gap_extend2 > 0) return fail(who + ": the second gap extend score must not be positive, not " + std::to_string(p.gap_extend2));
+    if (p.gap_extend2 < p.gap_open2) return fail(who + ": the second gap extend score " + std::to_string(p.gap_extend2) + " is below the second gap open score " + std::to_string(p.gap_open2) + " (extending a gap must not cost more than opening one)");
+    if (p.gap_open2 > p.gap_open) return fail(who + ": the second gap open score " + std::to_string(p.gap_open2) + " is above the first gap open score " + std::to_string(p.gap_open) + " (the first piece is the one that opens no dearer)");
+    return 0;
+}
+// a second piece that extends no cheaper than the first never wins (it opens no cheaper either): the call is the affine one with the first piece,
+// unless option poa_convex keeps it on the convex kernel (the cross-check of that kernel against the affine one)
+static bool convex_is_affine(const hx_ctx* c, const hx_poa_convex_params& p) { return p.gap_extend2 <= p.gap_extend && !c->opt.poa_convex; }
+static GapScores convex_scores(const hx_poa_convex_params& p) { return GapScores{p.match, p.mismatch, p.gap_open, p.gap_extend, p.gap_open2, p.gap_extend2, p.type, 2}; }
+
 extern "C" int hx_poa_sequences_affine(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_affine_params* ap, hx_cns_out* out) {
     memset(out, 0, sizeof(*out));
     if (!ap) return fail("hx_poa_sequences_affine: no parameters");
@@ -500,17 +516,25 @@ extern "C" int hx_poa_sequences_affine(hx_ctx* c, uint32_t n_sets, const uint64_
         const hx_poa_mode_params mp{ap->match, ap->mismatch, ap->gap_open, ap->type};
         return hx_poa_sequences_mode(c, n_sets, set_off, seq_off, bases, &mp, out);
     }
-    return poa_general_call(c, general_args("hx_poa_sequences_affine", n_sets, set_off, seq_off, bases, ap->match, ap->mismatch, ap->gap_open, ap->gap_extend, ap->type, 1), out);
+    return poa_general_call(c, general_args("hx_poa_sequences_affine", n_sets, set_off, seq_off, bases, GapScores{ap->match, ap->mismatch, ap->gap_open, ap->gap_extend, 0, 0, ap->type, 1}), out);
+}
+
+extern "C" int hx_poa_sequences_convex(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_convex_params* cp, hx_cns_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!cp) return fail("hx_poa_sequences_convex: no parameters");
+    if (check_convex_call("hx_poa_sequences_convex", *cp, set_off[n_sets])) return -1;
+    if (convex_is_affine(c, *cp)) {
+        const hx_poa_affine_params ap{cp->match, cp->mismatch, cp->gap_open, cp->gap_extend, cp->type};
+        return hx_poa_sequences_affine(c, n_sets, set_off, seq_off, bases, &ap, out);
+    }
+    return poa_general_call(c, general_args("hx_poa_sequences_convex", n_sets, set_off, seq_off, bases, convex_scores(*cp)), out);
 }
 
 // the multiple sequence alignment of every set: the general path's MSA instances (all three types: the tuned kNW path keeps no node per
-// base), linear ones when the two gap scores are equal
-extern "C" int hx_poa_msa(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_msa_params* mp, hx_msa_out* out) {
-    memset(out, 0, sizeof(*out));
-    if (!mp) return fail("hx_poa_msa: no parameters");
-    if (check_affine_call("hx_poa_msa", mp->gap_open, mp->gap_extend, mp->type, set_off[n_sets])) return -1;
-    hxk::PoaModesArgs a = general_args("hx_poa_msa", n_sets, set_off, seq_off, bases, mp->match, mp->mismatch, mp->gap_open, mp->gap_extend, mp->type, mp->gap_extend != mp->gap_open || c->opt.poa_affine);
-    a.msa = 1; a.include_consensus = mp->include_consensus != 0;
+// base) of the gap model the scores name
+static int poa_msa_call(hx_ctx* c, const char* who, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const GapScores& sc, int include_consensus, hx_msa_out* out) {
+    hxk::PoaModesArgs a = general_args(who, n_sets, set_off, seq_off, bases, sc);
+    a.msa = 1; a.include_consensus = include_consensus != 0;
     hxk::PoaModesOut o;
     if (poa_general_run(c, "MSA", a, o)) return -1;
     out->n_set = n_sets;
@@ -525,20 +549,37 @@ extern "C" int hx_poa_msa(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, c
     return 0;
 }
 
+// linear instances when the two gap scores are equal
+extern "C" int hx_poa_msa(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_msa_params* mp, hx_msa_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!mp) return fail("hx_poa_msa: no parameters");
+    if (check_affine_call("hx_poa_msa", mp->gap_open, mp->gap_extend, mp->type, set_off[n_sets])) return -1;
+    return poa_msa_call(c, "hx_poa_msa", n_sets, set_off, seq_off, bases, GapScores{mp->match, mp->mismatch, mp->gap_open, mp->gap_extend, 0, 0, mp->type, mp->gap_extend != mp->gap_open || c->opt.poa_affine}, mp->include_consensus, out);
+}
+
+extern "C" int hx_poa_msa_convex(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_convex_params* cp, int include_consensus, hx_msa_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!cp) return fail("hx_poa_msa_convex: no parameters");
+    if (check_convex_call("hx_poa_msa_convex", *cp, set_off[n_sets])) return -1;
+    if (convex_is_affine(c, *cp)) {
+        const hx_poa_msa_params mp{cp->match, cp->mismatch, cp->gap_open, cp->gap_extend, cp->type, include_consensus != 0};
+        return hx_poa_msa(c, n_sets, set_off, seq_off, bases, &mp, out);
+    }
+    return poa_msa_call(c, "hx_poa_msa_convex", n_sets, set_off, seq_off, bases, convex_scores(*cp), include_consensus, out);
+}
+
 // the consensus under per-base weights with coverage and profile: the general path's instances that keep the node of every base (all
 // three types), the weighted ones when weights are given
-extern "C" int hx_poa_weighted(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_weighted_params* wp, hx_wcns_out* out) {
-    memset(out, 0, sizeof(*out));
-    if (!wp) return fail("hx_poa_weighted: no parameters");
-    if (check_affine_call("hx_poa_weighted", wp->gap_open, wp->gap_extend, wp->type, set_off[n_sets])) return -1;
+static int poa_weighted_call(hx_ctx* c, const std::string& who, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const GapScores& sc,
+                             int want_coverage, int want_profile, hx_wcns_out* out) {
     if (weights)
         for (uint32_t i = 0; i < n_sets; i++)
             for (uint64_t k = set_off[i]; k < set_off[i + 1]; k++)
                 for (uint64_t p = seq_off[k]; p < seq_off[k + 1]; p++)
                     if (weights[p] == 0)
-                        return fail("hx_poa_weighted: set " + std::to_string(i) + ", sequence " + std::to_string(k - set_off[i]) + ", position " + std::to_string(p - seq_off[k]) + ": a weight of 0 is not accepted (weights are 1..255)");
-    hxk::PoaModesArgs a = general_args("hx_poa_weighted", n_sets, set_off, seq_off, bases, wp->match, wp->mismatch, wp->gap_open, wp->gap_extend, wp->type, wp->gap_extend != wp->gap_open || c->opt.poa_affine);
-    a.weighted = 1; a.weights = weights; a.want_coverage = wp->want_coverage != 0; a.want_profile = wp->want_profile != 0;
+                        return fail(who + ": set " + std::to_string(i) + ", sequence " + std::to_string(k - set_off[i]) + ", position " + std::to_string(p - seq_off[k]) + ": a weight of 0 is not accepted (weights are 1..255)");
+    hxk::PoaModesArgs a = general_args(who.c_str(), n_sets, set_off, seq_off, bases, sc);
+    a.weighted = 1; a.weights = weights; a.want_coverage = want_coverage != 0; a.want_profile = want_profile != 0;
     std::vector<uint8_t> ones;
     if (!weights && c->opt.poa_weighted) { ones.assign(std::max<uint64_t>(1, seq_off[set_off[n_sets]]), 1); a.weights = ones.data(); }
     hxk::PoaModesOut o;
@@ -551,6 +592,26 @@ extern "C" int hx_poa_weighted(hx_ctx* c, uint32_t n_sets, const uint64_t* set_o
     out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
     out->cov_kernel_ms = o.cov_ms; out->cov_kernel_bytes = o.cov_moved_bytes;
     return 0;
+}
+
+extern "C" int hx_poa_weighted(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_weighted_params* wp, hx_wcns_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!wp) return fail("hx_poa_weighted: no parameters");
+    if (check_affine_call("hx_poa_weighted", wp->gap_open, wp->gap_extend, wp->type, set_off[n_sets])) return -1;
+    return poa_weighted_call(c, "hx_poa_weighted", n_sets, set_off, seq_off, bases, weights, GapScores{wp->match, wp->mismatch, wp->gap_open, wp->gap_extend, 0, 0, wp->type, wp->gap_extend != wp->gap_open || c->opt.poa_affine},
+                             wp->want_coverage, wp->want_profile, out);
+}
+
+extern "C" int hx_poa_weighted_convex(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params* cp, int want_coverage,
+                                      int want_profile, hx_wcns_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!cp) return fail("hx_poa_weighted_convex: no parameters");
+    if (check_convex_call("hx_poa_weighted_convex", *cp, set_off[n_sets])) return -1;
+    if (convex_is_affine(c, *cp)) {
+        const hx_poa_weighted_params wp{cp->match, cp->mismatch, cp->gap_open, cp->gap_extend, cp->type, want_coverage != 0, want_profile != 0};
+        return hx_poa_weighted(c, n_sets, set_off, seq_off, bases, weights, &wp, out);
+    }
+    return poa_weighted_call(c, "hx_poa_weighted_convex", n_sets, set_off, seq_off, bases, weights, convex_scores(*cp), want_coverage, want_profile, out);
 }
 
 extern "C" void hx_free_wcns(hx_ctx*, hx_wcns_out* o) { free(o->cns_off); free(o->cns); free(o->coverage); free(o->profile); memset(o, 0, sizeof(*o)); }

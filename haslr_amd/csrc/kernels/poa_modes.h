@@ -1,4 +1,4 @@
-// poa_modes.h — host side of the general POA path (kernels/poa_modes.hip): spoa's linear-gap and affine-gap engines in their three
+// poa_modes.h — host side of the general POA path (kernels/poa_modes.hip): spoa's linear-gap, affine-gap and convex-gap engines in their three
 // alignment modes (kSW local, kNW global, kOV overlap) for caller-given sequence sets, one workgroup per set. DESIGN.md "General POA path".
 #ifndef HX_POA_MODES_H
 #define HX_POA_MODES_H
@@ -26,8 +26,10 @@ struct PoaModesArgs {
     uint32_t slot_kb_cap = 0;            // first round only: workspace slots of at most this many KB (0: no cap); sets that overflow are rerun in larger slots
     double workspace_gb = 0;             // cap of the workspace (0: 40 % of the free device memory)
     int debug = 0;
-    int32_t gap_extend = 0;              // affine calls: gap is the gap open score, this the gap extend score (gap <= gap_extend <= 0)
-    int affine = 0;                      // 1: the affine instances (a cell is an (H, F) pair, sequences of up to 16383 bases)
+    int32_t gap_extend = 0;              // affine and convex calls: gap is the gap open score, this the gap extend score (gap <= gap_extend <= 0)
+    int32_t gap_open2 = 0, gap_extend2 = 0;   // convex calls: the second piece (gap_open2 <= gap_extend2 <= 0, gap_open2 <= gap)
+    int gap_model = 0;                   // 0: the linear instances; 1: the affine ones (a cell is an (H, F) pair, sequences of up to 16383 bases); 2: the
+                                         // convex ones (a cell is (H, F, O), 12 bytes, sequences of up to 8191 bases)
     int msa = 0;                         // 1: the MSA instances, and the alignment text in PoaModesOut (hx_poa_msa)
     int include_consensus = 0;           // MSA calls: the consensus is the last row of every set
     int weighted = 0;                    // 1: hx_poa_weighted (the instances that keep the node of every base)

@@ -1,7 +1,8 @@
 // poa_modes.hip — the general POA path: spoa's linear-gap engine in its three alignment modes (kSW local, kNW global, kOV overlap) for
 // caller-given sequence sets (hx_poa_sequences_mode; DESIGN.md "General POA path" has the semantics and the mapping), and the affine-gap
-// engine in the same modes (hx_poa_sequences_affine: same mapping, a cell is the pair (H, F), its own row of the instance table). All of it
-// is one kernel template, k_poa_general<NT, CPL, AFF, MSA, WTS>.
+// engine in the same modes (hx_poa_sequences_affine: same mapping, a cell is the pair (H, F), its own row of the instance table), and the
+// two-piece affine ("convex") gap model (hx_poa_sequences_convex: a cell is (H, F, O), 12 bytes, a third row of the table). All of it is
+// one kernel template, k_poa_general<NT, CPL, GM, MSA, WTS>, GM the gap model.
 //
 // It is a kernel family of its own beside the tuned global-only k_poa (kernels/poa.hip), which depends on kNW throughout (de-ramped keys
 // with tie bits, score-bound pruning, sink lists, end-node ties decided on closures, multi-member pipelines). What the modes share with
@@ -27,7 +28,7 @@
 // the heaviest bundle sees spoa's weighted edges; two grid-wide kernels (k_cov_hist, k_cov_gather) count the bases per column and letter and
 // pick the counts at the consensus bases' columns.
 //
-// Layout: the DP and traceback of both gap models are poa_modes_dp.inl, the columns, row text and coverage poa_modes_out.inl; this file keeps
+// Layout: the DP and traceback of the three gap models are poa_modes_dp.inl, the columns, row text and coverage poa_modes_out.inl; this file keeps
 // the work of one set (run_set), the kernel, the instance table and the host driver (poa_modes_run, in named stages).
 #include <algorithm>
 #include <chrono>
@@ -47,6 +48,7 @@ namespace {
 #include "poa_graph.inl"    // the graph of a set, spoa's topological order, heaviest bundle
 
 enum { MT_SW = 0, MT_NW = 1, MT_OV = 2 };
+enum { GM_LINEAR = 0, GM_AFFINE = 1, GM_CONVEX = 2 };   // PoaModesArgs::gap_model
 enum { MS_OK = 0, MS_H_OVERFLOW = 1, MS_GRAPH_OVERFLOW = 2 };
 constexpr uint32_t MAX_SET_BASES = (1u << 21) - 2;   // node ids are packed in 21 bits (+1) in the node records of poa_graph.inl
 
@@ -58,11 +60,12 @@ struct MArgs {
     uint8_t* ws; uint64_t slot_bytes;
     int32_t m, n, g, type;
     char* cns; uint32_t *cns_len, *status, *vseen; unsigned long long* cells;
-    int32_t e;   // affine instances only: gap extend (g is gap open)
+    int32_t e;   // affine and convex instances only: gap extend (g is gap open)
     // MSA instances only: per base of the call (global offset) its node, rewritten to its column when the set is done; columns per set;
     // column of every consensus base beside cns (null: not asked for)
     uint32_t *base_col, *n_cols, *cns_col;
     const uint8_t* wts;   // weighted instances only: the weight of every base of the call (1..255), beside codes
+    int32_t q, c;         // convex instances only: gap open and gap extend of the second piece
 };
 
 // one row of the MSA text: its columns (rising) start at cols[src], its letters at codes[src] (a sequence) or cns[src] (the consensus row)
@@ -144,10 +147,10 @@ __device__ void order_rows(G& g, const uint32_t V, uint32_t* s_scan) {
 
 struct Shared { uint32_t item, V, E, fail; int best; unsigned long long key; };
 
-#include "poa_modes_dp.inl"     // DP and traceback, linear and affine gaps
+#include "poa_modes_dp.inl"     // DP and traceback, linear, affine and convex gaps
 #include "poa_modes_out.inl"    // MSA columns and row text, base weights, coverage
 
-template <int NT, int CPL, bool AFF, bool MSA, bool WTS>
+template <int NT, int CPL, int GM, bool MSA, bool WTS>
 __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Shared& sh, int* s_wtot, uint32_t* s_scan) {
     const uint32_t t = threadIdx.x;
     const MSet S = a.sets[set];
@@ -155,7 +158,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     const uint64_t pools = carve_pools(slot, S.sum_len, S.nseq, S.lmax, &g, &path, &colref);
     if (pools > a.slot_bytes) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
     int32_t* H = (int32_t*)(slot + pools);
-    const uint64_t hcap = (a.slot_bytes - pools) / (AFF ? 8 : 4);   // cells the slot holds (affine: an (H, F) pair each)
+    const uint64_t hcap = (a.slot_bytes - pools) / (GM == GM_CONVEX ? 12 : GM == GM_AFFINE ? 8 : 4);   // cells the slot holds (affine: an (H, F) pair each; convex: (H, F, O))
     uint32_t V = 0, E = 0, non_empty = 0;
     unsigned long long cells = 0;
     for (uint32_t k = 0; k < S.nseq; k++) {
@@ -169,7 +172,10 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
             if ((uint64_t)(V + 1) * (L + 1) > hcap) { if (t == 0) { a.status[set] = MS_H_OVERFLOW; a.vseen[set] = V; } return; }
             cells += (unsigned long long)V * L;
             uint32_t bi, bj;
-            if (AFF) {
+            if (GM == GM_CONVEX) {
+                dp_rows_convex<NT, CPL>(g, (Cell3*)H, V, s, L, a, sh, s_wtot, &bi, &bj);
+                if (t == 0 && bi) na = traceback_convex(g, (const Cell3*)H, s, L, bi, bj, a);
+            } else if (GM == GM_AFFINE) {
                 dp_rows_affine<NT, CPL>(g, (int2*)H, V, s, L, a, sh, s_wtot, &bi, &bj);
                 if (t == 0 && bi) na = traceback_affine(g, (const int2*)H, s, L, bi, bj, a);
             } else {
@@ -210,10 +216,10 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     __syncthreads();   // the slot is free for the next set
 }
 
-template <int NT, int CPL, bool AFF, bool MSA, bool WTS>
+template <int NT, int CPL, int GM, bool MSA, bool WTS>
 __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
     __shared__ Shared sh;
-    __shared__ int s_wtot[NT / 64];
+    __shared__ int s_wtot[(GM == GM_CONVEX ? 2 : 1) * (NT / 64)];   // per wave the total of its row scan (convex: of its two)
     __shared__ uint32_t s_scan[NT / 64];
     uint8_t* slot = a.ws + (size_t)blockIdx.x * a.slot_bytes;
     for (;;) {
@@ -222,7 +228,7 @@ __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
         const uint32_t q = sh.item;
         __syncthreads();
         if (q >= a.n_items) return;
-        run_set<NT, CPL, AFF, MSA, WTS>(a, a.order[q], slot, sh, s_wtot, s_scan);
+        run_set<NT, CPL, GM, MSA, WTS>(a, a.order[q], slot, sh, s_wtot, s_scan);
     }
 }
 
@@ -230,16 +236,18 @@ __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
 // Each comes in three variants: the consensus alone (a consensus-only call runs the code it ran before the MSA existed), with the node of
 // every base kept (the MSA; coverage needs it too), and with base weights applied on top of that (hx_poa_weighted with weights).
 struct Inst { int nt, cpl; const void* variant[3]; };
-#define HX_INST(AFF, NT, CPL) {NT, CPL, {(const void*)k_poa_general<NT, CPL, AFF, false, false>, (const void*)k_poa_general<NT, CPL, AFF, true, false>, (const void*)k_poa_general<NT, CPL, AFF, true, true>}}
+#define HX_INST(GM, NT, CPL) {NT, CPL, {(const void*)k_poa_general<NT, CPL, GM, false, false>, (const void*)k_poa_general<NT, CPL, GM, true, false>, (const void*)k_poa_general<NT, CPL, GM, true, true>}}
 constexpr int N_INST = 4;
-// by gap model (0 linear, 1 affine). The affine instances keep two accumulators per column (diagonal and F): 16 columns per lane throughout,
-// more lanes instead
-const Inst kInst[2][N_INST] = {
-    {HX_INST(false, 64, 16), HX_INST(false, 256, 16), HX_INST(false, 256, 32), HX_INST(false, 1024, 32)},
-    {HX_INST(true, 64, 16), HX_INST(true, 256, 16), HX_INST(true, 512, 16), HX_INST(true, 1024, 16)},
+// by gap model (GM_LINEAR, GM_AFFINE, GM_CONVEX). The affine instances keep two accumulators per column (diagonal and F): 16 columns per
+// lane throughout, more lanes instead. The convex ones keep three (diagonal, F and O) and stop at 512 lanes, two waves per SIMD with up to
+// 256 registers each: 1024 lanes would have 128 and spill the row (DESIGN.md "Convex gaps")
+const Inst kInst[3][N_INST] = {
+    {HX_INST(GM_LINEAR, 64, 16), HX_INST(GM_LINEAR, 256, 16), HX_INST(GM_LINEAR, 256, 32), HX_INST(GM_LINEAR, 1024, 32)},
+    {HX_INST(GM_AFFINE, 64, 16), HX_INST(GM_AFFINE, 256, 16), HX_INST(GM_AFFINE, 512, 16), HX_INST(GM_AFFINE, 1024, 16)},
+    {HX_INST(GM_CONVEX, 64, 16), HX_INST(GM_CONVEX, 128, 16), HX_INST(GM_CONVEX, 256, 16), HX_INST(GM_CONVEX, 512, 16)},
 };
 #undef HX_INST
-constexpr uint32_t MAX_LEN[2] = {1024 * 32 - 1, 1024 * 16 - 1};
+constexpr uint32_t MAX_LEN[3] = {1024 * 32 - 1, 1024 * 16 - 1, 512 * 16 - 1};
 inline const void* fn(const Inst& inst, bool cols, bool weighted) { return inst.variant[weighted ? 2 : cols ? 1 : 0]; }
 
 template <class T> struct Buf {   // device buffer of one call
@@ -276,12 +284,13 @@ struct Run {
     hipStream_t s; PoaModesWs& ws; const PoaModesArgs& a; PoaModesOut& o; std::string& err;
     const std::string who = a.who;
     const uint32_t ns = a.n_sets;
-    const bool aff = a.affine != 0, msa = a.msa != 0;
+    const int gm = a.gap_model;                             // GM_LINEAR, GM_AFFINE or GM_CONVEX (the entry points set nothing else)
+    const bool msa = a.msa != 0;
     const bool wtd = a.weighted != 0;                        // hx_poa_weighted: the node of every base is kept, as for the MSA
     const bool cols = msa || wtd;
     const bool want_cov = wtd && (a.want_coverage || a.want_profile);
-    const Inst* const inst = kInst[aff];
-    const uint64_t cell_bytes = aff ? 8 : 4;                 // affine: an (H, F) pair per cell
+    const Inst* const inst = kInst[gm];
+    const uint64_t cell_bytes = gm == GM_CONVEX ? 12 : gm == GM_AFFINE ? 8 : 4;   // affine: an (H, F) pair per cell; convex: (H, F, O)
     const uint64_t nseq = a.set_off[ns], nb = a.seq_off[nseq];
     std::vector<MSet> sets = std::vector<MSet>(ns);
     std::vector<uint64_t> cns_off = std::vector<uint64_t>((size_t)ns + 1, 0);
@@ -314,14 +323,14 @@ struct Run {
 
     // ---- the sets checked and described, the call's inputs on the device, the memory budget
     int prepare() {
-        const uint32_t max_len = MAX_LEN[aff];
+        const uint32_t max_len = MAX_LEN[gm];
         o = PoaModesOut();
         for (uint32_t i = 0; i < ns; i++) {
             MSet& S = sets[i];
             S.seq_begin = a.set_off[i]; S.nseq = (uint32_t)(a.set_off[i + 1] - a.set_off[i]); S.sum_len = 0; S.lmax = 0;
             for (uint64_t k = a.set_off[i]; k < a.set_off[i + 1]; k++) {
                 const uint64_t L = a.seq_off[k + 1] - a.seq_off[k];
-                if (L > max_len) { err = who + ": set " + std::to_string(i) + " holds a sequence of " + std::to_string(L) + " bases, longer than " + std::to_string(max_len) + (aff ? " (the longest the general POA path takes with affine gaps)" : " (the longest the general POA path takes)"); return -1; }
+                if (L > max_len) { err = who + ": set " + std::to_string(i) + " holds a sequence of " + std::to_string(L) + " bases, longer than " + std::to_string(max_len) + (gm == GM_CONVEX ? " (the longest the general POA path takes with convex gaps)" : gm == GM_AFFINE ? " (the longest the general POA path takes with affine gaps)" : " (the longest the general POA path takes)"); return -1; }
                 S.sum_len += L; S.lmax = std::max(S.lmax, (uint32_t)L);
                 o.seq_bases += L; o.n_aligned += L != 0;
             }
@@ -410,11 +419,11 @@ struct Run {
                     if (by[k].empty()) continue;
                     MArgs q{d_sets.p, d_order.p + base[k], (uint32_t)by[k].size(), d_counter.p + k, d_codes.p, d_soff.p, (uint8_t*)ws.p, slot[k],
                             a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p, a.gap_extend,
-                            d_base_col.p, d_n_cols.p, d_cns_col.p, d_wts.p};
+                            d_base_col.p, d_n_cols.p, d_cns_col.p, d_wts.p, a.gap_open2, a.gap_extend2};
                     void* kargs[] = {&q};
                     MCHK(hipLaunchKernel(fn_of(k), dim3(nslots[k]), dim3((uint32_t)inst[k].nt), kargs, 0, s));
                     o.launches++;
-                    if (a.debug) fprintf(stderr, "[hx] POA modes%s: %zu sets on %u workgroups of %d lanes x %d columns, slots of %.1f MB\n", aff ? " (affine)" : "", by[k].size(), nslots[k], inst[k].nt, inst[k].cpl, slot[k] / 1e6);
+                    if (a.debug) fprintf(stderr, "[hx] POA modes%s: %zu sets on %u workgroups of %d lanes x %d columns, slots of %.1f MB\n", gm == GM_CONVEX ? " (convex)" : gm == GM_AFFINE ? " (affine)" : "", by[k].size(), nslots[k], inst[k].nt, inst[k].cpl, slot[k] / 1e6);
                 }
                 return 0;
             })) return -1;

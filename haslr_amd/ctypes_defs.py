@@ -71,6 +71,11 @@ class PoaAffineParams(C.Structure):
     _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("type", C.c_int32)]
 
 
+class PoaConvexParams(C.Structure):
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("gap_open2", C.c_int32),
+                ("gap_extend2", C.c_int32), ("type", C.c_int32)]
+
+
 class PoaMsaParams(C.Structure):
     _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("type", C.c_int32),
                 ("include_consensus", C.c_int32)]

@@ -15,7 +15,7 @@ _lib = None
 SYMBOLS = ["hx_last_error", "hx_device_count", "hx_ctx_create", "hx_ctx_destroy", "hx_upload", "hx_set_read_shard", "hx_set_prefiltered",
            "hx_chain_reads", "hx_edge_support", "hx_edge_coords", "hx_poa_batch", "hx_free_chain", "hx_free_edges",
            "hx_free_coords", "hx_free_cns", "hx_edge_emit", "hx_edge_records_bytes", "hx_edge_records_export",
-           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
+           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
            "hx_set_option", "hx_get_option", "hx_option_names", "hx_poa_memory_stats", "hx_poa_release_workspace", "hx_poa_prune_stats", "hx_poa_retry_stats", "hx_group_set_timeout", "hx_group_inject_fault", "hx_poa_reserve", "hx_poa_host_times", "hx_poa_arena_stats", "hx_group_rccl_ranks",
            "hx_group_create", "hx_group_destroy", "hx_group_size", "hx_group_ctx", "hx_group_transport", "hx_edge_merge", "hx_group_backend_fill", "hx_group_exchange_stats"]
 
@@ -49,6 +49,9 @@ def lib():
         L.hx_free_msa.argtypes = [C.c_void_p, C.POINTER(T.MsaOut)]
         L.hx_poa_weighted.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaWeightedParams), C.POINTER(T.WcnsOut)]
         L.hx_free_wcns.argtypes = [C.c_void_p, C.POINTER(T.WcnsOut)]
+        L.hx_poa_sequences_convex.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.CnsOut)]
+        L.hx_poa_msa_convex.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.c_int, C.POINTER(T.MsaOut)]
+        L.hx_poa_weighted_convex.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.c_int, C.c_int, C.POINTER(T.WcnsOut)]
         L.hx_free_chain.argtypes = [C.c_void_p, C.POINTER(T.ChainOut)]
         L.hx_free_edges.argtypes = [C.c_void_p, C.POINTER(T.EdgesOut)]
         L.hx_free_coords.argtypes = [C.c_void_p, C.POINTER(T.CoordsOut)]
@@ -127,6 +130,15 @@ def _flatten_sets(sets):
 def _check_type(type):
     if type not in T.POA_TYPES:
         raise ValueError(f"unknown alignment type {type!r} (sw, nw, ov)")
+
+
+def _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2):
+    """the PoaConvexParams of a call that gives the second piece, None of one that gives neither of its scores"""
+    if gap_open2 is None and gap_extend2 is None:
+        return None
+    if gap_open2 is None or gap_extend2 is None:
+        raise ValueError("give gap_open2 and gap_extend2, or neither")
+    return T.PoaConvexParams(match, mismatch, gap_open, gap_open if gap_extend is None else gap_extend, gap_open2, gap_extend2, T.POA_TYPES[type])
 
 
 def _counters(o, *more):
@@ -339,23 +351,41 @@ class HipContext:
         lib().hx_free_cns(self._h, C.byref(o))
         return (r, st) if stats else r
 
-    def poa_msa(self, sets, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=None, include_consensus=False, stats=False):
+    def poa_sequences_convex(self, sets, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=-6, gap_open2=-10, gap_extend2=-4, stats=False):
+        """poa_sequences_mode with two-piece affine (convex) gaps: a gap of k bases scores max(gap_open + (k - 1) gap_extend, gap_open2 +
+        (k - 1) gap_extend2); each piece has open < 0, open <= extend <= 0, and gap_open2 <= gap_open. gap_extend2 <= gap_extend is the
+        affine model of the first piece and runs poa_sequences_affine's paths unless option poa_convex is set. Sequences of up to 8191
+        bases. Returns the consensus strings, and with stats=True also the call's counters (dp_cells, seq_bases, n_aligned)."""
+        _check_type(type)
+        o, cp = T.CnsOut(), T.PoaConvexParams(match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2, T.POA_TYPES[type])
+        self._chk(lib().hx_poa_sequences_convex(self._h, *_flatten_sets(sets), C.byref(cp), C.byref(o)))
+        r = T.cns_to_list(o)
+        st = _counters(o)
+        lib().hx_free_cns(self._h, C.byref(o))
+        return (r, st) if stats else r
+
+    def poa_msa(self, sets, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=None, include_consensus=False, stats=False, gap_open2=None, gap_extend2=None):
         """the multiple sequence alignment of every set (spoa's generate_multiple_sequence_alignment): per set the list of its rows, one
         per given sequence in the given order (an empty sequence: a row of gaps) and, with include_consensus, the consensus as the last
         row; all rows of a set have its number of columns. gap_extend None (or equal to gap_open) is the linear gap model. With
         stats=True returns (rows, consensus strings, counters): dp_cells, seq_bases, n_aligned as poa_sequences_affine has them, and
-        rows_kernel_ms / rows_kernel_bytes of the kernel that writes the row text."""
+        rows_kernel_ms / rows_kernel_bytes of the kernel that writes the row text. gap_open2 and gap_extend2 (both or neither) switch to
+        the convex gap model of poa_sequences_convex (hx_poa_msa_convex)."""
         _check_type(type)
         o = T.MsaOut()
-        mp = T.PoaMsaParams(match, mismatch, gap_open, gap_open if gap_extend is None else gap_extend, T.POA_TYPES[type], int(bool(include_consensus)))
-        self._chk(lib().hx_poa_msa(self._h, *_flatten_sets(sets), C.byref(mp), C.byref(o)))
+        cp = _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
+        if cp is not None:
+            self._chk(lib().hx_poa_msa_convex(self._h, *_flatten_sets(sets), C.byref(cp), int(bool(include_consensus)), C.byref(o)))
+        else:
+            mp = T.PoaMsaParams(match, mismatch, gap_open, gap_open if gap_extend is None else gap_extend, T.POA_TYPES[type], int(bool(include_consensus)))
+            self._chk(lib().hx_poa_msa(self._h, *_flatten_sets(sets), C.byref(mp), C.byref(o)))
         rows, cns = T.msa_to_lists(o)
         st = _counters(o, "rows_kernel_ms", "rows_kernel_bytes")
         lib().hx_free_msa(self._h, C.byref(o))
         return (rows, cns, st) if stats else rows
 
     def poa_weighted(self, sets, weights=None, qualities=None, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=None, coverage=False, profile=False,
-                     stats=False):
+                     stats=False, gap_open2=None, gap_extend2=None):
         """the consensus of every set under per-base weights (spoa's add_alignment with weights or a quality string), and the coverage of
         every consensus base (spoa's generate_consensus(dst)). weights: nested like sets, one integer in 1..255 per base (a list or an integer array per sequence); qualities: nested
         like sets, one string per sequence, weight = character - 33 (spoa's rule); neither: every weight is 1. A sequence adds w[i-1] + w[i]
@@ -366,7 +396,8 @@ class HipContext:
         coverage can be 0); profile=True: per set a list of [A, C, G, T] counts of those sequences by their letter in the column. Returns
         the list of consensus strings when nothing else is asked for, else a tuple (consensus, coverage if asked, profile if asked,
         counters if stats): dp_cells, seq_bases, n_aligned as poa_sequences_affine has them, and cov_kernel_ms / cov_kernel_bytes of the
-        coverage kernels."""
+        coverage kernels. gap_open2 and gap_extend2 (both or neither) switch to the convex gap model of poa_sequences_convex
+        (hx_poa_weighted_convex)."""
         import numpy as np
         _check_type(type)
         if weights is not None and qualities is not None:
@@ -396,8 +427,12 @@ class HipContext:
                     flat += vals.astype(np.uint8).tobytes()
             wbytes = bytes(flat) or b"\0"
         o = T.WcnsOut()
-        wp = T.PoaWeightedParams(match, mismatch, gap_open, gap_open if gap_extend is None else gap_extend, T.POA_TYPES[type], int(bool(coverage)), int(bool(profile)))
-        self._chk(lib().hx_poa_weighted(self._h, *_flatten_sets(sets), wbytes, C.byref(wp), C.byref(o)))
+        cp = _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
+        if cp is not None:
+            self._chk(lib().hx_poa_weighted_convex(self._h, *_flatten_sets(sets), wbytes, C.byref(cp), int(bool(coverage)), int(bool(profile)), C.byref(o)))
+        else:
+            wp = T.PoaWeightedParams(match, mismatch, gap_open, gap_open if gap_extend is None else gap_extend, T.POA_TYPES[type], int(bool(coverage)), int(bool(profile)))
+            self._chk(lib().hx_poa_weighted(self._h, *_flatten_sets(sets), wbytes, C.byref(wp), C.byref(o)))
         cns, cov, prof = T.wcns_to_lists(o)
         st = _counters(o, "cov_kernel_ms", "cov_kernel_bytes")
         lib().hx_free_wcns(self._h, C.byref(o))

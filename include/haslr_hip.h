@@ -59,8 +59,9 @@ void hx_ctx_destroy(hx_ctx*);
  *                    poa_far_rows, poa_ring_zero, poa_slots, poa_slots_pct, poa_batches, poa_force_cm, coords_lds_supp), and two of the
  *                    general POA path (hx_poa_sequences_mode): poa_general (1: HX_POA_NW runs the general path too) and poa_modes_slot_kb (cap of
  *                    its first round of workspace slots, forcing the rerun of sets in larger ones), poa_affine (1: hx_poa_sequences_affine
- *                    with gap_extend == gap_open runs the affine kernel instead of the linear paths), and poa_weighted (1: hx_poa_weighted
- *                    without weights runs the weighted kernels on weights of 1 instead of the unit-weight ones).
+ *                    with gap_extend == gap_open runs the affine kernel instead of the linear paths), poa_weighted (1: hx_poa_weighted
+ *                    without weights runs the weighted kernels on weights of 1 instead of the unit-weight ones), and poa_convex (1: the convex
+ *                    entries with gap_extend2 <= gap_extend run the convex kernel instead of the affine entries).
  *                    Results never depend on any of them. */
 int hx_set_option(hx_ctx*, const char* name, const char* value);
 int hx_get_option(const hx_ctx*, const char* name, double* value);
@@ -128,6 +129,22 @@ int hx_poa_msa(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t
  *                     weights through the weighted instances on weights of 1 (same results). Not pinned against spoa, like the rest of the
  *                     general path: the tests hold it to a CPU restatement of spoa's rule. */
 int hx_poa_weighted(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_weighted_params*, hx_wcns_out* out);
+/*   hx_poa_sequences_convex, hx_poa_msa_convex, hx_poa_weighted_convex  the three entries above under two-piece affine ("convex") gaps (spoa's
+ *                     seven-score engine, minimap2's gap model; DESIGN.md "General POA path", "Convex gaps"): a gap of k bases scores
+ *                     max(gap_open + (k - 1) gap_extend, gap_open2 + (k - 1) gap_extend2), so short gaps pay the first piece and long ones the
+ *                     second. Outputs, weight rules, include_consensus, want_coverage and want_profile are those of hx_poa_sequences_affine,
+ *                     hx_poa_msa and hx_poa_weighted. gap_extend2 <= gap_extend: the second piece never wins, and the call IS the affine-form
+ *                     entry with (gap_open, gap_extend), which sends gap_extend == gap_open on to the linear paths (option poa_convex keeps such
+ *                     a call on the convex kernel instead, same results). Otherwise the convex instances of the general path run: a cell holds
+ *                     H, F and O (12 bytes), sequences of up to 8191 bases; a longer one is an error that names its set. Errors, each naming the
+ *                     score and its value: those of hx_poa_sequences_affine for the first piece, the same three for the second piece
+ *                     (gap_open2 >= 0, gap_extend2 > 0, gap_extend2 < gap_open2), gap_open2 > gap_open, an unknown type. Refused, not
+ *                     reinterpreted. Scores are int32 in this ABI and the matrices are int32 too, with -2^29 as "minus infinity": (nodes of a
+ *                     set + columns) x the largest score magnitude must stay below 2^29, which every int8 score does for every set the path
+ *                     accepts (2^21 nodes, 8 192 columns); larger scores are not checked and can wrap. Not pinned against spoa, like the rest of the general path: the tests hold it to a CPU restatement. */
+int hx_poa_sequences_convex(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_convex_params*, hx_cns_out* out);
+int hx_poa_msa_convex(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_convex_params*, int include_consensus, hx_msa_out* out);
+int hx_poa_weighted_convex(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params*, int want_coverage, int want_profile, hx_wcns_out* out);
 void hx_free_chain(hx_ctx*, hx_chain_out*);
 void hx_free_edges(hx_ctx*, hx_edges_out*);
 void hx_free_coords(hx_ctx*, hx_coords_out*);

@@ -144,6 +144,15 @@ typedef struct {
     int32_t type; /* hx_poa_type */
 } hx_poa_affine_params;
 
+/* hx_poa_sequences_convex, hx_poa_msa_convex, hx_poa_weighted_convex: two-piece affine ("convex") gaps. A gap of k bases scores
+ * max(gap_open + (k - 1) gap_extend, gap_open2 + (k - 1) gap_extend2). Each piece is a valid affine one (open < 0, extend <= 0,
+ * open <= extend), and gap_open2 <= gap_open: the first piece is the one that opens no dearer. gap_extend2 <= gap_extend: the second
+ * piece never wins, the call is the affine one with the first piece. */
+typedef struct {
+    int32_t match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2;
+    int32_t type; /* hx_poa_type */
+} hx_poa_convex_params;
+
 /* hx_poa_msa: hx_poa_sequences_affine's scores and type (gap_extend == gap_open is the linear model), and whether the consensus is
  * the last row of every set. */
 typedef struct {

@@ -17,8 +17,10 @@
 // (-1, ticket) pair, not a list of node/position pairs), add_alignment() appends the sequence that goes with a token,
 // generate_consensus() sends the recorded sequences, in order, through hx_poa_sequences_mode (the engine's alignment type and
 // three scores, linear gap; an engine made with five scores, gap open below gap extend, goes through
-// hx_poa_sequences_affine) and returns what spoa's generate_consensus returns for them. A graph that was given weights or qualities, or
-// is asked for the coverage, goes through hx_poa_weighted instead (below).
+// hx_poa_sequences_affine, an engine made with seven scores - two gap pieces, a gap of k bases scores max(g + (k-1) e, q + (k-1) c) -
+// through hx_poa_sequences_convex) and returns what spoa's generate_consensus returns for them. A graph that was given weights or
+// qualities, or is asked for the coverage, goes through hx_poa_weighted instead (below; hx_poa_weighted_convex under a seven-score engine,
+// as the MSA goes through hx_poa_msa_convex).
 // All three of spoa's alignment types are taken: kNW (global, what the reference uses) runs the tuned global path, kSW (local) and
 // kOV (overlap) the general path of the library (DESIGN.md "General POA path"). What is supported beyond that is the reference's call
 // pattern: every alignment added to the graph it was computed against, in the order it was computed. spoa 1.1.3 exits on invalid input; this header throws std::runtime_error with the
@@ -79,7 +81,7 @@ struct Device {
     hx_ctx* ctx = nullptr;
     std::mutex mu;                    // guards ctx and every call into it
     // flat combining of concurrent generate_consensus() calls
-    struct Request { const std::vector<std::string>* seqs; AlignmentType type; std::int8_t m, n, g, e; std::string result, error; bool done, answered; };   // answered: result or error is final (an empty consensus is a result)
+    struct Request { const std::vector<std::string>* seqs; AlignmentType type; std::int8_t m, n, g, e, q, c; std::string result, error; bool done, answered; };   // answered: result or error is final (an empty consensus is a result)
     std::mutex qmu;
     std::condition_variable qcv;
     std::vector<Request*> queue;
@@ -188,6 +190,32 @@ inline std::vector<std::string> consensus_batch(const std::vector<std::vector<st
     return consensus_batch(detail::pointers(sets), type, m, n, g, e);
 }
 
+// ... with convex gaps: a second piece, gap open q, gap extend c (q <= c <= 0, q <= g); a gap of k bases scores max(g + (k-1) e, q + (k-1) c).
+// c <= e: the second piece never wins, the library takes the affine route. Sequences of up to 8 191 bases otherwise.
+inline std::vector<std::string> consensus_batch(const std::vector<const std::vector<std::string>*>& sets, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e,
+                                                std::int8_t q, std::int8_t c) {
+    if (q == g && c == e) return consensus_batch(sets, type, m, n, g, e);
+    const detail::Flat f(sets);
+    const hx_poa_convex_params cp{m, n, g, e, q, c, static_cast<std::int32_t>(type)};
+    return detail::consensus_call([&](hx_ctx* ctx, hx_cns_out* out) { return hx_poa_sequences_convex(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), &cp, out); });
+}
+inline std::vector<std::string> consensus_batch(const std::vector<std::vector<std::string>>& sets, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e, std::int8_t q,
+                                                std::int8_t c) {
+    return consensus_batch(detail::pointers(sets), type, m, n, g, e, q, c);
+}
+
+namespace detail {
+inline std::vector<std::vector<std::string>> rows_of(const hx_msa_out& out, std::size_t n_sets) {
+    std::vector<std::vector<std::string>> res(n_sets);
+    for (std::size_t i = 0; i < n_sets; i++)
+        for (std::uint32_t r = 0; r < out.n_rows[i]; r++) {
+            const char* p = out.msa + out.msa_off[i] + (std::uint64_t)r * out.n_cols[i];
+            res[i].emplace_back(p, p + out.n_cols[i]);
+        }
+    return res;
+}
+}  // namespace detail
+
 // the multiple sequence alignment of every set in ONE device call (hx_poa_msa): per set one gapped row per sequence, in order, all of
 // the set's column count wide, and with include_consensus the consensus as one more, last row. e == g is the linear gap model. The C-ABI's
 // rule holds here: an empty sequence in a set gives a row of gaps (Graph below never records one, as spoa ignores it).
@@ -197,12 +225,7 @@ inline std::vector<std::vector<std::string>> msa_batch(const std::vector<const s
     const hx_poa_msa_params mp{m, n, g, e, static_cast<std::int32_t>(type), include_consensus ? 1 : 0};
     hx_msa_out out;
     return detail::locked_call([&](hx_ctx* ctx) { return hx_poa_msa(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), &mp, &out); }, [&](hx_ctx* ctx) -> std::vector<std::vector<std::string>> {
-        std::vector<std::vector<std::string>> res(sets.size());
-        for (std::size_t i = 0; i < sets.size(); i++)
-            for (std::uint32_t r = 0; r < out.n_rows[i]; r++) {
-                const char* p = out.msa + out.msa_off[i] + (std::uint64_t)r * out.n_cols[i];
-                res[i].emplace_back(p, p + out.n_cols[i]);
-            }
+        std::vector<std::vector<std::string>> res = detail::rows_of(out, sets.size());
         hx_free_msa(ctx, &out);
         return res;
     });
@@ -210,6 +233,23 @@ inline std::vector<std::vector<std::string>> msa_batch(const std::vector<const s
 inline std::vector<std::vector<std::string>> msa_batch(const std::vector<std::vector<std::string>>& sets, AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8,
                                                        std::int8_t e = -8, bool include_consensus = false) {
     return msa_batch(detail::pointers(sets), type, m, n, g, e, include_consensus);
+}
+// ... with convex gaps (hx_poa_msa_convex): all six scores are given
+inline std::vector<std::vector<std::string>> msa_batch(const std::vector<const std::vector<std::string>*>& sets, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e,
+                                                       std::int8_t q, std::int8_t c, bool include_consensus = false) {
+    const detail::Flat f(sets);
+    const hx_poa_convex_params cp{m, n, g, e, q, c, static_cast<std::int32_t>(type)};
+    hx_msa_out out;
+    return detail::locked_call([&](hx_ctx* ctx) { return hx_poa_msa_convex(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), &cp, include_consensus ? 1 : 0, &out); },
+                               [&](hx_ctx* ctx) -> std::vector<std::vector<std::string>> {
+        std::vector<std::vector<std::string>> res = detail::rows_of(out, sets.size());
+        hx_free_msa(ctx, &out);
+        return res;
+    });
+}
+inline std::vector<std::vector<std::string>> msa_batch(const std::vector<std::vector<std::string>>& sets, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e, std::int8_t q,
+                                                       std::int8_t c, bool include_consensus = false) {
+    return msa_batch(detail::pointers(sets), type, m, n, g, e, q, c, include_consensus);
 }
 
 // the consensus of every set under per-base weights in ONE device call (hx_poa_weighted), with the coverage of every consensus base and
@@ -220,8 +260,10 @@ struct Weighted {
     std::vector<std::vector<std::uint32_t>> coverage;   // per set, one per consensus base (empty unless asked for)
     std::vector<std::vector<std::uint32_t>> profile;    // per set, four per consensus base (empty unless asked for)
 };
-inline Weighted weighted_batch(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights,
-                               AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, bool coverage = true, bool profile = false) {
+namespace detail {
+// the flattening of the weights, the call and the outputs of both weighted_batch forms: call(ctx, flat sets, weights or null, &out)
+template <class Call>
+Weighted weighted_call(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights, bool coverage, bool profile, Call call) {
     if (!weights.empty() && weights.size() != sets.size()) throw std::invalid_argument("spoa_hx: weighted_batch needs one set of weights per set of sequences, or none");
     const detail::Flat f(sets);
     std::vector<std::uint8_t> w;
@@ -235,9 +277,8 @@ inline Weighted weighted_batch(const std::vector<const std::vector<std::string>*
         }
     }
     if (!weights.empty() && w.empty()) w.push_back(1);   // (no base at all: a pointer that is not null, nothing behind it is read)
-    const hx_poa_weighted_params wp{m, n, g, e, static_cast<std::int32_t>(type), coverage ? 1 : 0, profile ? 1 : 0};
     hx_wcns_out out;
-    return detail::locked_call([&](hx_ctx* ctx) { return hx_poa_weighted(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), weights.empty() ? nullptr : w.data(), &wp, &out); }, [&](hx_ctx* ctx) -> Weighted {
+    return locked_call([&](hx_ctx* ctx) { return call(ctx, f, weights.empty() ? nullptr : w.data(), &out); }, [&](hx_ctx* ctx) -> Weighted {
         Weighted res;
         res.consensus.resize(sets.size());
         if (coverage) res.coverage.resize(sets.size());
@@ -251,19 +292,43 @@ inline Weighted weighted_batch(const std::vector<const std::vector<std::string>*
         return res;
     });
 }
+inline std::vector<const std::vector<std::vector<std::uint8_t>>*> pointers(const std::vector<std::vector<std::vector<std::uint8_t>>>& weights) {
+    std::vector<const std::vector<std::vector<std::uint8_t>>*> p;
+    for (const auto& ws : weights) p.push_back(&ws);
+    return p;
+}
+}  // namespace detail
+inline Weighted weighted_batch(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights,
+                               AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, bool coverage = true, bool profile = false) {
+    const hx_poa_weighted_params wp{m, n, g, e, static_cast<std::int32_t>(type), coverage ? 1 : 0, profile ? 1 : 0};
+    return detail::weighted_call(sets, weights, coverage, profile, [&](hx_ctx* ctx, const detail::Flat& f, const std::uint8_t* w, hx_wcns_out* out) {
+        return hx_poa_weighted(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), w, &wp, out);
+    });
+}
 inline Weighted weighted_batch(const std::vector<std::vector<std::string>>& sets, const std::vector<std::vector<std::vector<std::uint8_t>>>& weights, AlignmentType type,
                                std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, bool coverage = true, bool profile = false) {
-    std::vector<const std::vector<std::vector<std::uint8_t>>*> q;
-    for (const auto& ws : weights) q.push_back(&ws);
-    return weighted_batch(detail::pointers(sets), q, type, m, n, g, e, coverage, profile);
+    return weighted_batch(detail::pointers(sets), detail::pointers(weights), type, m, n, g, e, coverage, profile);
+}
+// ... with convex gaps (hx_poa_weighted_convex): all six scores and both flags are given (no defaults: a call of nine arguments stays the
+// affine form above)
+inline Weighted weighted_batch(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights,
+                               AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e, std::int8_t q, std::int8_t c, bool coverage, bool profile) {
+    const hx_poa_convex_params cp{m, n, g, e, q, c, static_cast<std::int32_t>(type)};
+    return detail::weighted_call(sets, weights, coverage, profile, [&](hx_ctx* ctx, const detail::Flat& f, const std::uint8_t* w, hx_wcns_out* out) {
+        return hx_poa_weighted_convex(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), w, &cp, coverage ? 1 : 0, profile ? 1 : 0, out);
+    });
+}
+inline Weighted weighted_batch(const std::vector<std::vector<std::string>>& sets, const std::vector<std::vector<std::vector<std::uint8_t>>>& weights, AlignmentType type,
+                               std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e, std::int8_t q, std::int8_t c, bool coverage, bool profile) {
+    return weighted_batch(detail::pointers(sets), detail::pointers(weights), type, m, n, g, e, q, c, coverage, profile);
 }
 
 // one set on behalf of one caller thread, combined with whatever other threads have queued (see "Threads" above)
-inline std::string consensus_combined(const std::vector<std::string>& seqs, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) {
+inline std::string consensus_combined(const std::vector<std::string>& seqs, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e, std::int8_t q, std::int8_t c) {
     Device& d = device();
     static const long window_us = std::getenv("HASLR_SPOA_BATCH_US") ? std::atol(std::getenv("HASLR_SPOA_BATCH_US")) : 200;
     static const std::size_t batch_max = std::getenv("HASLR_SPOA_BATCH") ? (std::size_t)std::max(1L, std::atol(std::getenv("HASLR_SPOA_BATCH"))) : 256;
-    Device::Request me{&seqs, type, m, n, g, e, std::string(), std::string(), false, false};
+    Device::Request me{&seqs, type, m, n, g, e, q, c, std::string(), std::string(), false, false};
     std::unique_lock<std::mutex> lk(d.qmu);
     d.queue.push_back(&me);
     d.arrivals++;
@@ -286,7 +351,7 @@ inline std::string consensus_combined(const std::vector<std::string>& seqs, Alig
             if (batch.size() > batch_max) { d.queue.assign(batch.begin() + (std::ptrdiff_t)batch_max, batch.end()); batch.resize(batch_max); }
             d.arrivals = d.queue.size();                           // arrivals from here on = company for the next submitter
             lk.unlock();
-            // one device call per (alignment type, four scores) in the batch (the reference uses one of each)
+            // one device call per (alignment type, six scores) in the batch (the reference uses one of each)
             std::vector<char> served(batch.size(), 0);
             std::uint64_t calls = 0;
             for (std::size_t i = 0; i < batch.size(); i++) {
@@ -294,9 +359,9 @@ inline std::string consensus_combined(const std::vector<std::string>& seqs, Alig
                 std::vector<std::size_t> idx;
                 std::vector<const std::vector<std::string>*> sets;
                 for (std::size_t j = i; j < batch.size(); j++)
-                    if (!served[j] && batch[j]->type == batch[i]->type && batch[j]->m == batch[i]->m && batch[j]->n == batch[i]->n && batch[j]->g == batch[i]->g && batch[j]->e == batch[i]->e) { idx.push_back(j); sets.push_back(batch[j]->seqs); served[j] = 1; }
+                    if (!served[j] && batch[j]->type == batch[i]->type && batch[j]->m == batch[i]->m && batch[j]->n == batch[i]->n && batch[j]->g == batch[i]->g && batch[j]->e == batch[i]->e && batch[j]->q == batch[i]->q && batch[j]->c == batch[i]->c) { idx.push_back(j); sets.push_back(batch[j]->seqs); served[j] = 1; }
                 try {
-                    std::vector<std::string> res = consensus_batch(sets, batch[i]->type, batch[i]->m, batch[i]->n, batch[i]->g, batch[i]->e);
+                    std::vector<std::string> res = consensus_batch(sets, batch[i]->type, batch[i]->m, batch[i]->n, batch[i]->g, batch[i]->e, batch[i]->q, batch[i]->c);
                     for (std::size_t q = 0; q < idx.size(); q++) { batch[idx[q]]->result.swap(res[q]); batch[idx[q]]->answered = true; }
                     calls++;
                 } catch (const std::exception& e) {
@@ -309,7 +374,7 @@ inline std::string consensus_combined(const std::vector<std::string>& seqs, Alig
                         for (std::size_t q = 0; q < idx.size(); q++) {
                             Device::Request* r = batch[idx[q]];
                             if (same >= 2) { r->error = group_error; r->answered = true; continue; }
-                            try { r->result = consensus_batch(std::vector<const std::vector<std::string>*>{sets[q]}, batch[i]->type, batch[i]->m, batch[i]->n, batch[i]->g, batch[i]->e)[0]; same = 0; }
+                            try { r->result = consensus_batch(std::vector<const std::vector<std::string>*>{sets[q]}, batch[i]->type, batch[i]->m, batch[i]->n, batch[i]->g, batch[i]->e, batch[i]->q, batch[i]->c)[0]; same = 0; }
                             catch (const std::exception& e1) { r->error = e1.what(); same = r->error == group_error ? same + 1 : 0; }
                             r->answered = true;
                             calls++;
@@ -341,6 +406,9 @@ inline std::string consensus_combined(const std::vector<std::string>& seqs, Alig
     return me.result;
 }
 
+inline std::string consensus_combined(const std::vector<std::string>& seqs, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) {
+    return consensus_combined(seqs, type, m, n, g, e, g, e);   // one gap piece
+}
 inline std::string consensus_combined(const std::vector<std::string>& seqs, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g) {
     return consensus_combined(seqs, type, m, n, g, g);   // linear gap
 }
@@ -378,16 +446,14 @@ public:
     // spoa::Graph::generate_consensus()
     std::string generate_consensus() {
         if (sequences_.empty()) return std::string();
-        if (!weighted_) return hx::consensus_combined(sequences_, type_, m_, n_, g_, e_);
-        return hx::weighted_batch(std::vector<const std::vector<std::string>*>{&sequences_}, std::vector<const std::vector<std::vector<std::uint8_t>>*>{&weights_}, type_, m_, n_, g_, e_, false, false).consensus[0];
+        if (!weighted_) return hx::consensus_combined(sequences_, type_, m_, n_, g_, e_, q_, c_);
+        return weighted(true, false).consensus[0];
     }
     // spoa::Graph::generate_consensus(dst): dst is replaced by the coverage of every consensus base. A device call of its own.
     std::string generate_consensus(std::vector<std::uint32_t>& dst) {
         dst.clear();
         if (sequences_.empty()) return std::string();
-        hx::Weighted r = hx::weighted_batch(std::vector<const std::vector<std::string>*>{&sequences_},
-                                            weighted_ ? std::vector<const std::vector<std::vector<std::uint8_t>>*>{&weights_} : std::vector<const std::vector<std::vector<std::uint8_t>>*>{},
-                                            type_, m_, n_, g_, e_, true, false);
+        hx::Weighted r = weighted(weighted_, true);
         dst.swap(r.coverage[0]);
         return r.consensus[0];
     }
@@ -396,11 +462,19 @@ public:
     void generate_multiple_sequence_alignment(std::vector<std::string>& dst, bool include_consensus = false) {
         dst.clear();
         if (sequences_.empty()) return;
-        dst = std::move(hx::msa_batch(std::vector<const std::vector<std::string>*>{&sequences_}, type_, m_, n_, g_, e_, include_consensus)[0]);
+        const std::vector<const std::vector<std::string>*> one{&sequences_};
+        dst = std::move((convex() ? hx::msa_batch(one, type_, m_, n_, g_, e_, q_, c_, include_consensus) : hx::msa_batch(one, type_, m_, n_, g_, e_, include_consensus))[0]);
     }
 
 private:
     friend class AlignmentEngine;
+    bool convex() const { return q_ != g_ || c_ != e_; }   // a seven-score engine whose second piece is not the first again
+    // this graph's one set through the weighted entry of its gap model (with its weights, or on unit weights)
+    hx::Weighted weighted(bool with_weights, bool coverage) const {
+        const std::vector<const std::vector<std::string>*> one{&sequences_};
+        const std::vector<const std::vector<std::vector<std::uint8_t>>*> w = with_weights ? std::vector<const std::vector<std::vector<std::uint8_t>>*>{&weights_} : std::vector<const std::vector<std::vector<std::uint8_t>>*>{};
+        return convex() ? hx::weighted_batch(one, w, type_, m_, n_, g_, e_, q_, c_, coverage, false) : hx::weighted_batch(one, w, type_, m_, n_, g_, e_, coverage, false);
+    }
     void record(const Alignment& alignment, const std::string& sequence, const std::vector<std::uint8_t>& w) {
         if (alignment.size() != 1 || alignment[0].first != -1 || (std::uint32_t)alignment[0].second != ticket_)
             throw std::invalid_argument("spoa_hx: add_alignment needs the alignment that align_sequence_with_graph last returned for this graph");
@@ -415,30 +489,31 @@ private:
     bool weighted_ = false;                            // some base has another weight than 1
     std::uint32_t ticket_ = 0;
     AlignmentType type_ = AlignmentType::kNW;
-    std::int8_t m_ = 5, n_ = -4, g_ = -8, e_ = -8;
+    std::int8_t m_ = 5, n_ = -4, g_ = -8, e_ = -8, q_ = -8, c_ = -8;   // (q, c) == (g, e): one gap piece
 };
 
 class AlignmentEngine {
 public:
     // spoa::AlignmentEngine::align_sequence_with_graph(sequence, graph): a token for add_alignment (see the header comment)
     Alignment align_sequence_with_graph(const std::string& /*sequence*/, const std::unique_ptr<Graph>& graph) {
-        graph->type_ = type_; graph->m_ = m_; graph->n_ = n_; graph->g_ = g_; graph->e_ = e_;
+        graph->type_ = type_; graph->m_ = m_; graph->n_ = n_; graph->g_ = g_; graph->e_ = e_; graph->q_ = q_; graph->c_ = c_;
         return Alignment{{-1, (std::int32_t)graph->ticket_}};
     }
 
 private:
     friend std::unique_ptr<AlignmentEngine> createAlignmentEngine(AlignmentType, std::int8_t, std::int8_t, std::int8_t);
     friend std::unique_ptr<AlignmentEngine> createAlignmentEngine(AlignmentType, std::int8_t, std::int8_t, std::int8_t, std::int8_t);
-    AlignmentEngine(AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e) : type_(type), m_(m), n_(n), g_(g), e_(e) {}
+    friend std::unique_ptr<AlignmentEngine> createAlignmentEngine(AlignmentType, std::int8_t, std::int8_t, std::int8_t, std::int8_t, std::int8_t, std::int8_t);
+    AlignmentEngine(AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e, std::int8_t q, std::int8_t c) : type_(type), m_(m), n_(n), g_(g), e_(e), q_(q), c_(c) {}
     AlignmentType type_;
-    std::int8_t m_, n_, g_, e_;
+    std::int8_t m_, n_, g_, e_, q_, c_;
 };
 
 // spoa::createAlignmentEngine(type, match, mismatch, gap) — linear gap penalties, as spoa 1.1.3 has them
 inline std::unique_ptr<AlignmentEngine> createAlignmentEngine(AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g) {
     if (type != AlignmentType::kSW && type != AlignmentType::kNW && type != AlignmentType::kOV) throw std::invalid_argument("spoa_hx: unknown AlignmentType");
     if (g >= 0) throw std::invalid_argument("spoa_hx: the gap penalty must be negative");
-    return std::unique_ptr<AlignmentEngine>(new AlignmentEngine(type, m, n, g, g));
+    return std::unique_ptr<AlignmentEngine>(new AlignmentEngine(type, m, n, g, g, g, g));
 }
 // spoa::createAlignmentEngine(type, match, mismatch, gap_open, gap_extend) — affine gap penalties: a gap of k bases costs g + (k - 1) e.
 // e == g is the linear engine above. e < g is refused: what spoa does with such scores cannot be checked here, so nothing is guessed.
@@ -447,7 +522,23 @@ inline std::unique_ptr<AlignmentEngine> createAlignmentEngine(AlignmentType type
     if (g >= 0) throw std::invalid_argument("spoa_hx: the gap open penalty must be negative");
     if (e > 0) throw std::invalid_argument("spoa_hx: the gap extend penalty must not be positive");
     if (e < g) throw std::invalid_argument("spoa_hx: the gap extend penalty must not be below the gap open penalty");
-    return std::unique_ptr<AlignmentEngine>(new AlignmentEngine(type, m, n, g, e));
+    return std::unique_ptr<AlignmentEngine>(new AlignmentEngine(type, m, n, g, e, g, e));
+}
+// spoa::createAlignmentEngine(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2) - two-piece affine (convex) gap
+// penalties: a gap of k bases costs max(g + (k - 1) e, q + (k - 1) c). Each piece is a valid affine one and q <= g (the first piece is the
+// one that opens no dearer); anything else is refused, not reinterpreted. c <= e: the second piece never wins, the engine is the
+// five-score one with (g, e).
+inline std::unique_ptr<AlignmentEngine> createAlignmentEngine(AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e, std::int8_t q, std::int8_t c) {
+    if (type != AlignmentType::kSW && type != AlignmentType::kNW && type != AlignmentType::kOV) throw std::invalid_argument("spoa_hx: unknown AlignmentType");
+    if (g >= 0) throw std::invalid_argument("spoa_hx: the gap open penalty must be negative, not " + std::to_string((int)g));
+    if (e > 0) throw std::invalid_argument("spoa_hx: the gap extend penalty must not be positive, not " + std::to_string((int)e));
+    if (e < g) throw std::invalid_argument("spoa_hx: the gap extend penalty " + std::to_string((int)e) + " must not be below the gap open penalty " + std::to_string((int)g));
+    if (q >= 0) throw std::invalid_argument("spoa_hx: the second gap open penalty must be negative, not " + std::to_string((int)q));
+    if (c > 0) throw std::invalid_argument("spoa_hx: the second gap extend penalty must not be positive, not " + std::to_string((int)c));
+    if (c < q) throw std::invalid_argument("spoa_hx: the second gap extend penalty " + std::to_string((int)c) + " must not be below the second gap open penalty " + std::to_string((int)q));
+    if (q > g) throw std::invalid_argument("spoa_hx: the second gap open penalty " + std::to_string((int)q) + " must not be above the first gap open penalty " + std::to_string((int)g));
+    if (c <= e) return std::unique_ptr<AlignmentEngine>(new AlignmentEngine(type, m, n, g, e, g, e));
+    return std::unique_ptr<AlignmentEngine>(new AlignmentEngine(type, m, n, g, e, q, c));
 }
 inline std::unique_ptr<Graph> createGraph() { return std::unique_ptr<Graph>(new Graph()); }
 

@@ -3,12 +3,18 @@
 // network): a maintainer builds it on any networked machine against a genuine libspoa.a and commits the JSON it prints.
 //
 //   g++ -O2 -std=c++11 -I<spoa>/include make_spoa_vectors.cpp <spoa>/build/lib/libspoa.a -o make_spoa_vectors
-//   ./make_spoa_vectors [match mismatch gap [type [gap_extend]]] < sequences.txt > tests/golden/spoa/<name>.json
+//   ./make_spoa_vectors [match mismatch gap [type [gap_extend [gap_open2 gap_extend2]]]] < sequences.txt > tests/golden/spoa/<name>.json
 //
 // type: sw, nw or ov (spoa::AlignmentType kSW / kNW / kOV; default nw, the reference's). Vectors of the other two types pin the
 // general POA path (hx_poa_sequences_mode, DESIGN.md "General POA path"): they go to tests/golden/spoa_modes/<type>_<name>.json.
 // With a gap_extend the engine is spoa's five-score one (gap = gap open; affine gaps, hx_poa_sequences_affine): those vectors go to
 // tests/golden/spoa_affine/<type>_<name>.json and carry "gap_extend".
+// With gap_open2 and gap_extend2 as well the engine is the seven-score one (two gap pieces, convex gaps: hx_poa_sequences_convex,
+// DESIGN.md "Convex gaps"). spoa 1.1.3 has no such engine, so that call is compiled only with -DSPOA_HAS_CONVEX=\"<version>\" against a
+// later spoa that has createAlignmentEngine(type, m, n, g, e, q, c); the version given is what the vectors carry as "spoa_version". Without
+// the macro the tool builds against 1.1.3 as before and refuses the two extra scores. Those vectors go to
+// tests/golden/spoa_convex/<type>_<name>.json and carry "gap_open2" and "gap_extend2" too; tests/test_spoa_convex_golden.py picks them
+// up. Nothing is committed into that directory yet.
 // A sequence line may carry weights after a blank: "ACGT q IIII" (a quality string: add_alignment(alignment, sequence, quality)) or
 // "ACGT v 3,1,40,2" (a vector of weights: add_alignment(alignment, sequence, weights)). Vectors of a run in which some line does pin base
 // weights and coverage (hx_poa_weighted, DESIGN.md "Base weights and coverage"): they go to tests/golden/spoa_weighted/<type>_<name>.json
@@ -29,8 +35,15 @@
 
 struct Weights { char how = 0; std::string quality; std::vector<uint32_t> values; };   // how: 0 (none), 'q' or 'v'
 
-static std::string consensus_of(const std::vector<std::string>& seqs, const std::vector<Weights>& wts, int type, int m, int n, int g, bool affine, int e, std::vector<uint32_t>* coverage) {
-    auto engine = affine ? spoa::createAlignmentEngine(static_cast<spoa::AlignmentType>(type), (int8_t)m, (int8_t)n, (int8_t)g, (int8_t)e)
+static std::string consensus_of(const std::vector<std::string>& seqs, const std::vector<Weights>& wts, int type, int m, int n, int g, bool affine, int e, bool convex, int q, int c, std::vector<uint32_t>* coverage) {
+#ifdef SPOA_HAS_CONVEX
+    auto engine = convex ? spoa::createAlignmentEngine(static_cast<spoa::AlignmentType>(type), (int8_t)m, (int8_t)n, (int8_t)g, (int8_t)e, (int8_t)q, (int8_t)c)
+                  : affine ?
+#else
+    (void)convex; (void)q; (void)c;   // (main has refused them)
+    auto engine = affine ?
+#endif
+                   spoa::createAlignmentEngine(static_cast<spoa::AlignmentType>(type), (int8_t)m, (int8_t)n, (int8_t)g, (int8_t)e)
                          : spoa::createAlignmentEngine(static_cast<spoa::AlignmentType>(type), (int8_t)m, (int8_t)n, (int8_t)g);
     auto graph = spoa::createGraph();
     size_t used = 0;
@@ -54,6 +67,15 @@ int main(int argc, char** argv) {
     if (type < 0) { fprintf(stderr, "unknown alignment type '%s' (sw, nw, ov)\n", tname.c_str()); return 2; }
     const bool affine = argc > 5;
     const int e = affine ? atoi(argv[5]) : g;
+    if (argc == 7) { fprintf(stderr, "gap_open2 needs gap_extend2 (the second gap piece is two scores)\n"); return 2; }
+    const bool convex = argc > 7;
+#ifdef SPOA_HAS_CONVEX
+    const char* version = convex ? SPOA_HAS_CONVEX : "1.1.3";
+#else
+    const char* version = "1.1.3";
+    if (convex) { fprintf(stderr, "built without -DSPOA_HAS_CONVEX: spoa 1.1.3 has no seven-score engine\n"); return 2; }
+#endif
+    const int q = convex ? atoi(argv[6]) : g, c = convex ? atoi(argv[7]) : e;
     const char* algo[3] = {"kSW", "kNW", "kOV"};
     std::vector<std::pair<std::string, std::vector<std::string>>> cases;
     std::vector<std::vector<Weights>> weights;   // parallel to cases
@@ -74,8 +96,9 @@ int main(int argc, char** argv) {
             weights.back().push_back(w);
         }
     }
-    printf("{\"spoa_version\": \"1.1.3\", \"match\": %d, \"mismatch\": %d, \"gap\": %d, ", m, n, g);
+    printf("{\"spoa_version\": \"%s\", \"match\": %d, \"mismatch\": %d, \"gap\": %d, ", version, m, n, g);
     if (affine) printf("\"gap_extend\": %d, ", e);
+    if (convex) printf("\"gap_open2\": %d, \"gap_extend2\": %d, ", q, c);
     printf("\"algorithm\": \"%s\",\n \"cases\": [", algo[type]);
     for (size_t i = 0; i < cases.size(); i++) {
         printf("%s\n  {\"name\": \"%s\", \"sequences\": [", i ? "," : "", cases[i].first.c_str());
@@ -91,7 +114,7 @@ int main(int argc, char** argv) {
             }
         }
         std::vector<uint32_t> coverage;
-        const std::string cns = consensus_of(cases[i].second, weights[i], type, m, n, g, affine, e, weighted ? &coverage : nullptr);
+        const std::string cns = consensus_of(cases[i].second, weights[i], type, m, n, g, affine, e, convex, q, c, weighted ? &coverage : nullptr);
         printf("], \"consensus\": \"%s\"", cns.c_str());
         if (weighted) {
             printf(", \"coverage\": [");

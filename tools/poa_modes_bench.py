@@ -14,7 +14,12 @@ smallest and largest ratio the repeats allow), the kernel that writes the row te
 move = text + 4 per base read, GB/s), and the sample compared with the MSA restatement (tests/poa_msa_ref.cpp). And every row runs the
 weighted entry on the same sets (hx_poa_weighted, linear scores, seeded quality-like weights in 1..60, with coverage and profile): kernel
 time against the consensus-only general path ("over_general", as for the MSA), the coverage kernels on their own (time by device events,
-the bytes they have to move, GB/s), and the sample compared with the weighted restatement (tests/poa_weighted_ref.cpp). Prints one JSON line."""
+the bytes they have to move, GB/s), and the sample compared with the weighted restatement (tests/poa_weighted_ref.cpp). And every row runs
+the convex kernel on the same sets (hx_poa_sequences_convex with --convex-scores, default 5 -4 -8 -6 -10 -4): same figures, the convex /
+affine and convex / linear ratios of the median kernel times with the smallest and largest ratio the repeats allow, and every sampled set
+compared with the convex restatement (tests/poa_convex_ref.cpp). --only picks the parts to run; --package-root runs the parts another
+build of the package has (a checkout of the parent commit, say) in the same way, for a comparison on one machine. Prints one JSON line,
+and writes it to --out when given."""
 import argparse
 import json
 import os
@@ -29,6 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+PARTS = ["general", "tuned_nw", "cpu", "affine", "outputs", "convex"]   # outputs: the MSA and the weighted entry
 
 
 def text(a):
@@ -75,6 +81,11 @@ def workload_b(rng, n_sets):
     return sets
 
 
+def note(*what):
+    """progress on stderr: a row takes minutes, and stdout carries the one JSON line"""
+    print("[poa_modes_bench]", *what, file=sys.stderr, flush=True)
+
+
 def gpu_time(ctx, fn, repeats):
     fn()   # warm-up (workspace allocation, code objects)
     ms = []
@@ -93,28 +104,39 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=32, help="sets of each workload the CPU restatement runs (16 threads)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--affine-scores", type=int, nargs=4, default=[5, -4, -8, -6], metavar=("M", "N", "G", "E"), help="match, mismatch, gap open, gap extend of the affine rows")
+    ap.add_argument("--convex-scores", type=int, nargs=6, default=[5, -4, -8, -6, -10, -4], metavar=("M", "N", "G", "E", "Q", "C"), help="match, mismatch and the two gap pieces of the convex rows")
+    ap.add_argument("--only", nargs="+", default=PARTS, choices=PARTS, help="the parts of every row to run (outputs: the MSA and the weighted entry, which need general; ratios are given against the parts that ran)")
+    ap.add_argument("--package-root", default=ROOT, help="the tree whose built haslr_amd package runs (default: this one); parts it does not have are left out")
+    ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.package_root))
     from haslr_amd import hip
+    import cvxlib
     import msalib
     import parlib
     import pmrlib
     import wgtlib
+    only = set(a.only)
+    if not hasattr(hip.HipContext, "poa_sequences_convex"):
+        only.discard("convex")
     rng = np.random.default_rng(a.seed)
     loads = {"a_sw": ("sw", workload_a(rng, a.sets_a, True)), "a_nw": ("nw", workload_a(rng, a.sets_a, False))}
     loads["a_ov"] = ("ov", loads["a_nw"][1])
     loads["b_ov"] = ("ov", workload_b(rng, a.sets_b))
     ctx = hip.HipContext(0)
-    res = {"tool": "poa_modes_bench", "seed": a.seed, "repeats": a.repeats, "affine_scores": list(a.affine_scores)}
+    res = {"tool": "poa_modes_bench", "seed": a.seed, "repeats": a.repeats, "affine_scores": list(a.affine_scores), "convex_scores": list(a.convex_scores), "parts": [p for p in PARTS if p in only]}
     with tempfile.TemporaryDirectory() as d:
         ref = pmrlib.ModesRef(d)
         aref = parlib.AffineRef(d)
         mref = msalib.MsaRef(d)
         wref = wgtlib.WeightedRef(d)
+        cref = cvxlib.ConvexRef(d)
         wrng = np.random.default_rng(a.seed + 1000)   # (a generator of its own: the workloads are those of the earlier lines)
         for name, (mode, sets) in loads.items():
             r = {"mode": mode, "sets": len(sets)}
+            note(name, "sets", len(sets))
             for path, opts in (("general", {"poa_general": 1}), ("tuned_nw", {})):
-                if path == "tuned_nw" and mode != "nw":
+                if (path == "tuned_nw" and mode != "nw") or path not in only:
                     continue
                 with ctx.options(**opts):
                     cells = ctx.poa_sequences_mode(sets, mode, stats=True)[1]["dp_cells"]
@@ -122,23 +144,48 @@ def main():
                 med = float(np.median(ms))
                 r[path] = {"cells": int(cells), "kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
                            "gcups": round(cells / med / 1e6, 2)}
+                note(name, path, r[path]["kernel_ms_median"], "ms")
             sample = sets[:a.cpu_sample]
-            t0 = time.perf_counter()
-            with ThreadPoolExecutor(16) as ex:
-                out = list(ex.map(lambda st: ref.consensus_cells(st, mode), sample))
-            dt = time.perf_counter() - t0
-            sc = sum(c for _, c in out)
-            r["cpu_restatement_16t"] = {"sets": len(sample), "cells": int(sc), "s": round(dt, 2), "gcups": round(sc / dt / 1e9, 3)}
-            got = ctx.poa_sequences_mode(sample, mode)
-            r["sample_equal"] = got == [c for c, _ in out]
-            cells = ctx.poa_sequences_affine(sets, mode, *a.affine_scores, stats=True)[1]["dp_cells"]
-            ms = gpu_time(ctx, lambda: ctx.poa_sequences_affine(sets, mode, *a.affine_scores), a.repeats)
-            med = float(np.median(ms))
-            r["affine"] = {"cells": int(cells), "kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
-                           "gcups": round(cells / med / 1e6, 2), "over_linear": round(med / r["general"]["kernel_ms_median"], 3)}
-            with ThreadPoolExecutor(16) as ex:
-                out = list(ex.map(lambda st: aref.consensus(st, mode, *a.affine_scores), sample))
-            r["affine_sample_equal"] = ctx.poa_sequences_affine(sample, mode, *a.affine_scores) == out
+            if "cpu" in only:
+                t0 = time.perf_counter()
+                with ThreadPoolExecutor(16) as ex:
+                    out = list(ex.map(lambda st: ref.consensus_cells(st, mode), sample))
+                dt = time.perf_counter() - t0
+                sc = sum(c for _, c in out)
+                r["cpu_restatement_16t"] = {"sets": len(sample), "cells": int(sc), "s": round(dt, 2), "gcups": round(sc / dt / 1e9, 3)}
+                got = ctx.poa_sequences_mode(sample, mode)
+                r["sample_equal"] = got == [c for c, _ in out]
+            if "affine" in only:
+                cells = ctx.poa_sequences_affine(sets, mode, *a.affine_scores, stats=True)[1]["dp_cells"]
+                ms = gpu_time(ctx, lambda: ctx.poa_sequences_affine(sets, mode, *a.affine_scores), a.repeats)
+                med = float(np.median(ms))
+                r["affine"] = {"cells": int(cells), "kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
+                               "gcups": round(cells / med / 1e6, 2)}
+                if "general" in r:
+                    r["affine"]["over_linear"] = round(med / r["general"]["kernel_ms_median"], 3)
+                with ThreadPoolExecutor(16) as ex:
+                    out = list(ex.map(lambda st: aref.consensus(st, mode, *a.affine_scores), sample))
+                r["affine_sample_equal"] = ctx.poa_sequences_affine(sample, mode, *a.affine_scores) == out
+                note(name, "affine", r["affine"]["kernel_ms_median"], "ms")
+            if "convex" in only:
+                cells = ctx.poa_sequences_convex(sets, mode, *a.convex_scores, stats=True)[1]["dp_cells"]
+                ms = gpu_time(ctx, lambda: ctx.poa_sequences_convex(sets, mode, *a.convex_scores), a.repeats)
+                med = float(np.median(ms))
+                r["convex"] = {"cells": int(cells), "kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
+                               "gcups": round(cells / med / 1e6, 2)}
+                for key, base in (("over_affine", r.get("affine")), ("over_linear", r.get("general"))):
+                    if base:
+                        r["convex"].update({key: round(med / base["kernel_ms_median"], 3), key + "_min": round(min(ms) / base["kernel_ms_max"], 3),
+                                            key + "_max": round(max(ms) / base["kernel_ms_min"], 3)})
+                with ThreadPoolExecutor(16) as ex:
+                    out = list(ex.map(lambda st: cref.consensus(st, mode, tuple(a.convex_scores)), sample))
+                got = ctx.poa_sequences_convex(sample, mode, *a.convex_scores)
+                r["convex_sample_equal"] = got == out
+                r["convex_sample_differing_sets"] = [k for k in range(len(sample)) if got[k] != out[k]]
+                note(name, "convex", r["convex"]["kernel_ms_median"], "ms")
+            if "outputs" not in only or "general" not in r:
+                res[name] = r
+                continue
             rows_ms, moved = [], 0
 
             def msa_call():
@@ -182,6 +229,9 @@ def main():
             res[name] = r
     ctx.close()
     print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res) + "\n")
 
 
 if __name__ == "__main__":
