@@ -157,8 +157,8 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     G g; uint32_t *path, *colref;
     const uint64_t pools = carve_pools(slot, S.sum_len, S.nseq, S.lmax, &g, &path, &colref);
     if (pools > a.slot_bytes) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
-    int32_t* H = (int32_t*)(slot + pools);
-    const uint64_t hcap = (a.slot_bytes - pools) / (GM == GM_CONVEX ? 12 : GM == GM_AFFINE ? 8 : 4);   // cells the slot holds (affine: an (H, F) pair each; convex: (H, F, O))
+    Cell<GM>* H = (Cell<GM>*)(slot + pools);
+    const uint64_t hcap = (a.slot_bytes - pools) / sizeof(Cell<GM>);   // cells the slot holds
     uint32_t V = 0, E = 0, non_empty = 0;
     unsigned long long cells = 0;
     for (uint32_t k = 0; k < S.nseq; k++) {
@@ -172,16 +172,8 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
             if ((uint64_t)(V + 1) * (L + 1) > hcap) { if (t == 0) { a.status[set] = MS_H_OVERFLOW; a.vseen[set] = V; } return; }
             cells += (unsigned long long)V * L;
             uint32_t bi, bj;
-            if (GM == GM_CONVEX) {
-                dp_rows_convex<NT, CPL>(g, (Cell3*)H, V, s, L, a, sh, s_wtot, &bi, &bj);
-                if (t == 0 && bi) na = traceback_convex(g, (const Cell3*)H, s, L, bi, bj, a);
-            } else if (GM == GM_AFFINE) {
-                dp_rows_affine<NT, CPL>(g, (int2*)H, V, s, L, a, sh, s_wtot, &bi, &bj);
-                if (t == 0 && bi) na = traceback_affine(g, (const int2*)H, s, L, bi, bj, a);
-            } else {
-                dp_rows<NT, CPL>(g, H, V, s, L, a, sh, s_wtot, &bi, &bj);
-                if (t == 0 && bi) na = traceback(g, H, s, L, bi, bj, a);
-            }
+            dp_rows<NT, CPL, GM>(g, H, V, s, L, a, sh, s_wtot, &bi, &bj);
+            if (t == 0 && bi) na = traceback<GM>(g, H, s, L, bi, bj, a);
         }
         if (t == 0) {
             uint32_t v = V, e = E;
@@ -248,6 +240,8 @@ const Inst kInst[3][N_INST] = {
 };
 #undef HX_INST
 constexpr uint32_t MAX_LEN[3] = {1024 * 32 - 1, 1024 * 16 - 1, 512 * 16 - 1};
+constexpr uint64_t CELL_BYTES[3] = {4, 8, 12};   // of a cell of H by gap model: what the kernels take as sizeof(Cell<GM>)
+static_assert(CELL_BYTES[GM_LINEAR] == sizeof(Cell<GM_LINEAR>) && CELL_BYTES[GM_AFFINE] == sizeof(Cell<GM_AFFINE>) && CELL_BYTES[GM_CONVEX] == sizeof(Cell<GM_CONVEX>), "CELL_BYTES against the cell types of poa_modes_dp.inl");
 inline const void* fn(const Inst& inst, bool cols, bool weighted) { return inst.variant[weighted ? 2 : cols ? 1 : 0]; }
 
 template <class T> struct Buf {   // device buffer of one call
@@ -290,7 +284,7 @@ struct Run {
     const bool cols = msa || wtd;
     const bool want_cov = wtd && (a.want_coverage || a.want_profile);
     const Inst* const inst = kInst[gm];
-    const uint64_t cell_bytes = gm == GM_CONVEX ? 12 : gm == GM_AFFINE ? 8 : 4;   // affine: an (H, F) pair per cell; convex: (H, F, O)
+    const uint64_t cell_bytes = CELL_BYTES[gm];
     const uint64_t nseq = a.set_off[ns], nb = a.seq_off[nseq];
     std::vector<MSet> sets = std::vector<MSet>(ns);
     std::vector<uint64_t> cns_off = std::vector<uint64_t>((size_t)ns + 1, 0);
