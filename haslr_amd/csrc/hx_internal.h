@@ -1,5 +1,5 @@
 // hx_internal.h - what the units of the C-ABI share (hx_api.hip, hx_poa_plan.hip, hx_poa.hip, hx_group.hip): the error helpers, device
-// buffers, the POA workspace arena, the options of a context and the context itself.
+// buffers, the POA workspace arena, the options of a context, the shape of its last consensus call (for hx_poa_report.cpp) and the context itself.
 #pragma once
 #include <atomic>
 #include <thread>
@@ -22,6 +22,7 @@
 #include "host/haslr_host.h"
 #include "kernels/kernels.h"
 #include "kernels/poa_modes.h"
+#include "hx_poa_report.h"
 
 namespace hxi {
 
@@ -125,7 +126,7 @@ struct PoaArena {
 // variables of their environment in, once, when they create a context) and by the tests. Defaults in the table below; -1 = automatic.
 struct HxOptions {
     int debug = 0;                 // progress and statistics of every consensus call on stderr
-    int prof = 0;                  // 1 / 2 / 3: how hx_poa_phase_cycles reads the phase words of a build with -DHX_DP_PROF / PROF2 / PROF3 (development)
+    int prof = 0;                  // 1 / 2 / 3: how hx_poa_phase_cycles reads words 6-11 of a build with -DHX_DP_PROF / PROF2 / PROF3 (development: POA_PHASE_FLAVOUR, kernels/poa_phase_words.h)
     double poa_workspace_gb = 0;   // cap of the POA workspace in GB (0: 90 % of the memory that was free at the context's first consensus call)
     int poa_poll_limit = 1 << 24;  // polls before a wave gives up waiting for another member (testing: forces the unshared retry)
     int poa_max_indeg = 16;        // in-degree the direction bytes hold (testing: forces the score-matrix retry earlier)
@@ -156,6 +157,17 @@ struct HxOptions {
     int poa_weighted = 0;          // hx_poa_weighted without weights runs the weighted instances of the general path on weights of 1 instead of the MSA twins: the cross-check of the weighted graph update against the unit-weight one
     int poa_convex = 0;            // the convex entries with gap_extend2 <= gap_extend run the convex instances of the general path instead of the affine entries: the cross-check of the convex kernel against the affine one
     int poa_modes_slot_kb = 0;     // the general path's first round of slots holds at most this many KB (testing: forces the overflow and the rerun in a larger slot; 0 no cap)
+};
+
+// The shape of the last consensus call, as poa_consensus planned and launched it: what the report (hx_poa_report.h) prints beside the phase words
+struct PoaCallShape {
+    std::vector<uint32_t> lmax, nseq;   // per edge: longest sequence, sequences
+    std::vector<uint8_t> cls;           // per edge: launch class (direction bytes 0-4, score matrix 5-9; 11 = not launched)
+    std::vector<uint32_t> shape;        // per edge: lanes of its workgroup | column passes << 16 | members << 24
+    uint32_t ring[11] = {};             // per launch class: kept rows of its LDS ring
+    PoaReportView view(std::vector<unsigned long long>& words, int debug, int prof, FILE* out) const {
+        return PoaReportView{words.data(), words.size() / hxk::POA_PHASE_WORDS, lmax.data(), nseq.data(), cls.data(), shape.data(), std::min(cls.size(), shape.size()), ring, debug, prof, out};
+    }
 };
 
 template <class T>
@@ -205,10 +217,7 @@ struct hx_ctx {
     std::vector<uint32_t> h_supp_lr, h_spos, h_epos;
     uint32_t n_sel = 0;
     bool have_coords = false;
-    uint32_t dbg_slowest = 0;
-    std::vector<uint32_t> dbg_lmax, dbg_nseq;
-    std::vector<uint8_t> dbg_cls; uint32_t dbg_ring[11] = {};
-    std::vector<uint32_t> dbg_shape;   // per edge: lanes of its workgroup | column passes << 16 | members << 24
+    hxi::PoaCallShape poa_shape;
     bool poa_no_dir = false;   // diagnostics: force the score-matrix traceback
     int poa_block = 0;   // 0 = automatic (lanes per edge chosen from the gap length)
     hipStream_t poa_streams[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -243,7 +252,7 @@ struct hx_ctx {
     hxi::DV<uint32_t> poa_gather;            // collection: (source offset lo / hi, destination offset lo / hi, length) of every finished edge's consensus
     hxi::DV<char> poa_cns_dense;             // ... the strings side by side, as they are downloaded
     hxi::DV<unsigned long long> poa_phase_d, poa_cells_d;
-    std::vector<unsigned long long> poa_phase;   // per edge x 6, cycles of the last hx_poa_batch
+    std::vector<unsigned long long> poa_phase;   // per edge POA_PHASE_WORDS diagnostic words of the last consensus call (kernels/poa_phase_words.h)
 
     DevHits hits_view() const {
         return DevHits{n_hits, q_id.p, q_start.p, q_end.p, t_id.p, t_len.p, t_start.p, t_end.p, n_match.p, n_block.p, is_rev.p, mapq.p, cg_off.p, cg_ops.p};

@@ -182,8 +182,8 @@ struct PoaCall : PoaPlanner {
             }
             const int dcls = q.shared ? 0 : q.nt >= 1024 ? 1 : q.nt >= 512 ? 2 : q.nt >= 256 ? 3 : q.nt >= 128 ? 4 : 5;
             for (size_t k = grp[0]; k < grp[1]; k++)
-                for (uint32_t e : classes[k].edges) { c->dbg_cls[e] = (uint8_t)(dcls + (q.dir ? 0 : 5)); c->dbg_shape[e] = q.nt | std::min<uint32_t>(255, P.edges[e].passes) << 16 | std::min<uint32_t>(255, P.edges[e].members) << 24; }
-            c->dbg_ring[dcls + (q.dir ? 0 : 5)] = R;
+                for (uint32_t e : classes[k].edges) { c->poa_shape.cls[e] = (uint8_t)(dcls + (q.dir ? 0 : 5)); c->poa_shape.shape[e] = q.nt | std::min<uint32_t>(255, P.edges[e].passes) << 16 | std::min<uint32_t>(255, P.edges[e].members) << 24; }
+            c->poa_shape.ring[dcls + (q.dir ? 0 : 5)] = R;
             HIPCHK(hipStreamWaitEvent(c->poa_streams[sk], c->poa_ev[8], 0));
             hxk::PoaLaunch L{};
             L.edges = c->poa_edges.p; L.order = c->poa_order.p + q.order_at; L.n_items = q.persistent ? (uint32_t)g_items : (uint32_t)q.blocks;
@@ -306,9 +306,10 @@ static int poa_consensus(hx_ctx* c, const PoaInput& in, const hx_poa_params* pp,
     if (K.plan_input(todo)) return -1;
     c->poa_host_ms[0] += K.ms_since_start();
     if (c->opt.debug) fprintf(stderr, "[hx] POA call: %u edges prepared in %.1f ms\n", (unsigned)ne, K.ms_since_start());
-    c->dbg_cls.assign(ne, 11); for (int k = 0; k < 11; k++) c->dbg_ring[k] = 0;
-    c->dbg_shape.assign(ne, 0);
-    c->dbg_nseq = K.P.nseq; c->dbg_lmax.resize(ne); for (uint32_t e = 0; e < ne; e++) c->dbg_lmax[e] = K.P.edges[e].lmax;
+    PoaCallShape& sh = c->poa_shape;
+    sh.cls.assign(ne, POA_NO_CLASS); for (int k = 0; k < 11; k++) sh.ring[k] = 0;
+    sh.shape.assign(ne, 0);
+    sh.nseq = K.P.nseq; sh.lmax.resize(ne); for (uint32_t e = 0; e < ne; e++) sh.lmax[e] = K.P.edges[e].lmax;
     HIPCHK(c->poa_seqs.reserve(K.P.seqs.size()));
     if (!K.P.seqs.empty()) HIPCHK(hipMemcpyAsync(c->poa_seqs.p, K.P.seqs.data(), K.P.seqs.size() * sizeof(hxk::PoaSeq), hipMemcpyHostToDevice, s));
     HIPCHK(c->poa_cells_d.reserve(1));
@@ -618,117 +619,7 @@ extern "C" void hx_free_wcns(hx_ctx*, hx_wcns_out* o) { free(o->cns_off); free(o
 extern "C" void hx_free_cns(hx_ctx*, hx_cns_out* o) { free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }
 extern "C" void hx_free_msa(hx_ctx*, hx_msa_out* o) { free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa); free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }
 
-extern "C" uint32_t hx_poa_phase_cycles(hx_ctx* c, uint64_t* sum6, uint64_t* max6) {
-    // lane-0 cycle counters of the last hx_poa_batch: [decode, dp, traceback, graph update+consensus, toposort, csr];
-    // sum over edges and the breakdown of the edge with the largest total (the critical path)
-    constexpr size_t PW_ = hxk::POA_PHASE_WORDS;
-    for (int k = 0; k < 6; k++) { sum6[k] = 0; max6[k] = 0; }
-    unsigned long long best = 0;
-    size_t ne = c->poa_phase.size() / PW_;
-    for (size_t e = 0; e < ne; e++) for (int k = 0; k < 6; k++) if ((long long)c->poa_phase[e * PW_ + k] < 0) c->poa_phase[e * PW_ + k] = 0;   // (a phase that began and ended on different waves' clocks)
-    for (size_t e = 0; e < ne; e++) {
-        unsigned long long t = 0;
-        for (int k = 0; k < 6; k++) { sum6[k] += c->poa_phase[e * PW_ + k]; t += c->poa_phase[e * PW_ + k]; }
-        if (t > best) { best = t; for (int k = 0; k < 6; k++) max6[k] = c->poa_phase[e * PW_ + k]; c->dbg_slowest = (uint32_t)e; }
-    }
-    if (c->opt.debug && ne) {
-        const unsigned long long* q = &c->poa_phase[(size_t)c->dbg_slowest * PW_];
-        if (c->opt.prof == 1) {   // (a build with -DHX_DP_PROF: where the rows of the first wave of every workgroup spend their cycles, per launch class)
-            static const char* seg[6] = {"decode", "predecessors + cells + chain", "wave scan", "carry", "carry applied + ring", "stores"};
-            unsigned long long cs[12][7] = {};
-            for (size_t e = 0; e < ne; e++) { const int k = e < c->dbg_cls.size() ? c->dbg_cls[e] : 11; for (int j = 0; j < 6; j++) cs[k][j] += c->poa_phase[e * PW_ + 6 + j]; cs[k][6] += c->poa_phase[e * PW_ + 1]; }
-            for (int k = 0; k < 12; k++) {
-                unsigned long long t = 0; for (int j = 0; j < 6; j++) t += cs[k][j];
-                if (!t) continue;
-                fprintf(stderr, "[hx] prof1 class %d: row segments of wave 0, %.3g cycles (DP phase %.3g):", k, (double)t, (double)cs[k][6]);
-                for (int j = 0; j < 6; j++) fprintf(stderr, " %s %.1f %%%s", seg[j], 100.0 * (double)cs[k][j] / (double)t, j < 5 ? "," : "\n");
-            }
-            return (uint32_t)ne;
-        }
-        if (c->opt.prof == 2) {   // (a build with -DHX_DP_PROF -DHX_DP_PROF2: where member 0's DP phase goes, for the five longest edges)
-            std::vector<std::pair<unsigned long long, uint32_t>> tt;
-            for (size_t e = 0; e < ne; e++) { unsigned long long t = 0; for (int k = 0; k < 6; k++) t += c->poa_phase[e * PW_ + k]; tt.push_back({t, (uint32_t)e}); }
-            std::sort(tt.rbegin(), tt.rend());
-            for (size_t k = 0; k < std::min<size_t>(5, tt.size()); k++) {
-                const unsigned long long* q2 = &c->poa_phase[(size_t)tt[k].second * PW_];
-                fprintf(stderr, "[hx] prof2 edge %u lmax=%u nseq=%u dp phase %llu: publish %llu own columns %llu wait members %llu end node %llu (ties sorted %llu, toposort %llu)\n", tt[k].second, c->dbg_lmax[tt[k].second],
-                        c->dbg_nseq[tt[k].second], q2[1], q2[6], q2[7], q2[8], q2[9], q2[10], q2[11]);
-            }
-            return (uint32_t)ne;
-        }
-        if (c->opt.prof == 3) {   // (a build with -DHX_DP_PROF3: per member of the five longest edges, kilocycles inside the DP and of them waiting for carries)
-            std::vector<std::pair<unsigned long long, uint32_t>> tt;
-            for (size_t e = 0; e < ne; e++) { unsigned long long t = 0; for (int k = 0; k < 6; k++) t += c->poa_phase[e * PW_ + k]; tt.push_back({t, (uint32_t)e}); }
-            std::sort(tt.rbegin(), tt.rend());
-            for (size_t k = 0; k < std::min<size_t>(5, tt.size()); k++) {
-                const unsigned long long* q2 = &c->poa_phase[(size_t)tt[k].second * PW_];
-                fprintf(stderr, "[hx] prof3 edge %u lmax=%u nseq=%u dp %llu:", tt[k].second, c->dbg_lmax[tt[k].second], c->dbg_nseq[tt[k].second], q2[1]);
-                for (int m = 0; m < 6; m++) fprintf(stderr, " m%d dp %lluk wait %lluk", m, q2[6 + m] & 0xffffffffull, q2[6 + m] >> 32);
-                fprintf(stderr, "\n");
-            }
-            return (uint32_t)ne;
-        }
-        const unsigned long long M40 = (1ull << 40) - 1;
-        if (c->opt.debug >= 2) {   // every edge: shape of its launch, begin and end on the 100 MHz wall clock (relative to the call's first edge), phase cycles, DP rows
-            unsigned long long t0 = ~0ull;
-            const unsigned long long M44 = (1ull << 44) - 1;
-            for (size_t e = 0; e < ne; e++) if (c->poa_phase[e * PW_ + 16]) t0 = std::min(t0, c->poa_phase[e * PW_ + 16] & M44);
-            for (size_t e = 0; e < ne; e++) {
-                const unsigned long long* q2 = &c->poa_phase[e * PW_];
-                if (!q2[16]) continue;
-                const uint32_t sh = e < c->dbg_shape.size() ? c->dbg_shape[e] : 0;
-                fprintf(stderr, "[hx-edge] %zu lmax %u nseq %u cls %d lanes %u passes %u members %u hw %u begin_us %.1f end_us %.1f decode %llu dp %llu tb %llu graph %llu order %llu csr %llu rows %llu wrows %llu wskip %llu wbulk %llu cns %llu refcns %llu\n", e, c->dbg_lmax[e], c->dbg_nseq[e],
-                        e < c->dbg_cls.size() ? c->dbg_cls[e] : 11, sh & 0xffffu, (sh >> 16) & 255u, sh >> 24, (unsigned)(q2[16] >> 44), (double)((q2[16] & M44) - t0) * 0.01, (double)(q2[17] - t0) * 0.01, q2[0], q2[1], q2[2], q2[3], q2[4], q2[5], q2[6], q2[12], q2[13], q2[20], q2[18], q2[19]);
-            }
-        }
-        fprintf(stderr, "[hx] slowest edge %u: lmax=%u nseq=%u | DP rows %llu (multi-pred %llu, ring refs %llu, far refs %llu, kept %llu, more than 4 predecessors %llu, fifth-and-later entries %llu) over %llu sequences\n", c->dbg_slowest,
-                c->dbg_lmax[c->dbg_slowest], c->dbg_nseq[c->dbg_slowest], q[6], q[7], q[8] & M40, q[9] & M40, q[10], q[9] >> 40, q[8] >> 40, q[11] & 0xffffffffull);
-        {   // the five longest edges (critical-path candidates)
-            std::vector<std::pair<unsigned long long, uint32_t>> tt;
-            for (size_t e = 0; e < ne; e++) { unsigned long long t = 0; for (int k = 0; k < 6; k++) t += c->poa_phase[e * PW_ + k]; tt.push_back({t, (uint32_t)e}); }
-            std::sort(tt.rbegin(), tt.rend());
-            for (size_t k = 0; k < std::min<size_t>(5, tt.size()); k++) {
-                const unsigned long long* q2 = &c->poa_phase[(size_t)tt[k].second * PW_];
-                fprintf(stderr, "[hx] top edge %u: lmax=%u nseq=%u cycles=%llu (dp %llu tb %llu graph %llu order %llu csr %llu) rows %llu multi %llu ring %llu far %llu kept %llu wide %llu fifth+ %llu\n", tt[k].second, c->dbg_lmax[tt[k].second], c->dbg_nseq[tt[k].second],
-                        tt[k].first, q2[1], q2[2], q2[3], q2[4], q2[5], q2[6], q2[7], q2[8] & ((1ull << 40) - 1), q2[9] & ((1ull << 40) - 1), q2[10], q2[9] >> 40, q2[8] >> 40);
-            }
-        }
-        {   // finished graphs against the workspace estimate: nodes per base of the longest sequence, as a + b x sequences
-            std::vector<double> grow, fill;
-            for (size_t e = 0; e < ne; e++) {
-                const double V = (double)(c->poa_phase[e * PW_ + 11] >> 32), L = c->dbg_lmax[e], S = c->dbg_nseq[e];
-                if (V <= 0 || L <= 0 || S <= 0) continue;
-                grow.push_back((V - L) / (L * S));
-                fill.push_back(V / (L * (3 + S / 10) + 1024));
-            }
-            std::sort(grow.begin(), grow.end()); std::sort(fill.begin(), fill.end());
-            auto pc = [](const std::vector<double>& v, double q) { return v.empty() ? 0.0 : v[std::min(v.size() - 1, (size_t)(q * v.size()))]; };
-            fprintf(stderr, "[hx] graph growth (nodes - L) / (L x sequences): median %.3f  p90 %.3f  p99 %.3f  max %.3f | nodes / estimate: median %.2f  p99 %.2f  max %.2f\n",
-                    pc(grow, 0.5), pc(grow, 0.9), pc(grow, 0.99), pc(grow, 1.0), pc(fill, 0.5), pc(fill, 0.99), pc(fill, 1.0));
-        }
-        {   // per launch class: how often a row is read back from the LDS ring / from HBM
-            unsigned long long cr[12][4] = {};
-            for (size_t e = 0; e < ne; e++) { const int k = e < c->dbg_cls.size() ? c->dbg_cls[e] : 11; const unsigned long long* q3 = &c->poa_phase[e * PW_]; cr[k][0] += q3[6]; cr[k][1] += q3[10]; cr[k][2] += q3[8] & ((1ull << 40) - 1); cr[k][3] += q3[9] & ((1ull << 40) - 1); }
-            for (int k = 0; k < 12; k++) if (cr[k][0]) fprintf(stderr, "[hx] class %d (ring %u): DP rows %llu, kept %.1f %%, ring refs %.1f %%, far refs %.2f %%\n", k, k < 11 ? c->dbg_ring[k] : 0, cr[k][0], 100.0 * cr[k][1] / cr[k][0], 100.0 * cr[k][2] / cr[k][0], 100.0 * cr[k][3] / cr[k][0]);
-            unsigned long long cy[12][4] = {};   // edges, all cycles, DP cycles, longest edge
-            for (size_t e = 0; e < ne; e++) {
-                const int k = e < c->dbg_cls.size() ? c->dbg_cls[e] : 11; const unsigned long long* q3 = &c->poa_phase[e * PW_];
-                unsigned long long t = 0; for (int j = 0; j < 6; j++) t += q3[j];
-                cy[k][0]++; cy[k][1] += t; cy[k][2] += q3[1]; cy[k][3] = std::max(cy[k][3], t);
-            }
-            for (int k = 0; k < 12; k++) if (cy[k][0]) fprintf(stderr, "[hx] class %d: %llu workgroups, %.3e cycles in all (DP %.0f %%), longest %.3e, DP cycles per row %.0f\n", k, cy[k][0], (double)cy[k][1], 100.0 * cy[k][2] / cy[k][1], (double)cy[k][3], cr[k][0] ? (double)cy[k][2] / cr[k][0] : 0.0);
-        }
-        {   // the pruning (kernels/poa.hip PRUNE): wave-rows of the pruned launches, those skipped, attempts repeated, per launch class
-            unsigned long long pr[12][4] = {};
-            for (size_t e = 0; e < ne; e++) { const int k = e < c->dbg_cls.size() ? c->dbg_cls[e] : 11; for (int j = 0; j < 4; j++) pr[k][j] += c->poa_phase[e * PW_ + 12 + j]; }
-            for (int k = 0; k < 12; k++) if (pr[k][0]) fprintf(stderr, "[hx] class %d pruning: %.4g wave-rows, %.1f %% skipped, %llu alignments with a threshold, %llu repeated\n", k, (double)pr[k][0], 100.0 * pr[k][1] / pr[k][0], pr[k][3], pr[k][2]);
-        }
-        unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};
-        for (size_t e = 0; e < ne; e++) for (int k = 0; k < 6; k++) tot[k] += k == 5 ? (c->poa_phase[e * PW_ + 11] & 0xffffffffull) : (k == 2 || k == 3 ? c->poa_phase[e * PW_ + 6 + k] & ((1ull << 40) - 1) : c->poa_phase[e * PW_ + 6 + k]);
-        fprintf(stderr, "[hx] all edges: DP rows %llu (multi-pred %llu, ring refs %llu, far refs %llu, kept %llu) over %llu sequences\n", tot[0], tot[1], tot[2], tot[3], tot[4], tot[5]);
-    }
-    return (uint32_t)ne;
-}
+extern "C" uint32_t hx_poa_phase_cycles(hx_ctx* c, uint64_t* sum6, uint64_t* max6) { return poa_phase_report(c->poa_shape.view(c->poa_phase, c->opt.debug, c->opt.prof, stderr), sum6, max6).edges; }
 extern "C" uint64_t hx_poa_workspace_bytes(const hx_ctx* c) { return c->poa_workspace_bytes; }
 extern "C" int hx_poa_release_workspace(hx_ctx* c) {
     HIPCHK(hipSetDevice(c->device));
@@ -759,11 +650,7 @@ extern "C" void hx_poa_arena_stats(const hx_ctx* c, uint64_t* capacity, uint64_t
 extern "C" void hx_poa_memory_stats(const hx_ctx* c, uint64_t* free_at_first_call, uint64_t* budget, uint64_t* last_call_workspace) {
     *free_at_first_call = c->poa_free_at_first_call; *budget = c->poa_budget; *last_call_workspace = c->poa_last_workspace_bytes;
 }
-extern "C" void hx_poa_prune_stats(const hx_ctx* c, uint64_t* out4) {
-    for (int j = 0; j < 4; j++) out4[j] = 0;
-    const size_t PW_ = hxk::POA_PHASE_WORDS, ne = c->poa_phase.size() / PW_;
-    for (size_t e = 0; e < ne; e++) for (int j = 0; j < 4; j++) out4[j] += c->poa_phase[e * PW_ + 12 + j];
-}
+extern "C" void hx_poa_prune_stats(const hx_ctx* c, uint64_t* out4) { poa_prune_sums(c->poa_phase.data(), c->poa_phase.size() / hxk::POA_PHASE_WORDS, out4); }
 extern "C" void hx_poa_retry_stats(const hx_ctx* c, uint64_t* out6) { for (int k = 0; k < 6; k++) out6[k] = c->poa_retry[k]; }
 extern "C" void hx_set_poa_traceback(hx_ctx* c, int use_direction_bytes) { c->poa_no_dir = !use_direction_bytes; }
 extern "C" void hx_set_poa_block(hx_ctx* c, int t) { c->poa_block = t <= 0 ? 0 : t >= 1024 ? 1024 : t >= 512 ? 512 : t >= 256 ? 256 : t >= 128 ? 128 : 64; }

@@ -44,11 +44,11 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                                          const uint32_t* __restrict__ read_len, const PoaPools& P, int32_t match, int32_t mismatch, int32_t gap,
                                          char* cns, uint32_t* cns_len, uint32_t* status, unsigned long long* cells, unsigned long long* phase,
                                          uint32_t poll_limit, uint32_t lds_bytes, uint32_t max_indeg, uint32_t dp_lanes, uint32_t prune_pct) {
-    __shared__ unsigned long long ph[POA_PHASE_WORDS];   // lane-0 cycle counts: decode, dp, traceback, graph update, toposort, csr; then row statistics (6-11) and the pruning's (12-15)
+    __shared__ unsigned long long ph[POA_PHASE_WORDS];   // the edge's diagnostic words (enum PoaPhaseWord, poa_phase_words.h), written by lane 0
     __shared__ long long tc;
-    if (threadIdx.x == 0) { for (int k = 0; k < POA_PHASE_WORDS; k++) ph[k] = 0; tc = clock64(); ph[16] = (wall_clock64() & ((1ull << 44) - 1)) | ((unsigned long long)((__builtin_amdgcn_s_getreg(63492) & 0x7fffu) | ((__builtin_amdgcn_s_getreg(63508) & 15u) << 15)) << 44); }   // (begin; where: HW_ID bits 0-14 = wave, SIMD, pipe, CU, SH, SE and the XCC)
+    if (threadIdx.x == 0) { for (int k = 0; k < POA_PHASE_WORDS; k++) ph[k] = 0; tc = clock64(); ph[PW_BEGIN] = pw_pack(pw_lo(wall_clock64(), PW_SPLIT_CLOCK), (unsigned long long)((__builtin_amdgcn_s_getreg(63492) & 0x7fffu) | ((__builtin_amdgcn_s_getreg(63508) & 15u) << 15)), PW_SPLIT_CLOCK); }   // (begin; where: HW_ID bits 0-14 = wave, SIMD, pipe, CU, SH, SE and the XCC)
 #define PHASE(k) do { if (tid == 0) { long long _n = clock64(); ph[k] += (unsigned long long)(_n - tc); tc = _n; } } while (0)
-#ifdef HX_GU_PROF   // development: where the graph update (slots 6-10) and the CSR rebuild (slot 11: its first half) spend their cycles - printed by HX_PROF2 (its labels are the DP's)
+#if POA_PHASE_FLAVOUR == POA_PHASE_GUSTAGES   // development: where the graph update (PW_GU_STAGE0 ...) and the CSR rebuild (PW_GU_CSR: its first half) spend their cycles - printed by HX_PROF2 (its labels are the DP's)
 #define GU_T0() do { __syncthreads(); if (tid == 0) tg = clock64(); } while (0)
 #define GU_T(k) do { __syncthreads(); if (tid == 0) { long long _n = clock64(); ph[k] += (unsigned long long)(_n - tg); tg = _n; } } while (0)
     long long tg = 0;
@@ -56,7 +56,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
 #define GU_T0() do { } while (0)
 #define GU_T(k) do { } while (0)
 #endif
-#if defined(HX_DP_PROF2) && !defined(HX_DP_PROF3)
+#if POA_PHASE_FLAVOUR == POA_PHASE_DPSUB
     __shared__ long long tc2;
 #define SUBT(k) do { if (tid == 0) { long long _n = clock64(); ph[k] += (unsigned long long)(_n - tc2); tc2 = _n; } } while (0)
 #define SUBT0() do { if (tid == 0) tc2 = clock64(); } while (0)
@@ -134,7 +134,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
     constexpr uint32_t CL_ABORT = 0xffffffffu;
 #define HX_DP_DISPATCH(Lq, Vq, nsq, Tq) do { \
         if (((Lq) + 1 + GM * NP * DL - 1) / (GM * NP * DL) <= (uint32_t)CM) {    /* the host puts an edge into a launch whose columns per lane hold its longest sequence */ \
-            dp_rows<CM, DIR, PRUNE, MAXNT == 64>(g, H, Dm, Dw, W, WH, seq, Lq, Vq, ring, R, ring_w, match, mismatch, gap, wmail.box, wmail.consumed, sink_row, sink_score, SINK_LDS, nsq, cl, ph + 6, Tq, (prune_pct >> 16) & 1u, ph + 12, ED.hrows); \
+            dp_rows<CM, DIR, PRUNE, MAXNT == 64>(g, H, Dm, Dw, W, WH, seq, Lq, Vq, ring, R, ring_w, match, mismatch, gap, wmail.box, wmail.consumed, sink_row, sink_score, SINK_LDS, nsq, cl, ph + PW_BUILD0, Tq, (prune_pct >> 16) & 1u, ph + PW_PRUNE0, ED.hrows); \
         } else sOk = 2; } while (0)
     // The reference's topological order (spoa's DFS, inherently serial) is needed in two places only: to break ties between equally scored
     // end nodes of an alignment, and for the heaviest-bundle traversal of the finished graph. The DP itself runs on a cheaper order that
@@ -163,12 +163,12 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
         __syncthreads();
         if (wave_dfs) {
             uint32_t* ranks = reinterpret_cast<uint32_t*>(g.score);   // free between the CSR build and the graph update
-#if defined(HX_DP_PROF2) && !defined(HX_DP_PROF3)
+#if POA_PHASE_FLAVOUR == POA_PHASE_DPSUB
             long long tq0 = clock64();
 #endif
             if (tid < 64) toposort_rank(g, Vn, st, t_stack, t_cache, t_tags, ranks, topo_lcap, topo_lines);   // wave 0, 64 lanes in lock step
-#if defined(HX_DP_PROF2) && !defined(HX_DP_PROF3)
-            if (tid == 0) ph[11] += (unsigned long long)(clock64() - tq0);
+#if POA_PHASE_FLAVOUR == POA_PHASE_DPSUB
+            if (tid == 0) ph[PW_P2_TOPO] += (unsigned long long)(clock64() - tq0);
 #endif
             __threadfence_block();
             __syncthreads();
@@ -200,7 +200,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                 }
             }
             __syncthreads();
-            PHASE(0);
+            PHASE(PW_DECODE);
             V = sV;
             SUBT0();
         } else {
@@ -221,7 +221,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
             V = ld_dev(csy + 2); L = ld_dev(csy + 3);
         }
         // =================================================== DP over (rank, column): every member, its own columns
-        if (mem == 0) SUBT(6);   // publish
+        if (mem == 0) SUBT(PW_P2_PUBLISH);   // publish
         // PRUNE: the threshold of this alignment = what the previous one of the edge scored per base, on this length, x prune_pct / 100 (scores per
         // base rise as the graph turns into a consensus, so this errs low). Too high an estimate costs a second attempt, never a wrong result: the
         // best sink of a pruned matrix is a real path's score, and an attempt that stays below its threshold is repeated with exactly that score.
@@ -245,9 +245,9 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
         }
         if (V > 0) {
             uint32_t ns = 0xffffffffu;
-#ifdef HX_DP_PROF3
+#if POA_PHASE_FLAVOUR == POA_PHASE_MEMBERS
             const long long td0 = clock64();
-            if (tid == 0) ph[6] = 0;
+            if (tid == 0) ph[PW_P3_WAIT] = 0;
 #endif
             if (NP > 1) {
                 for (uint32_t pass = 0; pass < NP && (uint64_t)pass * DL * CM <= L; pass++) {   // (a window beyond the sequence has nothing to do)
@@ -259,8 +259,8 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                 cl.mem = 0; cl.members = 1;
             } else
             HX_DP_DISPATCH(L, V, ns, thrT);
-#ifdef HX_DP_PROF3
-            if (tid == 0 && phase) atomicAdd(&phase[(uint64_t)eidx * POA_PHASE_WORDS + 6 + min(mem, 5u)], ((ph[6] >> 10) << 32) | ((unsigned long long)(clock64() - td0) >> 10));
+#if POA_PHASE_FLAVOUR == POA_PHASE_MEMBERS
+            if (tid == 0 && phase) atomicAdd(&phase[(uint64_t)eidx * POA_PHASE_WORDS + PW_P3_MEMBER0 + min(mem, (uint32_t)(PW_N_BUILD - 1))], pw_pack(0, ph[PW_P3_WAIT] >> 10, PW_SPLIT_HALF) | pw_pack((unsigned long long)(clock64() - td0) >> 10, 0, PW_SPLIT_HALF));   // (the wait half first: it is read before the clock)
 #endif
             if (ns != 0xffffffffu) sNsink = ns;   // written by the lane that owns column L
             cl.tag0 += V;
@@ -277,7 +277,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
             if (tid == 0) __hip_atomic_fetch_add(csy + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             continue;
         }
-        SUBT(7);   // own columns
+        SUBT(PW_P2_OWN);   // own columns
         if (V > 0) {
             {
                 if (GM > 1) {   // wait for the other members' columns (direction bytes, sinks)
@@ -304,7 +304,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                                                                     // when the members of an edge are not resident together): the host redoes the edge unshared
             __syncthreads();
             if (sOk != 1) break;                                    // (the matrix of this sequence is not to be walked)
-            SUBT(8);   // wait for the other members, sinks
+            SUBT(PW_P2_WAIT);   // wait for the other members, sinks
             // ---- end node of the global alignment: the best-scoring sink; ties go to the smallest rank in the REFERENCE's order
             if (tid == 0) {
                 if (sNsink > SINK_LDS) sOk = 6;   // more sink rows than the launch keeps: the host redoes the edge in a launch with the full list
@@ -315,8 +315,8 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                 (void)first;
                 if constexpr (PRUNE) {   // did the alignment reach its threshold? (else: again, with the score it did reach - a real path's - or, no sink computed at all, unpruned)
                     sRetry = thrT > PRUNE_OFF && sOk == 1 && best < thrT;
-                    if (sRetry) { sNewT = nsk ? max(best, PRUNE_OFF) : PRUNE_OFF; ph[14]++; }
-                    else { sPrevScore = best; sPrevLen = L; ph[15] += thrT > PRUNE_OFF; }
+                    if (sRetry) { sNewT = nsk ? max(best, PRUNE_OFF) : PRUNE_OFF; ph[PW_PRUNE_REPEATED]++; }
+                    else { sPrevScore = best; sPrevLen = L; ph[PW_PRUNE_THRESHOLDS] += thrT > PRUNE_OFF; }
                 }
                 sNcand = ncand; sBestI = ncand ? (int)sink_row[0] : -1; sBestKey = 0xffffffffu;
                 lds_u[8] = 0; lds_u[9] = 0; lds_u[10] = 0;   // (traceback helper: nowhere yet, not done)
@@ -401,7 +401,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                 }
             }
             if (sNcand > 1 && sOk == 1) {
-                if (tid == 0) ph[10] += 1;
+                if (tid == 0) ph[PW_P2_TIES] += 1;
                 exact_order(V, tmp_u32);
                 const uint32_t nc = sNcand;
                 for (uint32_t r = tid; r < V; r += NT) {
@@ -410,11 +410,11 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                         if (g.rank2node[sink_row[q] - 1] == n) atomicMin(&sBestKey, (r << 10) | q);   // nc <= 1024 candidates
                 }
                 __syncthreads();
-                if (tid == 0) { sBestI = (int)sink_row[sBestKey & 1023u]; atomicAdd(&ph[4], 0ull); }
+                if (tid == 0) { sBestI = (int)sink_row[sBestKey & 1023u]; atomicAdd(&ph[PW_ORDER], 0ull); }
             }
             __syncthreads();
-            SUBT(9);   // end node (ties: reference order)
-            PHASE(1);
+            SUBT(PW_P2_END);   // end node (ties: reference order)
+            PHASE(PW_DP);
             // =================================================== traceback, stored reversed
             if (DIR) {
                 // Direction bytes: the first wavefront walks the path together. A tile of 64 rows x 32 columns of direction nibbles (four registers)
@@ -605,20 +605,20 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
         }
         __syncthreads();
         if (sOk != 1) break;                                        // (a walk that did not end: see there)
-        PHASE(2);
+        PHASE(PW_TRACEBACK);
         // =================================================== graph update + order update (all lanes): graph_update / order_update above
         const uint32_t V_old = sV;
         graph_update(g, seq, L, sNaln, sWalkN, sWalkI, sWalkJ, lds_u, &sV, &sE, &sNcand, &sOk);
-        PHASE(3);
+        PHASE(PW_GRAPH);
         __syncthreads();
         if (sOk != 1) break;
         order_update(g, V_old, sV, L, lds_u);
-        PHASE(4);
+        PHASE(PW_ORDER);
         __syncthreads();
         // =================================================== rank-order CSR for the next DP (all lanes): csr_rebuild above
         csr_rebuild<MAXNT, DIR>(g, sV, R, max_indeg, ED.hrows, ED.wrows, lds_u, &sOk, ph, phase != nullptr, eidx, k == ED.seq_begin, k + 1 == ED.seq_end);
         __syncthreads();
-        PHASE(5);
+        PHASE(PW_CSR);
     }
     if (mem > 0) return;
     if (GM > 1 && tid == 0) st_dev(csy + 0, CL_ABORT);   // release the other members (they wait for the next attempt: done or not, there is none)
@@ -630,7 +630,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
         if (tid < 64) { const uint32_t cl_ = consensus_fast_wave(g, sV, cns + ED.cns_off); if (tid == 0) sCtl = cl_; }
         __syncthreads();
         if (sCtl == NONE) {
-            if (tid == 0) ph[19] = 1;
+            if (tid == 0) ph[PW_REFCNS] = 1;
             exact_order(sV, g.rank2node);
             for (uint32_t r = tid; r < sV; r += NT) g.node2rank[g.rank2node[r]] = r;
             __syncthreads();
@@ -653,15 +653,15 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
         else if (sOk == 8) { status[eidx] = HXE_POA_STALLED; cns_len[eidx] = 0; }
         else {
             status[eidx] = 0; cns_len[eidx] = !sV ? 0 : sCtl; atomicAdd(cells, sCells);
-#if !defined(HX_DP_PROF) && !defined(HX_GU_PROF)
-            if (phase) atomicAdd(&ph[11], (unsigned long long)sV << 32);   // statistics: nodes of the finished graph (high word)
+#if POA_PHASE_FLAVOUR == POA_PHASE_ROWSTATS
+            if (phase) atomicAdd(&ph[PW_SEQS_NODES], pw_pack(0, sV, PW_SPLIT_HALF));   // statistics: nodes of the finished graph (high word)
 #endif
         }
-        ph[18] = (unsigned long long)(clock64() - t_cns);
-        PHASE(3);
-        ph[17] = wall_clock64() & ((1ull << 44) - 1);
-#ifdef HX_DP_PROF3
-        if (phase) for (int k = 0; k < 6; k++) phase[(uint64_t)eidx * POA_PHASE_WORDS + k] = ph[k];
+        ph[PW_CNS] = (unsigned long long)(clock64() - t_cns);
+        PHASE(PW_GRAPH);
+        ph[PW_END] = pw_lo(wall_clock64(), PW_SPLIT_CLOCK);
+#if POA_PHASE_FLAVOUR == POA_PHASE_MEMBERS
+        if (phase) for (int k = 0; k < PW_N_PHASES; k++) phase[(uint64_t)eidx * POA_PHASE_WORDS + k] = ph[k];   // (the members have added to the others in place)
 #else
         if (phase) for (int k = 0; k < POA_PHASE_WORDS; k++) phase[(uint64_t)eidx * POA_PHASE_WORDS + k] = ph[k];
 #endif

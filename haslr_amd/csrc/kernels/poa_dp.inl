@@ -301,12 +301,10 @@ template <int CM> __device__ __forceinline__ void store_nibbles_buf(__amdgpu_buf
     }
 }
 
-#ifdef HX_DP_PROF3   // development: per member of a shared edge, cycles inside the DP and cycles of them spent waiting for carries (phase slots 6 + member)
-#define HX_DP_PROF
-#define HX_DP_PROF2
-#endif
-#if defined(HX_DP_PROF) && !defined(HX_DP_PROF2)
-#define DP_T(k) do { if (tid == 0) { const long long _n = clock64(); prof[k] += (unsigned long long)(_n - tprev); tprev = _n; } } while (0)
+// development builds (POA_PHASE_FLAVOUR, poa_phase_words.h; `prof` = the edge's word PW_BUILD0): POA_PHASE_ROWSEG - lane 0's cycles per segment of a row (PW_SEG0 + k); POA_PHASE_MEMBERS -
+// per member of a shared edge, cycles inside the DP and cycles of them spent waiting for carries (PW_P3_WAIT)
+#if POA_PHASE_FLAVOUR == POA_PHASE_ROWSEG
+#define DP_T(k) do { if (tid == 0) { const long long _n = clock64(); prof[PW_SEG0 - PW_BUILD0 + (k)] += (unsigned long long)(_n - tprev); tprev = _n; } } while (0)
 #else
 #define DP_T(k) do { } while (0)
 #endif
@@ -318,11 +316,11 @@ template <int CM> __device__ __forceinline__ void store_nibbles_buf(__amdgpu_buf
 template <int CM, bool DIR, bool PRUNE, bool ONEW /* the workgroup is one wave (the 64-lane instances): no LDS mailbox on either side, no relay - known at compile time, the row loses its tests of them */>
 __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uint8_t* __restrict__ D, uint8_t* __restrict__ Dwide, const uint32_t W, const uint32_t WH, const uint8_t* __restrict__ seq,
                         const uint32_t L_, const uint32_t V_, int32_t* ring, const uint32_t R_, const uint32_t ring_w_, const int match, const int mismatch, const int gap,
-                        unsigned long long* wm_box, uint32_t* wm_cons, uint32_t* sink_row, int* sink_score, const uint32_t sink_cap, uint32_t& nSinkOut, const DpCl& cl, unsigned long long* prof,
-                        const int thrT /* PRUNE: score threshold T of this alignment (PRUNE_OFF: nothing real is below it) */, const uint32_t lazy_on /* PRUNE: skipped waves poll rarely */, unsigned long long* pstat /* PRUNE: wave-rows, wave-rows skipped */,
+                        unsigned long long* wm_box, uint32_t* wm_cons, uint32_t* sink_row, int* sink_score, const uint32_t sink_cap, uint32_t& nSinkOut, const DpCl& cl, unsigned long long* prof /* development builds: the edge's word PW_BUILD0 */,
+                        const int thrT /* PRUNE: score threshold T of this alignment (PRUNE_OFF: nothing real is below it) */, const uint32_t lazy_on /* PRUNE: skipped waves poll rarely */, unsigned long long* pstat /* PRUNE: the edge's word PW_PRUNE0 */,
                         const uint32_t far_n /* PRUNE: rows of H (far-read rows) of the edge */) {
     static_assert(!PRUNE || DIR, "pruned rows: direction-byte flavour only");
-#if defined(HX_DP_PROF) && !defined(HX_DP_PROF2)
+#if POA_PHASE_FLAVOUR == POA_PHASE_ROWSEG
     long long tprev = clock64();
 #endif
     // wave-uniform values the compiler cannot know to be uniform (they come through LDS / integer division / the thread index): in scalar
@@ -558,7 +556,7 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
             nb = want;
             int cinV = NEGK;     // lane r: carry into this wave for row i0 + r
             if (has_in) {
-#ifdef HX_DP_PROF3
+#if POA_PHASE_FLAVOUR == POA_PHASE_MEMBERS
                 const long long tw0 = clock64();
 #endif
                 for (uint32_t spin = 0;; spin++) {
@@ -578,8 +576,8 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
                     else if (in_lds) __builtin_amdgcn_s_sleep(2); else __builtin_amdgcn_s_sleep(8);
                 }
                 if (in_lds && lane == 0) st_wg(cons_in, cl.tag0 + i0 + nb - 1);   // the entries of these rows may be written again
-#ifdef HX_DP_PROF3
-                if (tid == 0) prof[0] += (unsigned long long)(clock64() - tw0);
+#if POA_PHASE_FLAVOUR == POA_PHASE_MEMBERS
+                if (tid == 0) prof[PW_P3_WAIT - PW_BUILD0] += (unsigned long long)(clock64() - tw0);
 #endif
             }
             if (has_out && out_lds) {   // the rows of this batch overwrite the entries of the rows WAVE_MBOX earlier: the wave on the right must have taken those
@@ -879,6 +877,6 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
         }
     }
     if (owns_last) nSinkOut = nsink;
-    if constexpr (PRUNE) { if (lane == 0 && pstat) { atomicAdd(&pstat[0], (unsigned long long)V); atomicAdd(&pstat[1], (unsigned long long)n_dead); atomicAdd(&pstat[8], (unsigned long long)n_bulk); } }
+    if constexpr (PRUNE) { if (lane == 0 && pstat) { atomicAdd(&pstat[PW_PRUNE_ROWS - PW_PRUNE0], (unsigned long long)V); atomicAdd(&pstat[PW_PRUNE_SKIPPED - PW_PRUNE0], (unsigned long long)n_dead); atomicAdd(&pstat[PW_PRUNE_BULK - PW_PRUNE0], (unsigned long long)n_bulk); } }
 }
 

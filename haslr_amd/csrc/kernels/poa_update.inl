@@ -230,12 +230,12 @@ __device__ __forceinline__ void csr_rebuild(const G& g_in, const uint32_t V2, co
         if (tid == 0 && last_seq && eidx % 500 == 0)
             printf("[csrprof] edge %u lanes %u V %u seqs %u: scatter %llu | B: ranks %llu records %llu neighbours %llu scans+stores %llu store drain %llu | C %llu | D %llu\n", eidx, NT, V2, 0u, cp[0], cp[1], cp[2], cp[3], cp[4], cp[7], cp[5], cp[6]);
 #endif
-#if !defined(HX_DP_PROF) && !defined(HX_GU_PROF)
+#if POA_PHASE_FLAVOUR == POA_PHASE_ROWSTATS
         if (stats) {   // statistics of the rows the next DP will run over
-            if (st_multi) atomicAdd(&ph[7], (unsigned long long)st_multi);
-            if (st_ring | st_fifth) atomicAdd(&ph[8], (unsigned long long)st_ring | ((unsigned long long)st_fifth << 40));   // (high bits: fifth-and-later predecessor entries, fetched inside the row)
-            if (st_far | st_wide) atomicAdd(&ph[9], (unsigned long long)st_far | ((unsigned long long)st_wide << 40));      // (high bits: rows with more than 4 predecessors)
-            if (tid == 0) { atomicAdd(&ph[6], (unsigned long long)V2); atomicAdd(&ph[10], (unsigned long long)ktot); atomicAdd(&ph[11], 1ull); }
+            if (st_multi) atomicAdd(&ph[PW_MULTI], (unsigned long long)st_multi);
+            if (st_ring | st_fifth) atomicAdd(&ph[PW_RING_FIFTH], pw_pack(st_ring, st_fifth, PW_SPLIT_REFS));   // (high bits: fifth-and-later predecessor entries, fetched inside the row)
+            if (st_far | st_wide) atomicAdd(&ph[PW_FAR_WIDE], pw_pack(st_far, st_wide, PW_SPLIT_REFS));      // (high bits: rows with more than 4 predecessors)
+            if (tid == 0) { atomicAdd(&ph[PW_ROWS], (unsigned long long)V2); atomicAdd(&ph[PW_KEPT], (unsigned long long)ktot); atomicAdd(&ph[PW_SEQS_NODES], pw_pack(1, 0, PW_SPLIT_HALF)); }
         }
 #endif
     }
