@@ -447,14 +447,15 @@ static hxk::PoaModesArgs general_args(const char* who, uint32_t n_sets, const ui
 // runs a validated request with the context's options, books its time and prints the debug line (tag: what that line calls the entry)
 static int poa_general_run(hx_ctx* c, const char* tag, hxk::PoaModesArgs& a, hxk::PoaModesOut& o) {
     HIPCHK(hipSetDevice(c->device));
-    a.slot_kb_cap = (uint32_t)std::max(0, c->opt.poa_modes_slot_kb); a.workspace_gb = c->opt.poa_workspace_gb; a.debug = c->opt.debug;
+    a.slot_kb_cap = (uint32_t)std::max(0, c->opt.poa_modes_slot_kb); a.aln_cap = (uint32_t)std::max(0, c->opt.poa_graph_aln_cap); a.workspace_gb = c->opt.poa_workspace_gb; a.debug = c->opt.debug;
     std::string err;
     if (hxk::poa_modes_run(c->stream, c->poa_modes_ws, a, o, err)) return fail(err);
     c->tm.ms[3] += o.kernel_ms; c->tm.launches[3] += o.launches;
     if (c->opt.debug) {
-        char rows[48] = "", part[48] = "";   // what an MSA or a weighted call adds to the line
+        char rows[96] = "", part[96] = "";   // what an MSA or a weighted call adds to the line
         if (a.msa) { snprintf(rows, sizeof rows, "%zu bytes of rows, ", o.msa.size()); snprintf(part, sizeof part, " (rows %.3f ms)", o.msa_rows_ms); }
         if (a.weighted) snprintf(part, sizeof part, " (coverage %.3f ms)", o.cov_ms);
+        if (a.graph) { snprintf(rows, sizeof rows, "%zu nodes, %zu edges, %zu pairs, ", o.node_base.size(), o.edge_w.size(), o.aln_pos.size()); snprintf(part, sizeof part, " (gather %.3f ms, %u sets rerun for their alignments)", o.gather_ms, o.aln_retried); }
         fprintf(stderr, "[hx] POA %s call%s: %u sets, %.3g cells, %skernels %.2f ms%s, %u sets rerun in a larger slot\n", tag, a.gap_model == 2 ? " (convex)" : a.gap_model == 1 ? " (affine)" : "", a.n_sets, (double)o.cells, rows, o.kernel_ms, part, o.retried);
     }
     return 0;
@@ -571,14 +572,20 @@ extern "C" int hx_poa_msa_convex(hx_ctx* c, uint32_t n_sets, const uint64_t* set
 
 // the consensus under per-base weights with coverage and profile: the general path's instances that keep the node of every base (all
 // three types), the weighted ones when weights are given
-static int poa_weighted_call(hx_ctx* c, const std::string& who, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const GapScores& sc,
-                             int want_coverage, int want_profile, hx_wcns_out* out) {
+// 0, or the error that names the first weight of 0
+static int check_weights(const std::string& who, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const uint8_t* weights) {
     if (weights)
         for (uint32_t i = 0; i < n_sets; i++)
             for (uint64_t k = set_off[i]; k < set_off[i + 1]; k++)
                 for (uint64_t p = seq_off[k]; p < seq_off[k + 1]; p++)
                     if (weights[p] == 0)
                         return fail(who + ": set " + std::to_string(i) + ", sequence " + std::to_string(k - set_off[i]) + ", position " + std::to_string(p - seq_off[k]) + ": a weight of 0 is not accepted (weights are 1..255)");
+    return 0;
+}
+
+static int poa_weighted_call(hx_ctx* c, const std::string& who, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const GapScores& sc,
+                             int want_coverage, int want_profile, hx_wcns_out* out) {
+    if (check_weights(who, n_sets, set_off, seq_off, weights)) return -1;
     hxk::PoaModesArgs a = general_args(who.c_str(), n_sets, set_off, seq_off, bases, sc);
     a.weighted = 1; a.weights = weights; a.want_coverage = want_coverage != 0; a.want_profile = want_profile != 0;
     std::vector<uint8_t> ones;
@@ -615,6 +622,41 @@ extern "C" int hx_poa_weighted_convex(hx_ctx* c, uint32_t n_sets, const uint64_t
     return poa_weighted_call(c, "hx_poa_weighted_convex", n_sets, set_off, seq_off, bases, weights, convex_scores(*cp), want_coverage, want_profile, out);
 }
 
+// the graph, the paths and the alignments of every set: the general path's graph instances (all three types) of the gap model the scores
+// name, chosen by the rules of the convex entries
+extern "C" int hx_poa_graph(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params* cp, hx_graph_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!cp) return fail("hx_poa_graph: no parameters");
+    if (check_convex_call("hx_poa_graph", *cp, set_off[n_sets])) return -1;
+    if (check_weights("hx_poa_graph", n_sets, set_off, seq_off, weights)) return -1;
+    GapScores sc = convex_scores(*cp);
+    if (convex_is_affine(c, *cp)) { sc.open2 = sc.extend2 = 0; sc.model = cp->gap_extend != cp->gap_open || c->opt.poa_affine; }   // the second piece never wins: the call takes the affine route
+    hxk::PoaModesArgs a = general_args("hx_poa_graph", n_sets, set_off, seq_off, bases, sc);
+    a.graph = 1; a.weights = weights;
+    hxk::PoaModesOut o;
+    if (poa_general_run(c, "graph", a, o)) return -1;
+    const uint64_t n_seq = set_off[n_sets];
+    out->n_set = n_sets; out->n_seq = n_seq;
+    out->node_off = dup(o.node_off.data(), (size_t)n_sets + 1);
+    out->node_base = dup(o.node_base.data(), o.node_base.size()); out->node_rank = dup(o.node_rank.data(), o.node_rank.size()); out->node_col = dup(o.node_col.data(), o.node_col.size());
+    out->edge_off = dup(o.edge_off.data(), (size_t)n_sets + 1);
+    out->edge_from = dup(o.edge_from.data(), o.edge_from.size()); out->edge_to = dup(o.edge_to.data(), o.edge_to.size()); out->edge_w = dup(o.edge_w.data(), o.edge_w.size());
+    out->base_node = dup(o.base_node.data(), o.base_node.size());
+    out->cns_off = dup(o.cns_off.data(), (size_t)n_sets + 1);
+    out->cns = dup(o.cns.data(), o.cns.size()); out->cns_node = dup(o.cns_node.data(), o.cns_node.size());
+    out->aln_off = dup(o.aln_off.data(), (size_t)n_seq + 1);
+    out->aln_node = dup(o.aln_node.data(), o.aln_node.size()); out->aln_pos = dup(o.aln_pos.data(), o.aln_pos.size()); out->aln_score = dup(o.aln_score.data(), o.aln_score.size());
+    out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
+    out->gather_kernel_ms = o.gather_ms; out->gather_kernel_bytes = o.gather_moved_bytes;
+    out->slot_reruns = o.retried; out->aln_reruns = o.aln_retried;
+    return 0;
+}
+
+extern "C" void hx_free_graph(hx_ctx*, hx_graph_out* o) {
+    free(o->node_off); free(o->node_base); free(o->node_rank); free(o->node_col); free(o->edge_off); free(o->edge_from); free(o->edge_to); free(o->edge_w); free(o->base_node);
+    free(o->cns_off); free(o->cns); free(o->cns_node); free(o->aln_off); free(o->aln_node); free(o->aln_pos); free(o->aln_score);
+    memset(o, 0, sizeof(*o));
+}
 extern "C" void hx_free_wcns(hx_ctx*, hx_wcns_out* o) { free(o->cns_off); free(o->cns); free(o->coverage); free(o->profile); memset(o, 0, sizeof(*o)); }
 extern "C" void hx_free_cns(hx_ctx*, hx_cns_out* o) { free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }
 extern "C" void hx_free_msa(hx_ctx*, hx_msa_out* o) { free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa); free(o->cns_off); free(o->cns); memset(o, 0, sizeof(*o)); }

@@ -36,6 +36,9 @@ struct PoaModesArgs {
     const uint8_t* weights = nullptr;    // weighted calls: a weight per base of `bases`, 1..255 (the caller has checked), or null: all 1
     int want_coverage = 0;               // weighted calls: the coverage of every consensus base in PoaModesOut
     int want_profile = 0;                // weighted calls: and the four letter counts of its column
+    int graph = 0;                       // 1: hx_poa_graph (the graph instances; weights as for a weighted call, or null), and the graph and the alignments in PoaModesOut
+    uint32_t aln_cap = 0;                // graph calls, first round only: a set's share of the alignment pool holds at most this many pairs (0: no cap); sets whose
+                                         // alignments outgrow it are rerun once with exactly the room they need
 };
 
 struct PoaModesOut {
@@ -55,6 +58,14 @@ struct PoaModesOut {
     std::vector<uint32_t> cov, prof;
     double cov_ms = 0;                   // the coverage kernels alone, with the clearing of their counters (part of kernel_ms)
     uint64_t cov_moved_bytes = 0;        // what they have to move
+    // graph calls: hx_graph_out's arrays (include/haslr_types.h)
+    std::vector<uint64_t> node_off, edge_off, aln_off;   // n_sets + 1, n_sets + 1, sequences + 1
+    std::string node_base;
+    std::vector<uint32_t> node_rank, node_col, edge_from, edge_to, base_node, cns_node;
+    std::vector<int32_t> edge_w, aln_node, aln_pos, aln_score;
+    uint32_t aln_retried = 0;            // sets rerun because their alignments outgrew their share of the pool
+    double gather_ms = 0;                // the gather kernel alone (part of kernel_ms)
+    uint64_t gather_moved_bytes = 0;     // what it has to move: every dense element read once and written once
 };
 
 // 0 = ok, else -1 with the reason in err

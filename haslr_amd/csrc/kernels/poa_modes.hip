@@ -28,10 +28,18 @@
 // the heaviest bundle sees spoa's weighted edges; two grid-wide kernels (k_cov_hist, k_cov_gather) count the bases per column and letter and
 // pick the counts at the consensus bases' columns.
 //
-// Layout: the DP and traceback of the three gap models are poa_modes_dp.inl, the columns, row text and coverage poa_modes_out.inl; this file keeps
-// the work of one set (run_set), the kernel, the instance table and the host driver (poa_modes_run, in named stages).
+// The graph itself and the alignments (hx_poa_graph; DESIGN.md "Graph and alignment output") are a third flag on top of the weighted one: after
+// every traceback the workgroup copies the alignment's pairs and the end cell's score into the call's alignment pool, after the last sort it
+// writes the set's nodes (code, rank, column), its edges in creation order and the nodes of the consensus, and base_col stays node ids. A
+// grid-wide kernel (k_graph_gather) moves all of it into dense arrays once the host knows the sizes. The pool is the one array sized from an
+// estimate: a set whose alignments outgrow its share finishes, reports what it needed, and is rerun once with exactly that room.
+//
+// Layout: the DP and traceback of the three gap models are poa_modes_dp.inl, the columns, row text, coverage and the graph output's helpers
+// and gather poa_modes_out.inl; this file keeps the work of one set (run_set), the kernel, the instance table and the host driver
+// (poa_modes_run, in named stages).
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <numeric>
 
 #include "kernels.h"
@@ -49,10 +57,24 @@ namespace {
 
 enum { MT_SW = 0, MT_NW = 1, MT_OV = 2 };
 enum { GM_LINEAR = 0, GM_AFFINE = 1, GM_CONVEX = 2 };   // PoaModesArgs::gap_model
-enum { MS_OK = 0, MS_H_OVERFLOW = 1, MS_GRAPH_OVERFLOW = 2 };
+enum { MS_OK = 0, MS_H_OVERFLOW = 1, MS_GRAPH_OVERFLOW = 2, MS_ALN_OVERFLOW = 3 };   // (3: done, but its alignments outgrew their share of the pool)
 constexpr uint32_t MAX_SET_BASES = (1u << 21) - 2;   // node ids are packed in 21 bits (+1) in the node records of poa_graph.inl
 
 struct MSet { uint64_t seq_begin, sum_len, cns_off; uint32_t nseq, lmax; };
+
+// What the graph instances (hx_poa_graph) write beside the consensus. The alignment pool holds the (node, position) pairs of every
+// alignment of a set, back to front as the traceback leaves them, one alignment after the other from the set's share on (aln_at, aln_room
+// pairs); a set stores nothing beyond its share and reports in aln_need what all of its alignments hold. Per sequence of the call: the
+// pairs of its alignment and the score of its end cell. The node and edge arrays need no estimate: a set has at most one node per base and
+// one edge per base and sequence, so its nodes start at its first base's global offset and its edges at that offset plus its first
+// sequence's index.
+struct GraphOutArgs {
+    int32_t *aln_node, *aln_pos; const uint64_t* aln_at; const uint32_t* aln_room; uint32_t* aln_need;
+    uint32_t* aln_cnt; int32_t* aln_score;
+    uint8_t* node_code; uint32_t *node_rank, *node_col, *n_nodes;
+    uint32_t *edge_from, *edge_to; int32_t* edge_w; uint32_t* n_edges;
+    uint32_t* cns_node;   // beside cns
+};
 
 struct MArgs {
     const MSet* sets; const uint32_t* order; uint32_t n_items; uint32_t* counter;
@@ -66,6 +88,7 @@ struct MArgs {
     uint32_t *base_col, *n_cols, *cns_col;
     const uint8_t* wts;   // weighted instances only: the weight of every base of the call (1..255), beside codes
     int32_t q, c;         // convex instances only: gap open and gap extend of the second piece
+    GraphOutArgs go;      // graph instances only (poa_modes_out.inl)
 };
 
 // one row of the MSA text: its columns (rising) start at cols[src], its letters at codes[src] (a sequence) or cns[src] (the consensus row)
@@ -145,12 +168,12 @@ __device__ void order_rows(G& g, const uint32_t V, uint32_t* s_scan) {
     __syncthreads();
 }
 
-struct Shared { uint32_t item, V, E, fail; int best; unsigned long long key; };
+struct Shared { uint32_t item, V, E, fail; int best; uint32_t na /* graph instances: the pairs the traceback left */; unsigned long long key; };
 
 #include "poa_modes_dp.inl"     // DP and traceback, linear, affine and convex gaps
-#include "poa_modes_out.inl"    // MSA columns and row text, base weights, coverage
+#include "poa_modes_out.inl"    // MSA columns and row text, base weights, coverage, graph and alignment output
 
-template <int NT, int CPL, int GM, bool MSA, bool WTS>
+template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH>
 __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Shared& sh, int* s_wtot, uint32_t* s_scan) {
     const uint32_t t = threadIdx.x;
     const MSet S = a.sets[set];
@@ -161,6 +184,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     const uint64_t hcap = (a.slot_bytes - pools) / sizeof(Cell<GM>);   // cells the slot holds
     uint32_t V = 0, E = 0, non_empty = 0;
     unsigned long long cells = 0;
+    uint64_t aln_used = 0;   // graph instances: the pairs of the set's alignments so far
     for (uint32_t k = 0; k < S.nseq; k++) {
         const uint64_t b = a.soff[S.seq_begin + k];
         const uint32_t L = (uint32_t)(a.soff[S.seq_begin + k + 1] - b);
@@ -172,8 +196,10 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
             if ((uint64_t)(V + 1) * (L + 1) > hcap) { if (t == 0) { a.status[set] = MS_H_OVERFLOW; a.vseen[set] = V; } return; }
             cells += (unsigned long long)V * L;
             uint32_t bi, bj;
+            if (GRAPH) mark_pairs<NT>(g, V);   // (dp_rows' barriers lie between this and the traceback)
             dp_rows<NT, CPL, GM>(g, H, V, s, L, a, sh, s_wtot, &bi, &bj);
             if (t == 0 && bi) na = traceback<GM>(g, H, s, L, bi, bj, a);
+            if (GRAPH && t == 0) sh.na = bi ? keep_score(g, V, na, sh.best, a.go.aln_score + S.seq_begin + k) : 0u;   // (sh.best: dp_rows' end-cell score)
         }
         if (t == 0) {
             uint32_t v = V, e = E;
@@ -181,6 +207,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
             sh.V = v; sh.E = e; sh.fail = !ok;
         }
         __syncthreads();
+        if (GRAPH && V) aln_used += keep_pairs<NT>(g, sh.na, a.go, set, S.seq_begin + k, aln_used);   // (V: the graph before the add)
         V = sh.V; E = sh.E;
         if (sh.fail) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
         if (MSA) for (uint32_t i = t; i < L; i += NT) a.base_col[b + i] = path[i];   // (node ids never change: a rerun set rewrites its part)
@@ -192,14 +219,20 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
         uint32_t* colr = g.stack;
         const uint32_t ncols = msa_columns<NT>(g, V, colr, s_scan);
         const uint64_t b0 = a.soff[S.seq_begin];
-        for (uint64_t i = t; i < S.sum_len; i += NT) a.base_col[b0 + i] = colr[g.node2rank[a.base_col[b0 + i]]];
+        // (a graph instance keeps base_col as node ids: there the column travels with the node)
+        if (GRAPH) keep_graph<NT>(g, V, E, colr, a.go, set, b0, b0 + S.seq_begin);
+        else for (uint64_t i = t; i < S.sum_len; i += NT) a.base_col[b0 + i] = colr[g.node2rank[a.base_col[b0 + i]]];
         if (t < 64) {
             uint32_t len = 0, end_rank = 0;
             if (non_empty) {
                 len = consensus_wave_end(g, V, a.cns + S.cns_off, &end_rank);
                 if (a.cns_col) consensus_columns(g, end_rank, len, colr, (uint32_t*)g.aln_pos, a.cns_col + S.cns_off);
+                if (GRAPH) consensus_columns(g, end_rank, len, g.rank2node, (uint32_t*)g.aln_pos, a.go.cns_node + S.cns_off);   // (the same walk, the rank's node in place of its column)
             }
-            if (t == 0) { a.cns_len[set] = len; a.n_cols[set] = ncols; a.cells[set] = cells; a.status[set] = MS_OK; }
+            if (t == 0) {
+                a.cns_len[set] = len; a.n_cols[set] = ncols; a.cells[set] = cells; a.status[set] = MS_OK;
+                if (GRAPH) { a.go.aln_need[set] = (uint32_t)min(aln_used, (uint64_t)0xffffffffu); if (aln_used > a.go.aln_room[set]) a.status[set] = MS_ALN_OVERFLOW; }
+            }
         }
     } else if (t < 64) {
         const uint32_t len = non_empty ? consensus_wave(g, V, a.cns + S.cns_off) : 0u;
@@ -208,7 +241,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     __syncthreads();   // the slot is free for the next set
 }
 
-template <int NT, int CPL, int GM, bool MSA, bool WTS>
+template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH = false>
 __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
     __shared__ Shared sh;
     __shared__ int s_wtot[(GM == GM_CONVEX ? 2 : 1) * (NT / 64)];   // per wave the total of its row scan (convex: of its two)
@@ -220,15 +253,17 @@ __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
         const uint32_t q = sh.item;
         __syncthreads();
         if (q >= a.n_items) return;
-        run_set<NT, CPL, GM, MSA, WTS>(a, a.order[q], slot, sh, s_wtot, s_scan);
+        run_set<NT, CPL, GM, MSA, WTS, GRAPH>(a, a.order[q], slot, sh, s_wtot, s_scan);
     }
 }
 
 // the instances: workgroup lanes x columns per lane; a set goes to the first whose NT x CPL columns hold its longest sequence + 1.
 // Each comes in three variants: the consensus alone (a consensus-only call runs the code it ran before the MSA existed), with the node of
-// every base kept (the MSA; coverage needs it too), and with base weights applied on top of that (hx_poa_weighted with weights).
-struct Inst { int nt, cpl; const void* variant[3]; };
-#define HX_INST(GM, NT, CPL) {NT, CPL, {(const void*)k_poa_general<NT, CPL, GM, false, false>, (const void*)k_poa_general<NT, CPL, GM, true, false>, (const void*)k_poa_general<NT, CPL, GM, true, true>}}
+// every base kept (the MSA; coverage needs it too), with base weights applied on top of that (hx_poa_weighted with weights), and with the
+// graph and the alignments written out on top of that (hx_poa_graph; without weights it runs on weights of 1, which add nothing to an edge).
+struct Inst { int nt, cpl; const void* variant[4]; };
+#define HX_INST(GM, NT, CPL) {NT, CPL, {(const void*)k_poa_general<NT, CPL, GM, false, false>, (const void*)k_poa_general<NT, CPL, GM, true, false>, (const void*)k_poa_general<NT, CPL, GM, true, true>, \
+                                        (const void*)k_poa_general<NT, CPL, GM, true, true, true>}}
 constexpr int N_INST = 4;
 // by gap model (GM_LINEAR, GM_AFFINE, GM_CONVEX). The affine instances keep two accumulators per column (diagonal and F): 16 columns per
 // lane throughout, more lanes instead. The convex ones keep three (diagonal, F and O) and stop at 512 lanes, two waves per SIMD with up to
@@ -242,7 +277,7 @@ const Inst kInst[3][N_INST] = {
 constexpr uint32_t MAX_LEN[3] = {1024 * 32 - 1, 1024 * 16 - 1, 512 * 16 - 1};
 constexpr uint64_t CELL_BYTES[3] = {4, 8, 12};   // of a cell of H by gap model: what the kernels take as sizeof(Cell<GM>)
 static_assert(CELL_BYTES[GM_LINEAR] == sizeof(Cell<GM_LINEAR>) && CELL_BYTES[GM_AFFINE] == sizeof(Cell<GM_AFFINE>) && CELL_BYTES[GM_CONVEX] == sizeof(Cell<GM_CONVEX>), "CELL_BYTES against the cell types of poa_modes_dp.inl");
-inline const void* fn(const Inst& inst, bool cols, bool weighted) { return inst.variant[weighted ? 2 : cols ? 1 : 0]; }
+inline const void* fn(const Inst& inst, bool cols, bool weighted, bool graph) { return inst.variant[graph ? 3 : weighted ? 2 : cols ? 1 : 0]; }
 
 template <class T> struct Buf {   // device buffer of one call
     T* p = nullptr;
@@ -281,7 +316,8 @@ struct Run {
     const int gm = a.gap_model;                             // GM_LINEAR, GM_AFFINE or GM_CONVEX (the entry points set nothing else)
     const bool msa = a.msa != 0;
     const bool wtd = a.weighted != 0;                        // hx_poa_weighted: the node of every base is kept, as for the MSA
-    const bool cols = msa || wtd;
+    const bool graph = a.graph != 0;                         // hx_poa_graph: the node of every base stays a node, the graph and the alignments are written out
+    const bool cols = msa || wtd || graph;
     const bool want_cov = wtd && (a.want_coverage || a.want_profile);
     const Inst* const inst = kInst[gm];
     const uint64_t cell_bytes = CELL_BYTES[gm];
@@ -296,11 +332,19 @@ struct Run {
     uint64_t budget = 0;
     Buf<MSet> d_sets; Buf<uint8_t> d_codes; Buf<uint64_t> d_soff; Buf<uint32_t> d_order, d_counter, d_status, d_vseen, d_cns_len; Buf<unsigned long long> d_cells; Buf<char> d_cns;
     Buf<uint32_t> d_base_col, d_n_cols, d_cns_col;   // MSA and weighted calls only
-    Buf<uint8_t> d_wts;                              // weighted calls with weights only: a byte per base
+    Buf<uint8_t> d_wts;                              // weighted calls with weights only: a byte per base (graph calls: always, 1 without weights)
+    // graph calls only: what GraphOutArgs points to. The alignment pool is one allocation per round (a rerun set's share lies in a later
+    // round's pool; pool_of / aln_at tell where a set's pairs are after the last round it ran in)
+    struct Pool { Buf<int32_t> node, pos; };
+    std::vector<std::unique_ptr<Pool>> pools;
+    std::vector<uint32_t> pool_of, aln_room, aln_rerun;   // per set: the round of its share, the share in pairs, 1 once it was rerun for want of room
+    std::vector<uint64_t> aln_at;
+    Buf<uint64_t> d_aln_at; Buf<uint32_t> d_aln_room, d_aln_need, d_aln_cnt, d_n_nodes, d_n_edges, d_node_rank, d_node_col, d_edge_from, d_edge_to, d_cns_node;
+    Buf<int32_t> d_aln_score, d_edge_w; Buf<uint8_t> d_node_code;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~Run() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
 
-    const void* fn_of(int k) const { return fn(inst[k], cols, d_wts.p != nullptr); }
+    const void* fn_of(int k) const { return fn(inst[k], cols, d_wts.p != nullptr, graph); }
     uint64_t pools_of(uint32_t i) const { const MSet& S = sets[i]; return carve_pools(nullptr, S.sum_len, S.nseq, S.lmax, nullptr, nullptr, nullptr); }
 
     // runs f (0 = ok) between two events, waits for it, and adds the milliseconds it took on the device to *ms
@@ -348,9 +392,38 @@ struct Run {
             MCHK(hipMemsetAsync(d_n_cols.p, 0, std::max<size_t>(1, ns) * 4, s));
             if (msa ? a.include_consensus != 0 : want_cov) MCHK(d_cns_col.alloc(cns_off[ns]));
         }
-        if (wtd && a.weights) {
+        if ((wtd || graph) && a.weights) {
             MCHK(d_wts.alloc(nb));
             MCHK(hipMemcpyAsync(d_wts.p, a.weights, nb, hipMemcpyHostToDevice, s));
+        }
+        if (graph) {
+            if (!a.weights) { MCHK(d_wts.alloc(nb)); MCHK(hipMemsetAsync(d_wts.p, 1, std::max<uint64_t>(1, nb), s)); }
+            const uint64_t ne = nb + nseq;   // (a set's edges start at its first base's offset plus its first sequence's index)
+            MCHK(d_aln_at.alloc(ns)); MCHK(d_aln_room.alloc(ns)); MCHK(d_aln_need.alloc(ns)); MCHK(d_aln_cnt.alloc(nseq)); MCHK(d_aln_score.alloc(nseq));
+            MCHK(d_n_nodes.alloc(ns)); MCHK(d_n_edges.alloc(ns)); MCHK(d_node_code.alloc(nb)); MCHK(d_node_rank.alloc(nb)); MCHK(d_node_col.alloc(nb));
+            MCHK(d_edge_from.alloc(ne)); MCHK(d_edge_to.alloc(ne)); MCHK(d_edge_w.alloc(ne)); MCHK(d_cns_node.alloc(cns_off[ns]));
+            // (a sequence that meets no DP writes neither: its alignment is empty, its score 0; a set without a base writes no counts)
+            MCHK(hipMemsetAsync(d_aln_cnt.p, 0, std::max<uint64_t>(1, nseq) * 4, s)); MCHK(hipMemsetAsync(d_aln_score.p, 0, std::max<uint64_t>(1, nseq) * 4, s));
+            MCHK(hipMemsetAsync(d_n_nodes.p, 0, std::max<size_t>(1, ns) * 4, s)); MCHK(hipMemsetAsync(d_n_edges.p, 0, std::max<size_t>(1, ns) * 4, s));
+            // The share of the alignment pool a set gets in its first round. The alignment of a sequence of L bases holds one pair per base
+            // and one per graph node the walk passes without a base; under kNW the walk spans the graph from a source to a sink, which for
+            // copies of one template is about the longest sequence. So: max(L, longest) pairs, an eighth more for the nodes passed without
+            // a base (the copy's deletions against that path: 3 % in the error models of the tests and the bench tool, a quarter of that
+            // room), and 16 for short sequences, per sequence after the first non-empty one (DESIGN.md "Graph and alignment output" has
+            // the reasoning and the measured reruns)
+            pool_of.assign(ns, 0); aln_room.assign(ns, 0); aln_rerun.assign(ns, 0); aln_at.assign(ns, 0);
+            for (uint32_t i = 0; i < ns; i++) {
+                uint64_t est = 0;
+                bool seen = false;
+                for (uint64_t k = a.set_off[i]; k < a.set_off[i + 1]; k++) {
+                    const uint64_t L = a.seq_off[k + 1] - a.seq_off[k];
+                    if (L == 0) continue;
+                    if (seen) { const uint64_t span = std::max<uint64_t>(L, sets[i].lmax); est += span + span / 8 + 16; }
+                    seen = true;
+                }
+                aln_room[i] = (uint32_t)std::min<uint64_t>(est, 0xfffffffeu);
+                if (a.aln_cap) aln_room[i] = std::min(aln_room[i], a.aln_cap);   // (test switch: forces the overflow and the rerun with the exact room)
+            }
         }
         // H is sized from an estimate of the graph's final size (noisy copies add about a tenth of their length each); a set that outgrows its
         // slot comes back and is rerun with twice the room (or the room for what it had when it stopped, doubled), the worst case at most
@@ -404,6 +477,22 @@ struct Run {
             if (e != hipSuccess) { ws.p = nullptr; err = who + ": the workspace of " + std::to_string(total) + " bytes could not be allocated: " + hipGetErrorString(e); return -1; }
             ws.cap = total;
         }
+        GraphOutArgs go{};
+        if (graph) {   // this round's pool: the shares of its sets side by side
+            pools.emplace_back(new Pool);
+            uint64_t at = 0;
+            for (uint32_t i : todo) { pool_of[i] = (uint32_t)pools.size() - 1; aln_at[i] = at; at += aln_room[i]; }
+            Pool& P = *pools.back();
+            {
+                hipError_t e = P.node.alloc(at);
+                if (e == hipSuccess) e = P.pos.alloc(at);
+                if (e != hipSuccess) { err = who + ": the alignment pool of " + std::to_string(at) + " pairs could not be allocated on the device: " + hipGetErrorString(e); return -1; }
+            }
+            MCHK(hipMemcpyAsync(d_aln_at.p, aln_at.data(), ns * 8, hipMemcpyHostToDevice, s));
+            MCHK(hipMemcpyAsync(d_aln_room.p, aln_room.data(), ns * 4, hipMemcpyHostToDevice, s));
+            go = GraphOutArgs{P.node.p, P.pos.p, d_aln_at.p, d_aln_room.p, d_aln_need.p, d_aln_cnt.p, d_aln_score.p, d_node_code.p, d_node_rank.p, d_node_col.p, d_n_nodes.p,
+                              d_edge_from.p, d_edge_to.p, d_edge_w.p, d_n_edges.p, d_cns_node.p};
+        }
         MCHK(hipMemcpyAsync(d_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, s));
         MCHK(hipMemsetAsync(d_counter.p, 0, N_INST * 4, s));
         MCHK(hipMemsetAsync(d_status.p, 0xff, std::max<size_t>(1, ns) * 4, s));
@@ -413,7 +502,7 @@ struct Run {
                     if (by[k].empty()) continue;
                     MArgs q{d_sets.p, d_order.p + base[k], (uint32_t)by[k].size(), d_counter.p + k, d_codes.p, d_soff.p, (uint8_t*)ws.p, slot[k],
                             a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p, a.gap_extend,
-                            d_base_col.p, d_n_cols.p, d_cns_col.p, d_wts.p, a.gap_open2, a.gap_extend2};
+                            d_base_col.p, d_n_cols.p, d_cns_col.p, d_wts.p, a.gap_open2, a.gap_extend2, go};
                     void* kargs[] = {&q};
                     MCHK(hipLaunchKernel(fn_of(k), dim3(nslots[k]), dim3((uint32_t)inst[k].nt), kargs, 0, s));
                     o.launches++;
@@ -425,9 +514,17 @@ struct Run {
         std::vector<uint32_t> status(ns), vseen(ns);
         MCHK(hipMemcpy(status.data(), d_status.p, ns * 4, hipMemcpyDeviceToHost));
         MCHK(hipMemcpy(vseen.data(), d_vseen.p, ns * 4, hipMemcpyDeviceToHost));
-        std::vector<uint32_t> next;
+        std::vector<uint32_t> next, pairs;   // (pairs: what the alignments of a set hold in all)
+        if (graph) { pairs.resize(ns); MCHK(hipMemcpy(pairs.data(), d_aln_need.p, ns * 4, hipMemcpyDeviceToHost)); }
         for (uint32_t i : todo) {
             if (status[i] == MS_OK) continue;
+            if (graph && status[i] == MS_ALN_OVERFLOW) {   // done, but for its alignments: once more, with exactly the room they need
+                if (aln_rerun[i] || pairs[i] == 0xffffffffu) { err = who + ": set " + std::to_string(i) + " failed on the device (its alignments hold " + std::to_string(pairs[i]) + " pairs, its share of the pool " + std::to_string(aln_room[i]) + ")"; return -1; }
+                aln_rerun[i] = 1; aln_room[i] = pairs[i];
+                next.push_back(i);
+                o.aln_retried++;
+                continue;
+            }
             const bool capped = first && a.slot_kb_cap;   // (a capped slot can be short of even the worst case)
             if (status[i] != MS_H_OVERFLOW || (vest[i] >= sets[i].sum_len && !capped)) { err = who + ": set " + std::to_string(i) + " failed on the device (status " + std::to_string((int)status[i]) + ")"; return -1; }
             vest[i] = std::min<uint64_t>(sets[i].sum_len, std::max<uint64_t>(2 * vest[i], 2 * (uint64_t)vseen[i] + 64));
@@ -504,6 +601,62 @@ struct Run {
         return 0;
     }
 
+    // ---- the graph and the alignments: now that the host knows the nodes, edges and pairs of every set, one grid-wide kernel moves them
+    // from the worst-case places run_set wrote them to into dense arrays, set after set (codes become letters, an alignment's pairs are
+    // turned into forward order), and only those are downloaded. Built here, after the last round: a set that was rerun is taken from
+    // the round it finished in, once.
+    int graph_out() {
+        std::vector<uint32_t> nv(ns), ne(ns), cnt(nseq);
+        o.aln_score.assign(nseq, 0);
+        MCHK(hipMemcpy(nv.data(), d_n_nodes.p, ns * 4, hipMemcpyDeviceToHost));
+        MCHK(hipMemcpy(ne.data(), d_n_edges.p, ns * 4, hipMemcpyDeviceToHost));
+        MCHK(hipMemcpy(cnt.data(), d_aln_cnt.p, nseq * 4, hipMemcpyDeviceToHost));
+        MCHK(hipMemcpy(o.aln_score.data(), d_aln_score.p, nseq * 4, hipMemcpyDeviceToHost));
+        o.node_off.assign((size_t)ns + 1, 0); o.edge_off.assign((size_t)ns + 1, 0); o.aln_off.assign((size_t)nseq + 1, 0);
+        RowList<GRow> rows;
+        for (uint32_t i = 0; i < ns; i++) {
+            const uint64_t b0 = a.seq_off[a.set_off[i]];
+            o.node_off[i + 1] = o.node_off[i] + nv[i]; o.edge_off[i + 1] = o.edge_off[i] + ne[i];
+            if (nv[i]) rows.add(GRow{nullptr, nullptr, b0, o.node_off[i], nv[i], GR_NODES}, nv[i]);
+            if (ne[i]) rows.add(GRow{nullptr, nullptr, b0 + a.set_off[i], o.edge_off[i], ne[i], GR_EDGES}, ne[i]);
+            if (len[i]) rows.add(GRow{nullptr, nullptr, cns_off[i], o.cns_off[i], len[i], GR_CNS}, len[i]);
+            uint64_t at = sets[i].sum_len ? aln_at[i] : 0;
+            for (uint64_t k = a.set_off[i]; k < a.set_off[i + 1]; k++) {
+                o.aln_off[k + 1] = o.aln_off[k] + cnt[k];
+                if (cnt[k]) { const Pool& P = *pools[pool_of[i]]; rows.add(GRow{P.node.p, P.pos.p, at, o.aln_off[k], cnt[k], GR_ALN}, cnt[k]); }
+                at += cnt[k];
+            }
+            if (sets[i].sum_len && at - aln_at[i] > aln_room[i]) { err = who + ": internal error (the alignments of set " + std::to_string(i) + " outgrew their share of the pool)"; return -1; }
+        }
+        if (rows.too_many()) { err = who + ": too many sequences"; return -1; }
+        const uint64_t NV = o.node_off[ns], NE = o.edge_off[ns], NC = o.cns.size(), NP = o.aln_off[nseq];
+        o.node_base.resize(NV); o.node_rank.resize(NV); o.node_col.resize(NV);
+        o.edge_from.resize(NE); o.edge_to.resize(NE); o.edge_w.resize(NE);
+        o.cns_node.resize(NC); o.aln_node.resize(NP); o.aln_pos.resize(NP);
+        o.base_node.resize(nb);
+        if (nb) MCHK(hipMemcpy(o.base_node.data(), d_base_col.p, nb * 4, hipMemcpyDeviceToHost));   // (dense as it is: the layout of the call's bases)
+        if (rows.n_chunks() == 0) return 0;
+        Buf<char> o_base; Buf<uint32_t> o_rank, o_col, o_from, o_to, o_cns; Buf<int32_t> o_w, o_an, o_ap;
+        MCHK(o_base.alloc(NV)); MCHK(o_rank.alloc(NV)); MCHK(o_col.alloc(NV)); MCHK(o_from.alloc(NE)); MCHK(o_to.alloc(NE)); MCHK(o_w.alloc(NE));
+        MCHK(o_cns.alloc(NC)); MCHK(o_an.alloc(NP)); MCHK(o_ap.alloc(NP));
+        MCHK(rows.upload(s));
+        const GatherArgs ga{d_node_code.p, d_node_rank.p, d_node_col.p, d_edge_from.p, d_edge_to.p, d_edge_w.p, d_cns_node.p,
+                            o_base.p, o_rank.p, o_col.p, o_from.p, o_to.p, o_w.p, o_cns.p, o_an.p, o_ap.p};
+        float ms = 0;
+        if (timed(&ms, [&] {
+                k_graph_gather<<<rows.blocks(), 256, 0, s>>>(rows.d_rows.p, rows.d_chunks.p, rows.n_chunks(), ga);
+                MCHK(hipGetLastError());
+                return 0;
+            })) return -1;
+        o.gather_ms = ms; o.kernel_ms += ms; o.launches++;
+        o.gather_moved_bytes = 2 * (9 * NV + 12 * NE + 4 * NC + 8 * NP);   // every element read once and written once
+        if (NV) { MCHK(hipMemcpy(&o.node_base[0], o_base.p, NV, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(o.node_rank.data(), o_rank.p, NV * 4, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(o.node_col.data(), o_col.p, NV * 4, hipMemcpyDeviceToHost)); }
+        if (NE) { MCHK(hipMemcpy(o.edge_from.data(), o_from.p, NE * 4, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(o.edge_to.data(), o_to.p, NE * 4, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(o.edge_w.data(), o_w.p, NE * 4, hipMemcpyDeviceToHost)); }
+        if (NC) MCHK(hipMemcpy(o.cns_node.data(), o_cns.p, NC * 4, hipMemcpyDeviceToHost));
+        if (NP) { MCHK(hipMemcpy(o.aln_node.data(), o_an.p, NP * 4, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(o.aln_pos.data(), o_ap.p, NP * 4, hipMemcpyDeviceToHost)); }
+        return 0;
+    }
+
     // ---- the MSA text: now that the columns of every set are known, the rows' places (set i = rows x n_cols bytes, row-major) and the
     // work list of k_msa_rows
     int msa_text() {
@@ -554,6 +707,7 @@ int poa_modes_run(hipStream_t s, PoaModesWs& ws, const PoaModesArgs& a, PoaModes
         if (r.round(first)) return -1;
     if (r.consensus()) return -1;
     if (r.want_cov && r.coverage()) return -1;
+    if (r.graph) return r.graph_out();
     return r.msa ? r.msa_text() : 0;
 }
 

@@ -1,6 +1,6 @@
 // poa_modes_out.inl - what the general POA path (kernels/poa_modes.hip) writes beside the consensus text: the columns of the multiple sequence
-// alignment and its row text, the base weights on the graph's edges, and the coverage of the consensus bases. Included inside that file's
-// anonymous namespace, after MRow and block_excl_sum.
+// alignment and its row text, the base weights on the graph's edges, the coverage of the consensus bases, and the graph and the alignments
+// themselves. Included inside that file's anonymous namespace, after MRow, GraphOutArgs and block_excl_sum.
 
 // ---- MSA output (DESIGN.md "General POA path", "MSA output") ----
 // The columns of spoa's generate_multiple_sequence_alignment on the final rank order (order_rows leaves aligned nodes contiguous): rank r
@@ -159,4 +159,66 @@ __global__ __launch_bounds__(256) void k_cov_gather(const CRow* rows, const uint
     }
     cov[R.dst + i] = n[0] + n[1] + n[2] + n[3];
     if (prof) { uint32_t* p = prof + 4 * (R.dst + i); p[0] = n[0]; p[1] = n[1]; p[2] = n[2]; p[3] = n[3]; }
+}
+
+// ---- graph and alignment output (DESIGN.md "General POA path", "Graph and alignment output") ----
+// The traceback reports 0 pairs for an alignment that holds no sequence position (add_alignment then adds the sequence as a chain), but the
+// output keeps such an alignment as the walk produced it. Such a walk only ever steps up a row, so it leaves at most V pairs, each with
+// position -1: with the first V + 1 positions set to -2 beforehand, the first -2 left tells where it ended. All lanes, before dp_rows.
+constexpr int32_t ALN_UNSET = -2;
+template <int NT>
+__device__ void mark_pairs(G& g, const uint32_t V) {
+    for (uint32_t i = threadIdx.x; i <= V; i += NT) g.aln_pos[i] = ALN_UNSET;
+}
+
+// thread 0, after the traceback returned na: stores the end cell's score and returns the pairs the walk left in aln_node / aln_pos
+__device__ uint32_t keep_score(const G& g, const uint32_t V, uint32_t na, const int32_t score, int32_t* out) {
+    *out = score;
+    if (na == 0) while (na <= V && g.aln_pos[na] != ALN_UNSET) na++;
+    return na;
+}
+
+// all lanes, after add_alignment's barrier: the na pairs of sequence `seq` (of the call) go to the set's share of the pool from `used` on,
+// as far as they fit. Returns na.
+template <int NT>
+__device__ uint32_t keep_pairs(const G& g, const uint32_t na, const GraphOutArgs& o, const uint32_t set, const uint64_t seq, const uint64_t used) {
+    const uint64_t at = o.aln_at[set], room = o.aln_room[set];
+    for (uint32_t i = threadIdx.x; i < na; i += NT)
+        if (used + i < room) { o.aln_node[at + used + i] = g.aln_node[i]; o.aln_pos[at + used + i] = g.aln_pos[i]; }
+    if (threadIdx.x == 0) o.aln_cnt[seq] = na;
+    return na;
+}
+
+// all lanes, after the last sort and msa_columns: the set's nodes (code, rank, column) from nb on, its edges in creation order from eb on
+template <int NT>
+__device__ void keep_graph(const G& g, const uint32_t V, const uint32_t E, const uint32_t* colr, const GraphOutArgs& o, const uint32_t set, const uint64_t nb, const uint64_t eb) {
+    const uint32_t t = threadIdx.x;
+    for (uint32_t n = t; n < V; n += NT) { const uint32_t r = g.node2rank[n]; o.node_code[nb + n] = g.code[n]; o.node_rank[nb + n] = r; o.node_col[nb + n] = colr[r]; }
+    for (uint32_t e = t; e < E; e += NT) { o.edge_from[eb + e] = g.e_from[e]; o.edge_to[eb + e] = g.e_to[e]; o.edge_w[eb + e] = g.e_w[e]; }
+    if (t == 0) { o.n_nodes[set] = V; o.n_edges[set] = E; }
+}
+
+// one run of elements that k_graph_gather moves from where run_set left them (src) to its place in the dense output (dst): the nodes of a
+// set, its edges, the nodes of its consensus, or the pairs of one alignment (pa / pb: the pool's two arrays; read back to front)
+enum { GR_NODES = 0, GR_EDGES = 1, GR_CNS = 2, GR_ALN = 3 };
+struct GRow { const int32_t *pa, *pb; uint64_t src, dst; uint32_t len, kind; };
+struct GatherArgs {
+    const uint8_t* node_code; const uint32_t *node_rank, *node_col, *edge_from, *edge_to; const int32_t* edge_w; const uint32_t* cns_node;
+    char* o_base; uint32_t *o_rank, *o_col, *o_from, *o_to; int32_t* o_w; uint32_t* o_cns_node; int32_t *o_aln_node, *o_aln_pos;
+};
+
+// The dense output of one call, grid-wide: a wavefront takes 64 consecutive elements of one run; reads and writes are contiguous (an
+// alignment's are read in falling, written in rising order). Codes become letters here.
+__global__ __launch_bounds__(256) void k_graph_gather(const GRow* rows, const uint2* chunks, const uint32_t n_chunks, const GatherArgs a) {
+    const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (w >= n_chunks) return;
+    const uint2 ch = chunks[w];
+    const GRow R = rows[ch.x];
+    const uint32_t i = ch.y + lane;
+    if (i >= R.len) return;
+    const uint64_t s = R.src + i, d = R.dst + i;
+    if (R.kind == GR_NODES) { a.o_base[d] = "ACGT"[a.node_code[s] & 3]; a.o_rank[d] = a.node_rank[s]; a.o_col[d] = a.node_col[s]; }
+    else if (R.kind == GR_EDGES) { a.o_from[d] = a.edge_from[s]; a.o_to[d] = a.edge_to[s]; a.o_w[d] = a.edge_w[s]; }
+    else if (R.kind == GR_CNS) a.o_cns_node[d] = a.cns_node[s];
+    else { const uint64_t b = R.src + (R.len - 1u - i); a.o_aln_node[d] = R.pa[b]; a.o_aln_pos[d] = R.pb[b]; }
 }

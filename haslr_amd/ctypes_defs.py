@@ -179,6 +179,17 @@ def wcns_to_lists(o):
     return cns, cov, prof
 
 
+i32p = C.POINTER(C.c_int32)
+
+
+class GraphOut(C.Structure):
+    _fields_ = [("n_set", C.c_uint32), ("n_seq", C.c_uint64), ("node_off", u64p), ("node_base", C.POINTER(C.c_char)), ("node_rank", u32p), ("node_col", u32p),
+                ("edge_off", u64p), ("edge_from", u32p), ("edge_to", u32p), ("edge_w", i32p), ("base_node", u32p),
+                ("cns_off", u64p), ("cns", C.POINTER(C.c_char)), ("cns_node", u32p), ("aln_off", u64p), ("aln_node", i32p), ("aln_pos", i32p), ("aln_score", i32p),
+                ("dp_cells", C.c_uint64), ("seq_bases", C.c_uint64), ("n_aligned", C.c_uint64),
+                ("gather_kernel_ms", C.c_double), ("gather_kernel_bytes", C.c_uint64), ("slot_reruns", C.c_uint32), ("aln_reruns", C.c_uint32)]
+
+
 def msa_to_lists(o):
     """(rows per set, consensus per set) of an MsaOut"""
     n = o.n_set

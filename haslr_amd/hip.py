@@ -4,6 +4,7 @@ No fallback: if the library or a HIP device is missing, construction raises.
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # POA classes run on separate streams that must map to distinct hardware queues
 
@@ -15,7 +16,7 @@ _lib = None
 SYMBOLS = ["hx_last_error", "hx_device_count", "hx_ctx_create", "hx_ctx_destroy", "hx_upload", "hx_set_read_shard", "hx_set_prefiltered",
            "hx_chain_reads", "hx_edge_support", "hx_edge_coords", "hx_poa_batch", "hx_free_chain", "hx_free_edges",
            "hx_free_coords", "hx_free_cns", "hx_edge_emit", "hx_edge_records_bytes", "hx_edge_records_export",
-           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
+           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_poa_graph", "hx_free_graph", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
            "hx_set_option", "hx_get_option", "hx_option_names", "hx_poa_memory_stats", "hx_poa_release_workspace", "hx_poa_prune_stats", "hx_poa_retry_stats", "hx_group_set_timeout", "hx_group_inject_fault", "hx_poa_reserve", "hx_poa_host_times", "hx_poa_arena_stats", "hx_group_rccl_ranks",
            "hx_group_create", "hx_group_destroy", "hx_group_size", "hx_group_ctx", "hx_group_transport", "hx_edge_merge", "hx_group_backend_fill", "hx_group_exchange_stats"]
 
@@ -52,6 +53,8 @@ def lib():
         L.hx_poa_sequences_convex.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.CnsOut)]
         L.hx_poa_msa_convex.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.c_int, C.POINTER(T.MsaOut)]
         L.hx_poa_weighted_convex.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.c_int, C.c_int, C.POINTER(T.WcnsOut)]
+        L.hx_poa_graph.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.GraphOut)]
+        L.hx_free_graph.argtypes = [C.c_void_p, C.POINTER(T.GraphOut)]
         L.hx_free_chain.argtypes = [C.c_void_p, C.POINTER(T.ChainOut)]
         L.hx_free_edges.argtypes = [C.c_void_p, C.POINTER(T.EdgesOut)]
         L.hx_free_coords.argtypes = [C.c_void_p, C.POINTER(T.CoordsOut)]
@@ -144,6 +147,66 @@ def _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_e
 def _counters(o, *more):
     """the counters every consensus output struct carries, and the named extra fields of o"""
     return {k: getattr(o, k) for k in ("dp_cells", "seq_bases", "n_aligned") + more}
+
+
+# One set of HipContext.poa_graph (include/haslr_types.h, hx_graph_out). Node and edge ids are set-local. node_base is a string, one letter
+# per node; node_rank, node_col, edge_from, edge_to (uint32) and edge_w (int32) are numpy arrays, edges in the order they were first made;
+# n_cols the MSA columns; sequences one GraphSequence per GIVEN sequence: path (uint32 array, the node of every base), alignment (list of
+# (node | -1, position | -1) pairs against the graph before the sequence was added) and score (of the DP's end cell); consensus a string,
+# consensus_nodes (uint32 array) the node of every consensus base.
+GraphRecord = namedtuple("GraphRecord", "node_base node_rank node_col edge_from edge_to edge_w n_cols sequences consensus consensus_nodes")
+GraphSequence = namedtuple("GraphSequence", "path alignment score")
+
+
+def _out_edges_in_list_order(rec):
+    """per node the ids of its out-edges, in edge-id order (spoa's out-list order)"""
+    outs = [[] for _ in rec.node_base]
+    for e, f in enumerate(rec.edge_from):
+        outs[int(f)].append(e)
+    return outs
+
+
+def graph_to_dot(rec):
+    """a GraphRecord as Graphviz text, after spoa's Graph::print_dot: one digraph (named by the number of non-empty sequences); per node `id [label = "id - LETTER"]`, filled for the
+    nodes of the consensus; per out-edge, in out-list order, `from -> to [label = "weight"]`; one dotted line without arrowhead per pair of
+    aligned nodes (nodes sharing a column), from the smaller to the larger id. The same bytes as spoa::Graph::print_dot of
+    include/spoa_hx.hpp writes for the same graph."""
+    cns = set(int(n) for n in rec.consensus_nodes)
+    outs = _out_edges_in_list_order(rec)
+    by_col = {}
+    for n, c in enumerate(rec.node_col):
+        by_col.setdefault(int(c), []).append(n)
+    lines = [f"digraph {sum(1 for sq in rec.sequences if len(sq.path))} {{", "    graph [rankdir = LR]"]
+    for n, letter in enumerate(rec.node_base):
+        lines.append(f'    {n} [label = "{n} - {letter}"' + (", style = filled, fillcolor = goldenrod1]" if n in cns else "]"))
+        for e in outs[n]:
+            lines.append(f'    {n} -> {int(rec.edge_to[e])} [label = "{int(rec.edge_w[e])}"]')
+        for a in by_col[int(rec.node_col[n])]:
+            if a > n:
+                lines.append(f"    {n} -> {a} [style = dotted, arrowhead = none]")
+    lines.append("}")
+    return "\n".join(lines) + "\n"
+
+
+def graph_to_gfa(rec, names=None):
+    """a GraphRecord as GFA 1 text: `H VN:Z:1.0`; one S line per node (name = id + 1, the letter, tags rk:i: rank and cl:i: column); one L
+    line per edge in edge-id order (+ / +, overlap 0M, tag ew:i: weight); one P line per non-empty sequence, named by names[k] or s<k> (k
+    counts the given sequences from 0), and one P line `consensus`. The same bytes as spoa::Graph::print_gfa of include/spoa_hx.hpp writes
+    for the same graph."""
+    lines = ["H\tVN:Z:1.0"]
+    for n, letter in enumerate(rec.node_base):
+        lines.append(f"S\t{n + 1}\t{letter}\trk:i:{int(rec.node_rank[n])}\tcl:i:{int(rec.node_col[n])}")
+    for e in range(len(rec.edge_from)):
+        lines.append(f"L\t{int(rec.edge_from[e]) + 1}\t+\t{int(rec.edge_to[e]) + 1}\t+\t0M\tew:i:{int(rec.edge_w[e])}")
+
+    def p_line(name, nodes):
+        return f"P\t{name}\t" + ",".join(f"{int(n) + 1}+" for n in nodes) + "\t" + ",".join(["0M"] * (len(nodes) - 1) or ["*"])
+    for k, sq in enumerate(rec.sequences):
+        if len(sq.path):
+            lines.append(p_line(names[k] if names is not None else f"s{k}", sq.path))
+    if len(rec.consensus_nodes):
+        lines.append(p_line("consensus", rec.consensus_nodes))
+    return "\n".join(lines) + "\n"
 
 
 class HipContext:
@@ -438,6 +501,57 @@ class HipContext:
         lib().hx_free_wcns(self._h, C.byref(o))
         res = [cns] + ([cov] if coverage else []) + ([prof] if profile else []) + ([st] if stats else [])
         return cns if len(res) == 1 else tuple(res)
+
+    def poa_graph(self, sets, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=None, gap_open2=None, gap_extend2=None, weights=None, stats=False):
+        """the partial-order graph of every set, the path of every sequence through it and the alignment of every sequence (hx_poa_graph): a
+        list with one GraphRecord per set. gap_extend None (or equal to gap_open) is the linear gap model; gap_open2 and gap_extend2 (both
+        or neither) give the convex one. weights: nested like sets, one integer in 1..255 per base, or None (every weight 1). With
+        stats=True returns (records, counters): dp_cells, seq_bases, n_aligned as the consensus entries have them, gather_kernel_ms /
+        gather_kernel_bytes of the kernel that gathers the dense arrays, and slot_reruns / aln_reruns, the sets that ran again in a larger
+        workspace slot or with more room for their alignments."""
+        import numpy as np
+        _check_type(type)
+        ge = gap_open if gap_extend is None else gap_extend
+        cp = _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
+        if cp is None:   # one piece: a second one that is the first again never wins
+            cp = T.PoaConvexParams(match, mismatch, gap_open, ge, gap_open, ge, T.POA_TYPES[type])
+        wbytes = None
+        if weights is not None:
+            if len(weights) != len(sets) or any(len(ws) != len(st) or any(len(w) != len(q) for w, q in zip(ws, st)) for ws, st in zip(weights, sets)):
+                raise ValueError("weights must be nested like sets: one per base")
+            flat = np.array([v for ws in weights for w in ws for v in w], dtype=np.int64)
+            if flat.size and (flat.min() < 0 or flat.max() > 255):
+                raise ValueError("weights are 1..255")
+            wbytes = flat.astype(np.uint8).tobytes() or b"\0"
+        o = T.GraphOut()
+        n_sets, set_off, seq_off, bases = _flatten_sets(sets)
+        self._chk(lib().hx_poa_graph(self._h, n_sets, set_off, seq_off, bases, wbytes, C.byref(cp), C.byref(o)))
+        try:
+            n_seq = int(o.n_seq)
+            node_off, edge_off, cns_off, aln_off = (T.arr(p, n + 1, np.uint64).astype(np.int64) for p, n in ((o.node_off, n_sets), (o.edge_off, n_sets), (o.cns_off, n_sets), (o.aln_off, n_seq)))
+            NV, NE, NC, NP = int(node_off[-1]), int(edge_off[-1]), int(cns_off[-1]), int(aln_off[-1])
+            letters = C.string_at(o.node_base, NV).decode() if NV else ""
+            cns = C.string_at(o.cns, NC).decode() if NC else ""
+            rank, col = T.arr(o.node_rank, NV, np.uint32), T.arr(o.node_col, NV, np.uint32)
+            ef, et, ew = T.arr(o.edge_from, NE, np.uint32), T.arr(o.edge_to, NE, np.uint32), T.arr(o.edge_w, NE, np.int32)
+            cn = T.arr(o.cns_node, NC, np.uint32)
+            lens = [len(q) for st in sets for q in st]
+            base_node = T.arr(o.base_node, sum(lens), np.uint32)
+            an, ap, score = T.arr(o.aln_node, NP, np.int32).tolist(), T.arr(o.aln_pos, NP, np.int32).tolist(), T.arr(o.aln_score, n_seq, np.int32).tolist()
+            res, k, b = [], 0, 0
+            for i, st in enumerate(sets):
+                seqs = []
+                for q in st:
+                    seqs.append(GraphSequence(base_node[b:b + len(q)], list(zip(an[aln_off[k]:aln_off[k + 1]], ap[aln_off[k]:aln_off[k + 1]])), score[k]))
+                    b += len(q)
+                    k += 1
+                v0, v1, e0, e1 = node_off[i], node_off[i + 1], edge_off[i], edge_off[i + 1]
+                res.append(GraphRecord(letters[v0:v1], rank[v0:v1], col[v0:v1], ef[e0:e1], et[e0:e1], ew[e0:e1], int(col[v0:v1].max()) + 1 if v1 > v0 else 0, seqs,
+                                       cns[cns_off[i]:cns_off[i + 1]], cn[cns_off[i]:cns_off[i + 1]]))
+            st = _counters(o, "gather_kernel_ms", "gather_kernel_bytes", "slot_reruns", "aln_reruns")
+        finally:
+            lib().hx_free_graph(self._h, C.byref(o))
+        return (res, st) if stats else res
 
     def poa_phase_cycles(self):
         a, b = (C.c_uint64 * 6)(), (C.c_uint64 * 6)()

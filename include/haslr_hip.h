@@ -60,8 +60,9 @@ void hx_ctx_destroy(hx_ctx*);
  *                    general POA path (hx_poa_sequences_mode): poa_general (1: HX_POA_NW runs the general path too) and poa_modes_slot_kb (cap of
  *                    its first round of workspace slots, forcing the rerun of sets in larger ones), poa_affine (1: hx_poa_sequences_affine
  *                    with gap_extend == gap_open runs the affine kernel instead of the linear paths), poa_weighted (1: hx_poa_weighted
- *                    without weights runs the weighted kernels on weights of 1 instead of the unit-weight ones), and poa_convex (1: the convex
- *                    entries with gap_extend2 <= gap_extend run the convex kernel instead of the affine entries).
+ *                    without weights runs the weighted kernels on weights of 1 instead of the unit-weight ones), poa_convex (1: the convex
+ *                    entries with gap_extend2 <= gap_extend run the convex kernel instead of the affine entries), and poa_graph_aln_cap
+ *                    (hx_poa_graph: cap, in pairs, of a set's first share of the alignment pool, forcing its rerun with the exact room).
  *                    Results never depend on any of them. */
 int hx_set_option(hx_ctx*, const char* name, const char* value);
 int hx_get_option(const hx_ctx*, const char* name, double* value);
@@ -145,6 +146,17 @@ int hx_poa_weighted(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uin
 int hx_poa_sequences_convex(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_convex_params*, hx_cns_out* out);
 int hx_poa_msa_convex(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_convex_params*, int include_consensus, hx_msa_out* out);
 int hx_poa_weighted_convex(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params*, int want_coverage, int want_profile, hx_wcns_out* out);
+/*   hx_poa_graph      the partial-order graph itself, the path of every sequence through it and the alignment of every sequence (spoa's
+ *                     Graph and its Alignment pairs; DESIGN.md "General POA path", "Graph and alignment output"; the arrays: haslr_types.h,
+ *                     hx_graph_out). One entry over the convex parameters, by the rules of hx_poa_msa_convex: gap_extend2 <= gap_extend is the
+ *                     affine model of the first piece, and then gap_extend == gap_open the linear one (sequences of up to 8191, 16383 and
+ *                     32767 bases). weights as for hx_poa_weighted (1..255, 0 refused), or NULL. Every type runs the general path. The consensus
+ *                     and the counters are those of the consensus entries on the same sets (with weights: hx_poa_weighted's). Options
+ *                     poa_modes_slot_kb and poa_workspace_gb act as on the other entries; poa_graph_aln_cap (test switch) caps a set's first
+ *                     share of the alignment pool in pairs, forcing the rerun with the exact room; options poa_affine and poa_convex keep a
+ *                     call of a simpler model on the richer kernel, as elsewhere. Not pinned against spoa, like the rest of the general path. */
+int hx_poa_graph(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params*, hx_graph_out* out);
+void hx_free_graph(hx_ctx*, hx_graph_out*);
 void hx_free_chain(hx_ctx*, hx_chain_out*);
 void hx_free_edges(hx_ctx*, hx_edges_out*);
 void hx_free_coords(hx_ctx*, hx_coords_out*);

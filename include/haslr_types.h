@@ -205,6 +205,43 @@ typedef struct {
     uint64_t cov_kernel_bytes;
 } hx_wcns_out;
 
+/* hx_poa_graph: the partial-order graph of every set as it stands after its last sequence, the path of every sequence through it and the
+ * alignment of every sequence against the graph as it was before that sequence was added (DESIGN.md "General POA path", "Graph and
+ * alignment output"). Node and edge ids are set-local. Nodes are in creation order (spoa's ids), edges in the order add_edge first made
+ * them: the edges out of (into) a node, taken in edge-id order, are spoa's out-list (in-list) order.
+ *   nodes   set i: node_off[i] .. node_off[i+1]. node_base the letter, node_rank the node's place in spoa's topological order (what the DP
+ *           of one more sequence would use), node_col its MSA column (hx_poa_msa's): aligned nodes are the nodes that share a column.
+ *   edges   set i: edge_off[i] .. edge_off[i+1]. edge_w is spoa's total weight (a sequence adds w[p-1] + w[p]: 2 on unit weights).
+ *   paths   base_node[p] is the node of base p of `bases` (the caller's seq_off indexes it).
+ *   consensus  cns / cns_off as in hx_cns_out, cns_node the node of every consensus base.
+ *   alignments  sequence k of the call (all sets, in order; n_seq of them): pairs aln_off[k] .. aln_off[k+1] of (aln_node | -1, aln_pos |
+ *           -1) in spoa's forward order, and aln_score[k], the score of the DP's end cell. A sequence that met no DP (an empty one, the
+ *           first non-empty one of its set, a local alignment without a cell above 0) has no pair and score 0. */
+typedef struct {
+    uint32_t n_set;
+    uint64_t n_seq;
+    uint64_t* node_off; /* n_set+1 */
+    char* node_base;
+    uint32_t *node_rank, *node_col;
+    uint64_t* edge_off; /* n_set+1 */
+    uint32_t *edge_from, *edge_to;
+    int32_t* edge_w;
+    uint32_t* base_node; /* one per base of the call */
+    uint64_t* cns_off;   /* n_set+1 */
+    char* cns;
+    uint32_t* cns_node; /* cns_off[n_set] */
+    uint64_t* aln_off;  /* n_seq+1 */
+    int32_t *aln_node, *aln_pos;
+    int32_t* aln_score; /* n_seq */
+    uint64_t dp_cells, seq_bases, n_aligned;
+    /* the kernel that gathers the dense arrays, on its own: its time by device events and the bytes it has to move (every element of the
+     * node, edge, consensus-node and alignment arrays read once and written once) */
+    double gather_kernel_ms;
+    uint64_t gather_kernel_bytes;
+    /* sets that ran again: in a larger workspace slot, and because their alignments outgrew their share of the alignment pool */
+    uint32_t slot_reruns, aln_reruns;
+} hx_graph_out;
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,16 @@
 // generate_consensus(dst), is one device call of its own through hx_poa_weighted, as the MSA call is. spoa::hx::weighted_batch() takes
 // many sets in one call. Held to a CPU restatement of spoa's rule by the tests, like the MSA.
 //
+// The graph itself: Graph::print_dot(path) (spoa 1.1.3's signature; an empty path does nothing) and Graph::print_gfa(path) write the
+// partial-order graph of the recorded sequences, and Graph::alignment(k) returns the real Alignment of the k-th added sequence - spoa's
+// (node id | -1, position | -1) pairs against the graph as it was before that sequence was added. align_sequence_with_graph() keeps
+// returning its token: the graph exists on the device only during a call, so the real pairs are available from alignment(k) after the
+// device call, not before add_alignment. All three go through hx_poa_graph (every alignment type runs the general path there; the
+// graph's weights count): a device call of its own under the device's mutex, not flat-combined, like the MSA. spoa::hx::graph_batch()
+// takes many sets in one call and returns a GraphData per set; spoa::hx::to_dot / to_gfa turn one into text (the formats: DESIGN.md
+// "Graph and alignment output"; the Python writers haslr_amd.hip.graph_to_dot / graph_to_gfa give the same bytes). The DOT text follows
+// spoa's print_dot as published; spoa is not available to the tests, so byte equality with it is not claimed. Held to a CPU restatement.
+//
 // This is product code. It is never used to build oracle/_ref (a reference build must not be made with stand-in
 // headers): tests/test_spoa_header.py compiles a small caller written against the five symbols, nothing else.
 #ifndef HASLR_SPOA_HX_HPP
@@ -60,6 +70,8 @@
 #include <condition_variable>
 #include <cstdint>
 #include <cstdlib>
+#include <fstream>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -323,6 +335,108 @@ inline Weighted weighted_batch(const std::vector<std::vector<std::string>>& sets
     return weighted_batch(detail::pointers(sets), detail::pointers(weights), type, m, n, g, e, q, c, coverage, profile);
 }
 
+// the partial-order graph of one set (hx_graph_out in haslr_types.h, one set of it): nodes in id order, edges in the order they were first
+// made, per GIVEN sequence its path (the node of every base), its alignment against the graph before it was added and the score of that
+// alignment's end cell, the consensus and its nodes
+struct GraphData {
+    std::string node_base;
+    std::vector<std::uint32_t> node_rank, node_col, edge_from, edge_to;
+    std::vector<std::int32_t> edge_w;
+    std::vector<std::vector<std::uint32_t>> paths;
+    std::vector<Alignment> alignments;
+    std::vector<std::int32_t> scores;
+    std::string consensus;
+    std::vector<std::uint32_t> consensus_nodes;
+};
+// many sets in ONE device call (hx_poa_graph). weights as for weighted_batch, or empty: every weight is 1. (q, c) == (g, e) is one gap
+// piece, and then e == g the linear model.
+inline std::vector<GraphData> graph_batch(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights,
+                                          AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, std::int8_t q = -8, std::int8_t c = -8) {
+    if (!weights.empty() && weights.size() != sets.size()) throw std::invalid_argument("spoa_hx: graph_batch needs one set of weights per set of sequences, or none");
+    const detail::Flat f(sets);
+    std::vector<std::uint8_t> w;
+    for (std::size_t i = 0; i < sets.size() && !weights.empty(); i++) {
+        const auto& st = *sets[i];
+        if (weights[i]->size() != st.size()) throw std::invalid_argument("spoa_hx: graph_batch: a set has another number of weight vectors than of sequences");
+        for (std::size_t k = 0; k < st.size(); k++) {
+            const auto& wk = (*weights[i])[k];
+            if (wk.size() != st[k].size()) throw std::invalid_argument("spoa_hx: graph_batch: a sequence has another number of weights than of bases");
+            w.insert(w.end(), wk.begin(), wk.end());
+        }
+    }
+    if (!weights.empty() && w.empty()) w.push_back(1);   // (no base at all: a pointer that is not null, nothing behind it is read)
+    const hx_poa_convex_params cp{m, n, g, e, q, c, static_cast<std::int32_t>(type)};
+    hx_graph_out out;
+    return detail::locked_call([&](hx_ctx* ctx) { return hx_poa_graph(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), weights.empty() ? nullptr : w.data(), &cp, &out); },
+                               [&](hx_ctx* ctx) -> std::vector<GraphData> {
+        std::vector<GraphData> res(sets.size());
+        for (std::size_t i = 0; i < sets.size(); i++) {
+            GraphData& d = res[i];
+            const std::uint64_t v0 = out.node_off[i], v1 = out.node_off[i + 1], e0 = out.edge_off[i], e1 = out.edge_off[i + 1], c0 = out.cns_off[i], c1 = out.cns_off[i + 1];
+            d.node_base.assign(out.node_base + v0, out.node_base + v1);
+            d.node_rank.assign(out.node_rank + v0, out.node_rank + v1); d.node_col.assign(out.node_col + v0, out.node_col + v1);
+            d.edge_from.assign(out.edge_from + e0, out.edge_from + e1); d.edge_to.assign(out.edge_to + e0, out.edge_to + e1); d.edge_w.assign(out.edge_w + e0, out.edge_w + e1);
+            d.consensus.assign(out.cns + c0, out.cns + c1); d.consensus_nodes.assign(out.cns_node + c0, out.cns_node + c1);
+            for (std::uint64_t k = f.set_off[i]; k < f.set_off[i + 1]; k++) {
+                d.paths.emplace_back(out.base_node + f.seq_off[k], out.base_node + f.seq_off[k + 1]);
+                Alignment a;
+                for (std::uint64_t p = out.aln_off[k]; p < out.aln_off[k + 1]; p++) a.emplace_back(out.aln_node[p], out.aln_pos[p]);
+                d.alignments.push_back(std::move(a));
+                d.scores.push_back(out.aln_score[k]);
+            }
+        }
+        hx_free_graph(ctx, &out);
+        return res;
+    });
+}
+inline std::vector<GraphData> graph_batch(const std::vector<std::vector<std::string>>& sets, const std::vector<std::vector<std::vector<std::uint8_t>>>& weights, AlignmentType type,
+                                          std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, std::int8_t q = -8, std::int8_t c = -8) {
+    return graph_batch(detail::pointers(sets), detail::pointers(weights), type, m, n, g, e, q, c);
+}
+
+// Graphviz text of a graph, after spoa's Graph::print_dot: per node `id [label = "id - LETTER"]`, filled for the nodes of the consensus;
+// per out-edge, in out-list order, `from -> to [label = "weight"]`; one dotted line without arrowhead per pair of aligned nodes (nodes that
+// share a column), from the smaller to the larger id
+inline std::string to_dot(const GraphData& d) {
+    const std::size_t V = d.node_base.size();
+    std::vector<char> in_cns(V, 0);
+    for (std::uint32_t nd : d.consensus_nodes) in_cns[nd] = 1;
+    std::vector<std::vector<std::size_t>> outs(V);
+    for (std::size_t e = 0; e < d.edge_from.size(); e++) outs[d.edge_from[e]].push_back(e);
+    std::map<std::uint32_t, std::vector<std::size_t>> by_col;
+    for (std::size_t nd = 0; nd < V; nd++) by_col[d.node_col[nd]].push_back(nd);
+    std::size_t n_seq = 0;
+    for (const auto& p : d.paths) n_seq += !p.empty();
+    std::string s = "digraph " + std::to_string(n_seq) + " {\n    graph [rankdir = LR]\n";
+    for (std::size_t nd = 0; nd < V; nd++) {
+        s += "    " + std::to_string(nd) + " [label = \"" + std::to_string(nd) + " - " + d.node_base[nd] + "\"" + (in_cns[nd] ? ", style = filled, fillcolor = goldenrod1]\n" : "]\n");
+        for (std::size_t e : outs[nd]) s += "    " + std::to_string(nd) + " -> " + std::to_string(d.edge_to[e]) + " [label = \"" + std::to_string(d.edge_w[e]) + "\"]\n";
+        for (std::size_t a : by_col[d.node_col[nd]]) if (a > nd) s += "    " + std::to_string(nd) + " -> " + std::to_string(a) + " [style = dotted, arrowhead = none]\n";
+    }
+    return s + "}\n";
+}
+// GFA 1 text of a graph: `H VN:Z:1.0`; one S line per node (name = id + 1, the letter, tags rk:i: rank and cl:i: column); one L line per
+// edge in edge-id order (+ / +, overlap 0M, tag ew:i: weight); one P line per non-empty sequence, named by names[k] or s<k> (k counts the
+// given sequences from 0), and one P line `consensus`
+inline std::string to_gfa(const GraphData& d, const std::vector<std::string>& names = std::vector<std::string>()) {
+    std::string s = "H\tVN:Z:1.0\n";
+    for (std::size_t nd = 0; nd < d.node_base.size(); nd++)
+        s += "S\t" + std::to_string(nd + 1) + "\t" + d.node_base[nd] + "\trk:i:" + std::to_string(d.node_rank[nd]) + "\tcl:i:" + std::to_string(d.node_col[nd]) + "\n";
+    for (std::size_t e = 0; e < d.edge_from.size(); e++)
+        s += "L\t" + std::to_string(d.edge_from[e] + 1) + "\t+\t" + std::to_string(d.edge_to[e] + 1) + "\t+\t0M\tew:i:" + std::to_string(d.edge_w[e]) + "\n";
+    auto p_line = [&s](const std::string& name, const std::vector<std::uint32_t>& nodes) {
+        s += "P\t" + name + "\t";
+        for (std::size_t i = 0; i < nodes.size(); i++) s += (i ? "," : "") + std::to_string(nodes[i] + 1) + "+";
+        s += "\t";
+        for (std::size_t i = 1; i < nodes.size(); i++) s += i > 1 ? ",0M" : "0M";
+        s += nodes.size() < 2 ? "*\n" : "\n";
+    };
+    for (std::size_t k = 0; k < d.paths.size(); k++)
+        if (!d.paths[k].empty()) p_line(k < names.size() ? names[k] : "s" + std::to_string(k), d.paths[k]);
+    if (!d.consensus_nodes.empty()) p_line("consensus", d.consensus_nodes);
+    return s;
+}
+
 // one set on behalf of one caller thread, combined with whatever other threads have queued (see "Threads" above)
 inline std::string consensus_combined(const std::vector<std::string>& seqs, AlignmentType type, std::int8_t m, std::int8_t n, std::int8_t g, std::int8_t e, std::int8_t q, std::int8_t c) {
     Device& d = device();
@@ -466,8 +580,37 @@ public:
         dst = std::move((convex() ? hx::msa_batch(one, type_, m_, n_, g_, e_, q_, c_, include_consensus) : hx::msa_batch(one, type_, m_, n_, g_, e_, include_consensus))[0]);
     }
 
+    // the graph of the recorded sequences (their weights count): a device call of its own, like the MSA. A graph without sequences needs no device.
+    hx::GraphData data() const {
+        if (sequences_.empty()) return hx::GraphData();
+        const std::vector<const std::vector<std::string>*> one{&sequences_};
+        const std::vector<const std::vector<std::vector<std::uint8_t>>*> w = weighted_ ? std::vector<const std::vector<std::vector<std::uint8_t>>*>{&weights_} : std::vector<const std::vector<std::vector<std::uint8_t>>*>{};
+        return std::move(hx::graph_batch(one, w, type_, m_, n_, g_, e_, q_, c_)[0]);
+    }
+    // spoa::Graph::print_dot(path): the graph as Graphviz text (hx::to_dot); an empty path does nothing, as in spoa
+    void print_dot(const std::string& path) const {
+        if (path.empty()) return;
+        write(path, hx::to_dot(data()));
+    }
+    // the graph as GFA 1 (hx::to_gfa; the sequences are named s0, s1, ... in the order they were added)
+    void print_gfa(const std::string& path) const {
+        if (path.empty()) return;
+        write(path, hx::to_gfa(data()));
+    }
+    // the real Alignment of the k-th added sequence (empty ones, which add_alignment ignores, do not count): spoa's pairs against the graph
+    // as it was before that sequence was added. The first sequence has none.
+    Alignment alignment(std::size_t k) const {
+        if (k >= sequences_.size()) throw std::out_of_range("spoa_hx: alignment(" + std::to_string(k) + ") of a graph with " + std::to_string(sequences_.size()) + " sequences");
+        return data().alignments[k];
+    }
+
 private:
     friend class AlignmentEngine;
+    static void write(const std::string& path, const std::string& text) {
+        std::ofstream out(path.c_str(), std::ios::binary);
+        out << text;
+        if (!out) throw std::runtime_error("spoa_hx: cannot write " + path);
+    }
     bool convex() const { return q_ != g_ || c_ != e_; }   // a seven-score engine whose second piece is not the first again
     // this graph's one set through the weighted entry of its gap model (with its weights, or on unit weights)
     hx::Weighted weighted(bool with_weights, bool coverage) const {

@@ -17,7 +17,11 @@ time against the consensus-only general path ("over_general", as for the MSA), t
 the bytes they have to move, GB/s), and the sample compared with the weighted restatement (tests/poa_weighted_ref.cpp). And every row runs
 the convex kernel on the same sets (hx_poa_sequences_convex with --convex-scores, default 5 -4 -8 -6 -10 -4): same figures, the convex /
 affine and convex / linear ratios of the median kernel times with the smallest and largest ratio the repeats allow, and every sampled set
-compared with the convex restatement (tests/poa_convex_ref.cpp). --only picks the parts to run; --package-root runs the parts another
+compared with the convex restatement (tests/poa_convex_ref.cpp). And rows (a) and (b) ask for the graph and the alignments of the same sets
+(hx_poa_graph, linear scores, unit weights; part "graph", which needs general and outputs): kernel time against the MSA's in the same
+process ("over_msa") and against the consensus-only general path, the gather kernel on its own (time by device events, the bytes it has to
+move, GB/s), the sets that were rerun because their alignments outgrew their share of the alignment pool under the default estimate, and
+the sample compared with the graph restatement (tests/poa_graph_ref.cpp). --only picks the parts to run; --package-root runs the parts another
 build of the package has (a checkout of the parent commit, say) in the same way, for a comparison on one machine. Prints one JSON line,
 and writes it to --out when given."""
 import argparse
@@ -34,7 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
-PARTS = ["general", "tuned_nw", "cpu", "affine", "outputs", "convex"]   # outputs: the MSA and the weighted entry
+PARTS = ["general", "tuned_nw", "cpu", "affine", "outputs", "convex", "graph"]   # outputs: the MSA and the weighted entry
 
 
 def text(a):
@@ -119,6 +123,8 @@ def main():
     only = set(a.only)
     if not hasattr(hip.HipContext, "poa_sequences_convex"):
         only.discard("convex")
+    if not hasattr(hip.HipContext, "poa_graph"):
+        only.discard("graph")
     rng = np.random.default_rng(a.seed)
     loads = {"a_sw": ("sw", workload_a(rng, a.sets_a, True)), "a_nw": ("nw", workload_a(rng, a.sets_a, False))}
     loads["a_ov"] = ("ov", loads["a_nw"][1])
@@ -226,6 +232,27 @@ def main():
             got = ctx.poa_weighted(sample, swts, type=mode, coverage=True, profile=True)
             r["weighted_sample_equal"] = list(zip(*got)) == [(w.consensus, w.coverage, w.profile) for w in out]
             r["weighted_sample_changed"] = sum(c != u for c, u in zip(got[0], ctx.poa_weighted(sample, type=mode)))
+            if "graph" in only:
+                import grflib
+                gath_ms, gst = [], {}
+
+                def graph_call():
+                    nonlocal gst
+                    gst = ctx.poa_graph(sets, mode, stats=True)[1]
+                    gath_ms.append(gst["gather_kernel_ms"])
+                ms = gpu_time(ctx, graph_call, a.repeats)
+                med, gmed, msa = float(np.median(ms)), float(np.median(gath_ms[1:])), r["msa"]
+                r["graph"] = {"kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
+                              "over_msa": round(med / msa["kernel_ms_median"], 4), "over_msa_min": round(min(ms) / msa["kernel_ms_max"], 4), "over_msa_max": round(max(ms) / msa["kernel_ms_min"], 4),
+                              "over_general": round(med / gen["kernel_ms_median"], 4),
+                              "gather_kernel": {"ms_median": round(gmed, 4), "ms_min": round(min(gath_ms[1:]), 4), "ms_max": round(max(gath_ms[1:]), 4),
+                                                "bytes": int(gst["gather_kernel_bytes"]), "gb_per_s": round(gst["gather_kernel_bytes"] / gmed / 1e6, 1)},
+                              "aln_reruns": int(gst["aln_reruns"]), "slot_reruns": int(gst["slot_reruns"])}
+                gref = grflib.GraphRef(d)
+                with ThreadPoolExecutor(16) as ex:
+                    out = list(ex.map(lambda st: gref.graph(st, mode), sample))
+                r["graph_sample_equal"] = all(grflib.same(x, y) for x, y in zip(ctx.poa_graph(sample, mode), out))
+                note(name, "graph", r["graph"]["kernel_ms_median"], "ms")
             res[name] = r
     ctx.close()
     print(json.dumps(res))
