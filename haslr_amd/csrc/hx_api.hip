@@ -26,7 +26,7 @@ const OptDesc kOptions[] = {
     {"poa_prune", &HxOptions::poa_prune, nullptr}, {"poa_prune_lanes", &HxOptions::poa_prune_lanes, nullptr}, {"poa_prune_lazy", &HxOptions::poa_prune_lazy, nullptr}, {"poa_prune_shared", &HxOptions::poa_prune_shared, nullptr}, {"poa_pass_lanes", &HxOptions::poa_pass_lanes, nullptr}, {"poa_chain_ms", &HxOptions::poa_chain_ms, nullptr}, {"poa_chain_pct", &HxOptions::poa_chain_pct, nullptr}, {"poa_resident_first", &HxOptions::poa_resident_first, nullptr}, {"poa_own_bucket_first", &HxOptions::poa_own_bucket_first, nullptr}, {"coords_lds_supp", &HxOptions::coords_lds_supp, nullptr},
     {"poa_general", &HxOptions::poa_general, nullptr}, {"poa_modes_slot_kb", &HxOptions::poa_modes_slot_kb, nullptr},
     {"poa_affine", &HxOptions::poa_affine, nullptr}, {"poa_weighted", &HxOptions::poa_weighted, nullptr}, {"poa_convex", &HxOptions::poa_convex, nullptr},
-    {"poa_graph_aln_cap", &HxOptions::poa_graph_aln_cap, nullptr},
+    {"poa_graph_aln_cap", &HxOptions::poa_graph_aln_cap, nullptr}, {"poa_strand_one_h", &HxOptions::poa_strand_one_h, nullptr},
 };
 }  // namespace
 

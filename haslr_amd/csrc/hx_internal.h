@@ -157,6 +157,7 @@ struct HxOptions {
     int poa_weighted = 0;          // hx_poa_weighted without weights runs the weighted instances of the general path on weights of 1 instead of the MSA twins: the cross-check of the weighted graph update against the unit-weight one
     int poa_convex = 0;            // the convex entries with gap_extend2 <= gap_extend run the convex instances of the general path instead of the affine entries: the cross-check of the convex kernel against the affine one
     int poa_modes_slot_kb = 0;     // the general path's first round of slots holds at most this many KB (testing: forces the overflow and the rerun in a larger slot; 0 no cap)
+    int poa_strand_one_h = 1;      // hx_poa_strand: one score matrix per slot, the winning reverse complement's DP runs once more (the only route built)
     int poa_graph_aln_cap = 0;     // hx_poa_graph: a set's first share of the alignment pool holds at most this many pairs (testing: forces the rerun with the exact room; 0 no cap)
 };
 

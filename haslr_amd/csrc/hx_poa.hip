@@ -455,6 +455,7 @@ static int poa_general_run(hx_ctx* c, const char* tag, hxk::PoaModesArgs& a, hxk
         char rows[96] = "", part[96] = "";   // what an MSA or a weighted call adds to the line
         if (a.msa) { snprintf(rows, sizeof rows, "%zu bytes of rows, ", o.msa.size()); snprintf(part, sizeof part, " (rows %.3f ms)", o.msa_rows_ms); }
         if (a.weighted) snprintf(part, sizeof part, " (coverage %.3f ms)", o.cov_ms);
+        if (a.strand) snprintf(part, sizeof part, " (%llu of %llu sequences reversed)", (unsigned long long)o.third_passes, (unsigned long long)o.n_aligned);
         if (a.graph) { snprintf(rows, sizeof rows, "%zu nodes, %zu edges, %zu pairs, ", o.node_base.size(), o.edge_w.size(), o.aln_pos.size()); snprintf(part, sizeof part, " (gather %.3f ms, %u sets rerun for their alignments)", o.gather_ms, o.aln_retried); }
         fprintf(stderr, "[hx] POA %s call%s: %u sets, %.3g cells, %skernels %.2f ms%s, %u sets rerun in a larger slot\n", tag, a.gap_model == 2 ? " (convex)" : a.gap_model == 1 ? " (affine)" : "", a.n_sets, (double)o.cells, rows, o.kernel_ms, part, o.retried);
     }
@@ -652,6 +653,43 @@ extern "C" int hx_poa_graph(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off,
     return 0;
 }
 
+// the consensus of sets whose sequences may lie on either strand: the general path's strand instances (all three types) of the gap model
+// the scores name, chosen by hx_poa_graph's rules
+extern "C" int hx_poa_strand(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params* cp,
+                             const hx_poa_strand_want* want, hx_strand_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!cp || !want) return fail("hx_poa_strand: no parameters");
+    if (check_convex_call("hx_poa_strand", *cp, set_off[n_sets])) return -1;
+    if (check_weights("hx_poa_strand", n_sets, set_off, seq_off, weights)) return -1;
+    GapScores sc = convex_scores(*cp);
+    if (convex_is_affine(c, *cp)) { sc.open2 = sc.extend2 = 0; sc.model = cp->gap_extend != cp->gap_open || c->opt.poa_affine; }   // the second piece never wins: the call takes the affine route
+    hxk::PoaModesArgs a = general_args("hx_poa_strand", n_sets, set_off, seq_off, bases, sc);
+    a.strand = 1; a.weights = weights;
+    a.msa = want->want_msa != 0; a.include_consensus = a.msa && want->include_consensus != 0;
+    a.want_coverage = want->want_coverage != 0; a.want_profile = want->want_profile != 0;
+    hxk::PoaModesOut o;
+    if (poa_general_run(c, "strand", a, o)) return -1;
+    const uint64_t n_seq = set_off[n_sets];
+    out->n_set = n_sets; out->n_seq = n_seq;
+    out->cns_off = dup(o.cns_off.data(), (size_t)n_sets + 1);
+    out->cns = dup(o.cns.data(), o.cns.size());
+    out->reversed = dup(o.reversed.data(), o.reversed.size()); out->score_fwd = dup(o.score_fwd.data(), o.score_fwd.size()); out->score_rev = dup(o.score_rev.data(), o.score_rev.size());
+    if (a.msa) {
+        out->n_rows = dup(o.msa_rows.data(), n_sets); out->n_cols = dup(o.msa_cols.data(), n_sets);
+        out->msa_off = dup(o.msa_off.data(), (size_t)n_sets + 1); out->msa = dup(o.msa.data(), o.msa.size());
+    }
+    if (a.want_coverage || a.want_profile) out->coverage = dup(o.cov.data(), o.cov.size());
+    if (a.want_profile) out->profile = dup(o.prof.data(), o.prof.size());
+    out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned; out->third_passes = o.third_passes;
+    out->slot_reruns = o.retried;
+    return 0;
+}
+
+extern "C" void hx_free_strand(hx_ctx*, hx_strand_out* o) {
+    free(o->cns_off); free(o->cns); free(o->reversed); free(o->score_fwd); free(o->score_rev); free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa);
+    free(o->coverage); free(o->profile);
+    memset(o, 0, sizeof(*o));
+}
 extern "C" void hx_free_graph(hx_ctx*, hx_graph_out* o) {
     free(o->node_off); free(o->node_base); free(o->node_rank); free(o->node_col); free(o->edge_off); free(o->edge_from); free(o->edge_to); free(o->edge_w); free(o->base_node);
     free(o->cns_off); free(o->cns); free(o->cns_node); free(o->aln_off); free(o->aln_node); free(o->aln_pos); free(o->aln_score);

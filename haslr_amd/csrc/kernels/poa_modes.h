@@ -37,6 +37,9 @@ struct PoaModesArgs {
     int want_coverage = 0;               // weighted calls: the coverage of every consensus base in PoaModesOut
     int want_profile = 0;                // weighted calls: and the four letter counts of its column
     int graph = 0;                       // 1: hx_poa_graph (the graph instances; weights as for a weighted call, or null), and the graph and the alignments in PoaModesOut
+    int strand = 0;                      // 1: hx_poa_strand (the strand instances: every sequence is aligned forward and reverse-complemented and the better
+                                         // one is added; weights as for a weighted call, or null). msa / include_consensus and want_coverage / want_profile
+                                         // say what PoaModesOut holds beside the flags and the scores
     uint32_t aln_cap = 0;                // graph calls, first round only: a set's share of the alignment pool holds at most this many pairs (0: no cap); sets whose
                                          // alignments outgrow it are rerun once with exactly the room they need
 };
@@ -66,6 +69,10 @@ struct PoaModesOut {
     uint32_t aln_retried = 0;            // sets rerun because their alignments outgrew their share of the pool
     double gather_ms = 0;                // the gather kernel alone (part of kernel_ms)
     uint64_t gather_moved_bytes = 0;     // what it has to move: every dense element read once and written once
+    // strand calls: per given sequence whether its reverse complement was added, and the end-cell scores of its two orientations
+    std::vector<uint8_t> reversed;
+    std::vector<int32_t> score_fwd, score_rev;
+    uint64_t third_passes = 0;           // sequences whose reverse complement won: each cost a third DP pass
 };
 
 // 0 = ok, else -1 with the reason in err

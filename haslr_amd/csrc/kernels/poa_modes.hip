@@ -2,7 +2,7 @@
 // caller-given sequence sets (hx_poa_sequences_mode; DESIGN.md "General POA path" has the semantics and the mapping), and the affine-gap
 // engine in the same modes (hx_poa_sequences_affine: same mapping, a cell is the pair (H, F), its own row of the instance table), and the
 // two-piece affine ("convex") gap model (hx_poa_sequences_convex: a cell is (H, F, O), 12 bytes, a third row of the table). All of it is
-// one kernel template, k_poa_general<NT, CPL, GM, MSA, WTS>, GM the gap model.
+// one kernel template, k_poa_general<NT, CPL, GM, MSA, WTS, GRAPH, STRAND>, GM the gap model.
 //
 // It is a kernel family of its own beside the tuned global-only k_poa (kernels/poa.hip), which depends on kNW throughout (de-ramped keys
 // with tie bits, score-bound pruning, sink lists, end-node ties decided on closures, multi-member pipelines). What the modes share with
@@ -33,6 +33,11 @@
 // writes the set's nodes (code, rank, column), its edges in creation order and the nodes of the consensus, and base_col stays node ids. A
 // grid-wide kernel (k_graph_gather) moves all of it into dense arrays once the host knows the sizes. The pool is the one array sized from an
 // estimate: a set whose alignments outgrow its share finishes, reports what it needed, and is rerun once with exactly that room.
+//
+// Strand-ambiguous sets (hx_poa_strand; DESIGN.md "Strand-ambiguous sets") are a fourth flag, over the weighted variant: every sequence after
+// a set's first is aligned to the graph reverse-complemented and as given, the orientation with the higher end-cell score is added (ties
+// forward; when the reverse complement wins, its DP runs once more so that its H is the one the traceback walks), and everything
+// downstream reads the codes and weights as they were added (codes_used / wts_used).
 //
 // Layout: the DP and traceback of the three gap models are poa_modes_dp.inl, the columns, row text, coverage and the graph output's helpers
 // and gather poa_modes_out.inl; this file keeps the work of one set (run_set), the kernel, the instance table and the host driver
@@ -76,6 +81,15 @@ struct GraphOutArgs {
     uint32_t* cns_node;   // beside cns
 };
 
+// What the strand instances (hx_poa_strand) read and write beside the rest: every sequence reverse-complemented at its own offset (codes_rc,
+// and wts_rc: base i of rc(s) carries the weight of base L-1-i of s), the orientation that was added (codes_used / wts_used: what
+// add_alignment, weigh_path and the row, coverage and profile kernels read), and per sequence of the call the choice and the two end-cell
+// scores; per set the sequences whose reverse complement won (each cost a third DP pass).
+struct StrandArgs {
+    const uint8_t *codes_rc, *wts_rc; uint8_t *codes_used, *wts_used;
+    uint8_t* reversed; int32_t *score_fwd, *score_rev; uint32_t* third;
+};
+
 struct MArgs {
     const MSet* sets; const uint32_t* order; uint32_t n_items; uint32_t* counter;
     const uint8_t* codes; const uint64_t* soff;
@@ -89,6 +103,7 @@ struct MArgs {
     const uint8_t* wts;   // weighted instances only: the weight of every base of the call (1..255), beside codes
     int32_t q, c;         // convex instances only: gap open and gap extend of the second piece
     GraphOutArgs go;      // graph instances only (poa_modes_out.inl)
+    StrandArgs sa;        // strand instances only
 };
 
 // one row of the MSA text: its columns (rising) start at cols[src], its letters at codes[src] (a sequence) or cns[src] (the consensus row)
@@ -173,7 +188,7 @@ struct Shared { uint32_t item, V, E, fail; int best; uint32_t na /* graph instan
 #include "poa_modes_dp.inl"     // DP and traceback, linear, affine and convex gaps
 #include "poa_modes_out.inl"    // MSA columns and row text, base weights, coverage, graph and alignment output
 
-template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH>
+template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH, bool STRAND>
 __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Shared& sh, int* s_wtot, uint32_t* s_scan) {
     const uint32_t t = threadIdx.x;
     const MSet S = a.sets[set];
@@ -185,6 +200,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     uint32_t V = 0, E = 0, non_empty = 0;
     unsigned long long cells = 0;
     uint64_t aln_used = 0;   // graph instances: the pairs of the set's alignments so far
+    uint32_t third = 0;      // strand instances: the sequences whose reverse complement won
     for (uint32_t k = 0; k < S.nseq; k++) {
         const uint64_t b = a.soff[S.seq_begin + k];
         const uint32_t L = (uint32_t)(a.soff[S.seq_begin + k + 1] - b);
@@ -194,12 +210,33 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
         uint32_t na = 0;
         if (V) {
             if ((uint64_t)(V + 1) * (L + 1) > hcap) { if (t == 0) { a.status[set] = MS_H_OVERFLOW; a.vseen[set] = V; } return; }
-            cells += (unsigned long long)V * L;
+            cells += (unsigned long long)V * L * (STRAND ? 2u : 1u);   // (strand instances: the algorithm's cells, both orientations)
             uint32_t bi, bj;
             if (GRAPH) mark_pairs<NT>(g, V);   // (dp_rows' barriers lie between this and the traceback)
-            dp_rows<NT, CPL, GM>(g, H, V, s, L, a, sh, s_wtot, &bi, &bj);
+            if constexpr (STRAND) {
+                // Both orientations against the graph as it stands, the reverse complement first: when the forward one wins or ties, its
+                // H is the one in the slot; when the reverse complement wins, a third pass computes its H again. One call site, so that
+                // dp_rows is inlined once, as in the other instances. Every lane reads the scores from sh.best behind dp_rows' last
+                // barrier (the next write to it lies behind the barriers of the next pass), so the choice is the same value in every lane.
+                const uint8_t* rc = a.sa.codes_rc + b;
+                int32_t score_r = 0, score_f = 0;
+                bool rev = false;
+#pragma unroll 1
+                for (int pass = 0; pass < 3; pass++) {
+                    if (pass == 2 && !rev) break;
+                    dp_rows<NT, CPL, GM>(g, H, V, pass == 1 ? s : rc, L, a, sh, s_wtot, &bi, &bj);
+                    if (pass == 0) score_r = sh.best;
+                    if (pass == 1) { score_f = sh.best; rev = score_r > score_f; }   // (ties go forward)
+                }
+                third += rev;
+                keep_strand<NT>(a, b, L, S.seq_begin + k, rev, score_f, score_r);
+                s = a.sa.codes_used + b;
+            } else dp_rows<NT, CPL, GM>(g, H, V, s, L, a, sh, s_wtot, &bi, &bj);
             if (t == 0 && bi) na = traceback<GM>(g, H, s, L, bi, bj, a);
             if (GRAPH && t == 0) sh.na = bi ? keep_score(g, V, na, sh.best, a.go.aln_score + S.seq_begin + k) : 0u;   // (sh.best: dp_rows' end-cell score)
+        } else if constexpr (STRAND) {   // the first non-empty sequence goes in forward, without a DP: both scores 0
+            keep_strand<NT>(a, b, L, S.seq_begin + k, false, 0, 0);
+            s = a.sa.codes_used + b;
         }
         if (t == 0) {
             uint32_t v = V, e = E;
@@ -211,7 +248,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
         V = sh.V; E = sh.E;
         if (sh.fail) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
         if (MSA) for (uint32_t i = t; i < L; i += NT) a.base_col[b + i] = path[i];   // (node ids never change: a rerun set rewrites its part)
-        if (WTS) weigh_path<NT>(g, path, a.wts + b, L);   // (order_rows reads e_w behind its barriers)
+        if (WTS) weigh_path<NT>(g, path, (STRAND ? a.sa.wts_used : a.wts) + b, L);   // (order_rows reads e_w behind its barriers)
         order_rows<NT>(g, V, s_scan);
     }
     if (MSA) {
@@ -231,6 +268,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
             }
             if (t == 0) {
                 a.cns_len[set] = len; a.n_cols[set] = ncols; a.cells[set] = cells; a.status[set] = MS_OK;
+                if (STRAND) a.sa.third[set] = third;
                 if (GRAPH) { a.go.aln_need[set] = (uint32_t)min(aln_used, (uint64_t)0xffffffffu); if (aln_used > a.go.aln_room[set]) a.status[set] = MS_ALN_OVERFLOW; }
             }
         }
@@ -241,7 +279,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     __syncthreads();   // the slot is free for the next set
 }
 
-template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH = false>
+template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH = false, bool STRAND = false>
 __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
     __shared__ Shared sh;
     __shared__ int s_wtot[(GM == GM_CONVEX ? 2 : 1) * (NT / 64)];   // per wave the total of its row scan (convex: of its two)
@@ -253,7 +291,7 @@ __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
         const uint32_t q = sh.item;
         __syncthreads();
         if (q >= a.n_items) return;
-        run_set<NT, CPL, GM, MSA, WTS, GRAPH>(a, a.order[q], slot, sh, s_wtot, s_scan);
+        run_set<NT, CPL, GM, MSA, WTS, GRAPH, STRAND>(a, a.order[q], slot, sh, s_wtot, s_scan);
     }
 }
 
@@ -261,9 +299,10 @@ __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
 // Each comes in three variants: the consensus alone (a consensus-only call runs the code it ran before the MSA existed), with the node of
 // every base kept (the MSA; coverage needs it too), with base weights applied on top of that (hx_poa_weighted with weights), and with the
 // graph and the alignments written out on top of that (hx_poa_graph; without weights it runs on weights of 1, which add nothing to an edge).
-struct Inst { int nt, cpl; const void* variant[4]; };
+// A fifth variant, over the weighted one, aligns every sequence in both orientations and adds the better one (hx_poa_strand).
+struct Inst { int nt, cpl; const void* variant[5]; };
 #define HX_INST(GM, NT, CPL) {NT, CPL, {(const void*)k_poa_general<NT, CPL, GM, false, false>, (const void*)k_poa_general<NT, CPL, GM, true, false>, (const void*)k_poa_general<NT, CPL, GM, true, true>, \
-                                        (const void*)k_poa_general<NT, CPL, GM, true, true, true>}}
+                                        (const void*)k_poa_general<NT, CPL, GM, true, true, true>, (const void*)k_poa_general<NT, CPL, GM, true, true, false, true>}}
 constexpr int N_INST = 4;
 // by gap model (GM_LINEAR, GM_AFFINE, GM_CONVEX). The affine instances keep two accumulators per column (diagonal and F): 16 columns per
 // lane throughout, more lanes instead. The convex ones keep three (diagonal, F and O) and stop at 512 lanes, two waves per SIMD with up to
@@ -277,7 +316,7 @@ const Inst kInst[3][N_INST] = {
 constexpr uint32_t MAX_LEN[3] = {1024 * 32 - 1, 1024 * 16 - 1, 512 * 16 - 1};
 constexpr uint64_t CELL_BYTES[3] = {4, 8, 12};   // of a cell of H by gap model: what the kernels take as sizeof(Cell<GM>)
 static_assert(CELL_BYTES[GM_LINEAR] == sizeof(Cell<GM_LINEAR>) && CELL_BYTES[GM_AFFINE] == sizeof(Cell<GM_AFFINE>) && CELL_BYTES[GM_CONVEX] == sizeof(Cell<GM_CONVEX>), "CELL_BYTES against the cell types of poa_modes_dp.inl");
-inline const void* fn(const Inst& inst, bool cols, bool weighted, bool graph) { return inst.variant[graph ? 3 : weighted ? 2 : cols ? 1 : 0]; }
+inline const void* fn(const Inst& inst, bool cols, bool weighted, bool graph, bool strand) { return inst.variant[strand ? 4 : graph ? 3 : weighted ? 2 : cols ? 1 : 0]; }
 
 template <class T> struct Buf {   // device buffer of one call
     T* p = nullptr;
@@ -317,14 +356,16 @@ struct Run {
     const bool msa = a.msa != 0;
     const bool wtd = a.weighted != 0;                        // hx_poa_weighted: the node of every base is kept, as for the MSA
     const bool graph = a.graph != 0;                         // hx_poa_graph: the node of every base stays a node, the graph and the alignments are written out
-    const bool cols = msa || wtd || graph;
-    const bool want_cov = wtd && (a.want_coverage || a.want_profile);
+    const bool strand = a.strand != 0;                       // hx_poa_strand: every sequence in both orientations; MSA text, coverage and profile as asked
+    const bool cols = msa || wtd || graph || strand;
+    const bool want_cov = (wtd || strand) && (a.want_coverage || a.want_profile);
     const Inst* const inst = kInst[gm];
     const uint64_t cell_bytes = CELL_BYTES[gm];
     const uint64_t nseq = a.set_off[ns], nb = a.seq_off[nseq];
     std::vector<MSet> sets = std::vector<MSet>(ns);
     std::vector<uint64_t> cns_off = std::vector<uint64_t>((size_t)ns + 1, 0);
     std::vector<uint8_t> codes;      // the bases as 0..3 (kept to the end of the call: they are uploaded asynchronously)
+    std::vector<uint8_t> codes_rc, wts_rc;   // strand calls: every sequence reverse-complemented at its own offset, its weights reversed with it
     std::vector<uint64_t> vest;      // per set: the estimate of its graph's final size that its H is sized from
     std::vector<uint32_t> todo;      // the sets of the next round
     std::vector<uint32_t> len;       // per set: the length of its consensus (after consensus())
@@ -332,7 +373,9 @@ struct Run {
     uint64_t budget = 0;
     Buf<MSet> d_sets; Buf<uint8_t> d_codes; Buf<uint64_t> d_soff; Buf<uint32_t> d_order, d_counter, d_status, d_vseen, d_cns_len; Buf<unsigned long long> d_cells; Buf<char> d_cns;
     Buf<uint32_t> d_base_col, d_n_cols, d_cns_col;   // MSA and weighted calls only
-    Buf<uint8_t> d_wts;                              // weighted calls with weights only: a byte per base (graph calls: always, 1 without weights)
+    Buf<uint8_t> d_wts;                              // weighted calls with weights only: a byte per base (graph and strand calls: always, 1 without weights)
+    // strand calls only: what StrandArgs points to
+    Buf<uint8_t> d_codes_rc, d_wts_rc, d_codes_used, d_wts_used, d_reversed; Buf<int32_t> d_score_fwd, d_score_rev; Buf<uint32_t> d_third;
     // graph calls only: what GraphOutArgs points to. The alignment pool is one allocation per round (a rerun set's share lies in a later
     // round's pool; pool_of / aln_at tell where a set's pairs are after the last round it ran in)
     struct Pool { Buf<int32_t> node, pos; };
@@ -344,7 +387,8 @@ struct Run {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~Run() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
 
-    const void* fn_of(int k) const { return fn(inst[k], cols, d_wts.p != nullptr, graph); }
+    const void* fn_of(int k) const { return fn(inst[k], cols, d_wts.p != nullptr, graph, strand); }
+    const uint8_t* codes_as_added() const { return strand ? d_codes_used.p : d_codes.p; }   // what the row, coverage and profile kernels read
     uint64_t pools_of(uint32_t i) const { const MSet& S = sets[i]; return carve_pools(nullptr, S.sum_len, S.nseq, S.lmax, nullptr, nullptr, nullptr); }
 
     // runs f (0 = ok) between two events, waits for it, and adds the milliseconds it took on the device to *ms
@@ -390,14 +434,29 @@ struct Run {
         if (cols) {
             MCHK(d_base_col.alloc(nb)); MCHK(d_n_cols.alloc(ns));
             MCHK(hipMemsetAsync(d_n_cols.p, 0, std::max<size_t>(1, ns) * 4, s));
-            if (msa ? a.include_consensus != 0 : want_cov) MCHK(d_cns_col.alloc(cns_off[ns]));
+            if ((msa && a.include_consensus) || want_cov) MCHK(d_cns_col.alloc(cns_off[ns]));
         }
-        if ((wtd || graph) && a.weights) {
+        if ((wtd || graph || strand) && a.weights) {
             MCHK(d_wts.alloc(nb));
             MCHK(hipMemcpyAsync(d_wts.p, a.weights, nb, hipMemcpyHostToDevice, s));
         }
+        if ((graph || strand) && !a.weights) { MCHK(d_wts.alloc(nb)); MCHK(hipMemsetAsync(d_wts.p, 1, std::max<uint64_t>(1, nb), s)); }
+        if (strand) {
+            codes_rc.resize(codes.size());
+            if (a.weights) wts_rc.resize(codes.size());
+            for (uint64_t k = 0; k < nseq; k++) {
+                const uint64_t b = a.seq_off[k], L = a.seq_off[k + 1] - b;
+                for (uint64_t i = 0; i < L; i++) { codes_rc[b + i] = (uint8_t)(3 - codes[b + L - 1 - i]); if (a.weights) wts_rc[b + i] = a.weights[b + L - 1 - i]; }
+            }
+            MCHK(d_codes_rc.alloc(nb)); MCHK(d_codes_used.alloc(nb)); MCHK(d_wts_used.alloc(nb));
+            MCHK(d_reversed.alloc(nseq)); MCHK(d_score_fwd.alloc(nseq)); MCHK(d_score_rev.alloc(nseq)); MCHK(d_third.alloc(ns));
+            MCHK(hipMemcpyAsync(d_codes_rc.p, codes_rc.data(), nb, hipMemcpyHostToDevice, s));
+            if (a.weights) { MCHK(d_wts_rc.alloc(nb)); MCHK(hipMemcpyAsync(d_wts_rc.p, wts_rc.data(), nb, hipMemcpyHostToDevice, s)); }   // (without weights: d_wts, all 1, is its own reverse)
+            // (an empty sequence and a set's first non-empty one keep flag 0 and scores 0; a set without a base writes no count)
+            MCHK(hipMemsetAsync(d_reversed.p, 0, std::max<uint64_t>(1, nseq), s)); MCHK(hipMemsetAsync(d_score_fwd.p, 0, std::max<uint64_t>(1, nseq) * 4, s));
+            MCHK(hipMemsetAsync(d_score_rev.p, 0, std::max<uint64_t>(1, nseq) * 4, s)); MCHK(hipMemsetAsync(d_third.p, 0, std::max<size_t>(1, ns) * 4, s));
+        }
         if (graph) {
-            if (!a.weights) { MCHK(d_wts.alloc(nb)); MCHK(hipMemsetAsync(d_wts.p, 1, std::max<uint64_t>(1, nb), s)); }
             const uint64_t ne = nb + nseq;   // (a set's edges start at its first base's offset plus its first sequence's index)
             MCHK(d_aln_at.alloc(ns)); MCHK(d_aln_room.alloc(ns)); MCHK(d_aln_need.alloc(ns)); MCHK(d_aln_cnt.alloc(nseq)); MCHK(d_aln_score.alloc(nseq));
             MCHK(d_n_nodes.alloc(ns)); MCHK(d_n_edges.alloc(ns)); MCHK(d_node_code.alloc(nb)); MCHK(d_node_rank.alloc(nb)); MCHK(d_node_col.alloc(nb));
@@ -502,7 +561,8 @@ struct Run {
                     if (by[k].empty()) continue;
                     MArgs q{d_sets.p, d_order.p + base[k], (uint32_t)by[k].size(), d_counter.p + k, d_codes.p, d_soff.p, (uint8_t*)ws.p, slot[k],
                             a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p, a.gap_extend,
-                            d_base_col.p, d_n_cols.p, d_cns_col.p, d_wts.p, a.gap_open2, a.gap_extend2, go};
+                            d_base_col.p, d_n_cols.p, d_cns_col.p, d_wts.p, a.gap_open2, a.gap_extend2, go,
+                            StrandArgs{d_codes_rc.p, d_wts_rc.p ? d_wts_rc.p : d_wts.p, d_codes_used.p, d_wts_used.p, d_reversed.p, d_score_fwd.p, d_score_rev.p, d_third.p}};
                     void* kargs[] = {&q};
                     MCHK(hipLaunchKernel(fn_of(k), dim3(nslots[k]), dim3((uint32_t)inst[k].nt), kargs, 0, s));
                     o.launches++;
@@ -549,6 +609,13 @@ struct Run {
             o.cns_off[i + 1] = o.cns.size();
             o.cells += cells[i];
         }
+        if (strand) {   // (a set that was rerun rewrote its own part)
+            std::vector<uint32_t> third(ns);
+            o.reversed.assign(nseq, 0); o.score_fwd.assign(nseq, 0); o.score_rev.assign(nseq, 0);
+            MCHK(hipMemcpy(third.data(), d_third.p, ns * 4, hipMemcpyDeviceToHost));
+            if (nseq) { MCHK(hipMemcpy(o.reversed.data(), d_reversed.p, nseq, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(o.score_fwd.data(), d_score_fwd.p, nseq * 4, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(o.score_rev.data(), d_score_rev.p, nseq * 4, hipMemcpyDeviceToHost)); }
+            for (uint32_t i = 0; i < ns; i++) o.third_passes += third[i];
+        }
         return 0;
     }
 
@@ -584,7 +651,7 @@ struct Run {
         if (timed(&cov_ms, [&] {
                 MCHK(hipMemsetAsync(d_hist.p, 0, std::max<uint64_t>(1, hoff * stride) * 4, s));
                 if (seqs.n_chunks()) {
-                    k_cov_hist<<<seqs.blocks(), 256, 0, s>>>(seqs.d_rows.p, seqs.d_chunks.p, seqs.n_chunks(), d_base_col.p, d_codes.p, stride, d_hist.p);
+                    k_cov_hist<<<seqs.blocks(), 256, 0, s>>>(seqs.d_rows.p, seqs.d_chunks.p, seqs.n_chunks(), d_base_col.p, codes_as_added(), stride, d_hist.p);
                     MCHK(hipGetLastError());
                     o.launches++;
                 }
@@ -687,7 +754,7 @@ struct Run {
         MCHK(rows.upload(s));
         float rows_ms = 0;
         if (timed(&rows_ms, [&] {
-                k_msa_rows<<<rows.blocks(), 256, 0, s>>>(rows.d_rows.p, rows.d_chunks.p, rows.n_chunks(), d_base_col.p, d_codes.p, d_cns_col.p, d_cns.p, d_out.p);
+                k_msa_rows<<<rows.blocks(), 256, 0, s>>>(rows.d_rows.p, rows.d_chunks.p, rows.n_chunks(), d_base_col.p, codes_as_added(), d_cns_col.p, d_cns.p, d_out.p);
                 MCHK(hipGetLastError());
                 return 0;
             })) return -1;

@@ -120,6 +120,18 @@ __device__ void weigh_path(G& g, const uint32_t* path, const uint8_t* w, const u
     }
 }
 
+// ---- strand-ambiguous sets (DESIGN.md "General POA path", "Strand-ambiguous sets") ----
+// all lanes, once the orientation of the sequence at base offset b (sequence `seq` of the call) is chosen: its codes and weights as they
+// are added go to codes_used / wts_used, the choice and the two end-cell scores to the per-sequence arrays. The barrier at its end lets
+// thread 0 (traceback, add_alignment) and weigh_path read what all lanes wrote.
+template <int NT>
+__device__ void keep_strand(const MArgs& a, const uint64_t b, const uint32_t L, const uint64_t seq, const bool rev, const int32_t score_f, const int32_t score_r) {
+    const uint8_t *c = (rev ? a.sa.codes_rc : a.codes) + b, *w = (rev ? a.sa.wts_rc : a.wts) + b;
+    for (uint32_t i = threadIdx.x; i < L; i += NT) { a.sa.codes_used[b + i] = c[i]; a.sa.wts_used[b + i] = w[i]; }
+    if (threadIdx.x == 0) { a.sa.reversed[seq] = rev ? 1 : 0; a.sa.score_fwd[seq] = score_f; a.sa.score_rev[seq] = score_r; }
+    __syncthreads();
+}
+
 // one sequence of >= 2 bases (k_cov_hist: src = its first base, hoff = the first column of its set among all columns of the call) or one
 // consensus (k_cov_gather: src = its place beside the device's consensus text, dst = its place in the output)
 struct CRow { uint64_t src, dst, hoff; uint32_t len, ncols; };

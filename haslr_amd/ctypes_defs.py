@@ -190,6 +190,16 @@ class GraphOut(C.Structure):
                 ("gather_kernel_ms", C.c_double), ("gather_kernel_bytes", C.c_uint64), ("slot_reruns", C.c_uint32), ("aln_reruns", C.c_uint32)]
 
 
+class PoaStrandWant(C.Structure):
+    _fields_ = [("want_msa", C.c_int32), ("include_consensus", C.c_int32), ("want_coverage", C.c_int32), ("want_profile", C.c_int32)]
+
+
+class StrandOut(C.Structure):
+    _fields_ = [("n_set", C.c_uint32), ("n_seq", C.c_uint64), ("cns_off", u64p), ("cns", C.POINTER(C.c_char)), ("reversed", u8p), ("score_fwd", i32p), ("score_rev", i32p),
+                ("n_rows", u32p), ("n_cols", u32p), ("msa_off", u64p), ("msa", C.POINTER(C.c_char)), ("coverage", u32p), ("profile", u32p),
+                ("dp_cells", C.c_uint64), ("seq_bases", C.c_uint64), ("n_aligned", C.c_uint64), ("third_passes", C.c_uint64), ("slot_reruns", C.c_uint32)]
+
+
 def msa_to_lists(o):
     """(rows per set, consensus per set) of an MsaOut"""
     n = o.n_set

@@ -16,7 +16,7 @@ _lib = None
 SYMBOLS = ["hx_last_error", "hx_device_count", "hx_ctx_create", "hx_ctx_destroy", "hx_upload", "hx_set_read_shard", "hx_set_prefiltered",
            "hx_chain_reads", "hx_edge_support", "hx_edge_coords", "hx_poa_batch", "hx_free_chain", "hx_free_edges",
            "hx_free_coords", "hx_free_cns", "hx_edge_emit", "hx_edge_records_bytes", "hx_edge_records_export",
-           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_poa_graph", "hx_free_graph", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
+           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_poa_graph", "hx_free_graph", "hx_poa_strand", "hx_free_strand", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
            "hx_set_option", "hx_get_option", "hx_option_names", "hx_poa_memory_stats", "hx_poa_release_workspace", "hx_poa_prune_stats", "hx_poa_retry_stats", "hx_group_set_timeout", "hx_group_inject_fault", "hx_poa_reserve", "hx_poa_host_times", "hx_poa_arena_stats", "hx_group_rccl_ranks",
            "hx_group_create", "hx_group_destroy", "hx_group_size", "hx_group_ctx", "hx_group_transport", "hx_edge_merge", "hx_group_backend_fill", "hx_group_exchange_stats"]
 
@@ -55,6 +55,8 @@ def lib():
         L.hx_poa_weighted_convex.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.c_int, C.c_int, C.POINTER(T.WcnsOut)]
         L.hx_poa_graph.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.GraphOut)]
         L.hx_free_graph.argtypes = [C.c_void_p, C.POINTER(T.GraphOut)]
+        L.hx_poa_strand.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.PoaStrandWant), C.POINTER(T.StrandOut)]
+        L.hx_free_strand.argtypes = [C.c_void_p, C.POINTER(T.StrandOut)]
         L.hx_free_chain.argtypes = [C.c_void_p, C.POINTER(T.ChainOut)]
         L.hx_free_edges.argtypes = [C.c_void_p, C.POINTER(T.EdgesOut)]
         L.hx_free_coords.argtypes = [C.c_void_p, C.POINTER(T.CoordsOut)]
@@ -144,6 +146,38 @@ def _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_e
     return T.PoaConvexParams(match, mismatch, gap_open, gap_open if gap_extend is None else gap_extend, gap_open2, gap_extend2, T.POA_TYPES[type])
 
 
+def _weight_bytes(sets, weights, qualities):
+    """the weights of a call as the C-ABI takes them (a byte per base, in the order of the bases), or None when neither weights nor
+    qualities are given; the checks and errors HipContext.poa_weighted documents"""
+    import numpy as np
+    if weights is not None and qualities is not None:
+        raise ValueError("give weights or qualities, not both")
+    given = weights if weights is not None else qualities
+    if given is None:
+        return None
+    if len(given) != len(sets):
+        raise ValueError(f"{len(given)} sets of weights for {len(sets)} sets of sequences")
+    flat = bytearray()
+    for i, (st, ws) in enumerate(zip(sets, given)):
+        if len(ws) != len(st):
+            raise ValueError(f"set {i}: {len(ws)} lists of weights for {len(st)} sequences")
+        for k, (q, w) in enumerate(zip(st, ws)):
+            if len(w) != len(q):
+                raise ValueError(f"set {i}, sequence {k}: {len(w)} weights for {len(q)} bases")
+            if qualities is not None:
+                vals = np.array([ord(ch) for ch in w], dtype=np.int64) - 33
+                bad = np.nonzero((vals < 1) | (vals > 93))[0]
+            else:
+                vals = np.asarray(w, dtype=np.int64)
+                bad = np.nonzero((vals < 1) | (vals > 255))[0]
+            if bad.size:
+                p = int(bad[0])
+                what = f"the quality character {w[p]!r} gives" if qualities is not None else "a weight of"
+                raise ValueError(f"set {i}, sequence {k}, position {p}: {what} {int(vals[p])}, which is not accepted (weights are 1..255, qualities '\"'..'~')")
+            flat += vals.astype(np.uint8).tobytes()
+    return bytes(flat) or b"\0"
+
+
 def _counters(o, *more):
     """the counters every consensus output struct carries, and the named extra fields of o"""
     return {k: getattr(o, k) for k in ("dp_cells", "seq_bases", "n_aligned") + more}
@@ -156,6 +190,11 @@ def _counters(o, *more):
 # consensus_nodes (uint32 array) the node of every consensus base.
 GraphRecord = namedtuple("GraphRecord", "node_base node_rank node_col edge_from edge_to edge_w n_cols sequences consensus consensus_nodes")
 GraphSequence = namedtuple("GraphSequence", "path alignment score")
+
+
+# One set of HipContext.poa_strand (include/haslr_types.h, hx_strand_out): the consensus; per GIVEN sequence whether its reverse complement
+# was added and the (forward, reverse-complemented) end-cell scores; the MSA rows, the coverage and the profile, each None unless asked for
+StrandRecord = namedtuple("StrandRecord", "consensus reversed scores rows coverage profile")
 
 
 def _out_edges_in_list_order(rec):
@@ -461,34 +500,8 @@ class HipContext:
         counters if stats): dp_cells, seq_bases, n_aligned as poa_sequences_affine has them, and cov_kernel_ms / cov_kernel_bytes of the
         coverage kernels. gap_open2 and gap_extend2 (both or neither) switch to the convex gap model of poa_sequences_convex
         (hx_poa_weighted_convex)."""
-        import numpy as np
         _check_type(type)
-        if weights is not None and qualities is not None:
-            raise ValueError("give weights or qualities, not both")
-        given = weights if weights is not None else qualities
-        wbytes = None
-        if given is not None:
-            if len(given) != len(sets):
-                raise ValueError(f"{len(given)} sets of weights for {len(sets)} sets of sequences")
-            flat = bytearray()
-            for i, (st, ws) in enumerate(zip(sets, given)):
-                if len(ws) != len(st):
-                    raise ValueError(f"set {i}: {len(ws)} lists of weights for {len(st)} sequences")
-                for k, (q, w) in enumerate(zip(st, ws)):
-                    if len(w) != len(q):
-                        raise ValueError(f"set {i}, sequence {k}: {len(w)} weights for {len(q)} bases")
-                    if qualities is not None:
-                        vals = np.array([ord(ch) for ch in w], dtype=np.int64) - 33
-                        bad = np.nonzero((vals < 1) | (vals > 93))[0]
-                    else:
-                        vals = np.asarray(w, dtype=np.int64)
-                        bad = np.nonzero((vals < 1) | (vals > 255))[0]
-                    if bad.size:
-                        p = int(bad[0])
-                        what = f"the quality character {w[p]!r} gives" if qualities is not None else "a weight of"
-                        raise ValueError(f"set {i}, sequence {k}, position {p}: {what} {int(vals[p])}, which is not accepted (weights are 1..255, qualities '\"'..'~')")
-                    flat += vals.astype(np.uint8).tobytes()
-            wbytes = bytes(flat) or b"\0"
+        wbytes = _weight_bytes(sets, weights, qualities)
         o = T.WcnsOut()
         cp = _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
         if cp is not None:
@@ -551,6 +564,45 @@ class HipContext:
             st = _counters(o, "gather_kernel_ms", "gather_kernel_bytes", "slot_reruns", "aln_reruns")
         finally:
             lib().hx_free_graph(self._h, C.byref(o))
+        return (res, st) if stats else res
+
+    def poa_strand(self, sets, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=None, gap_open2=None, gap_extend2=None, weights=None, qualities=None,
+                   msa=False, include_consensus=False, coverage=False, profile=False, stats=False):
+        """the consensus of sets whose sequences may lie on either strand (hx_poa_strand; spoa's -s / --strand-ambiguous): every sequence
+        after a set's first non-empty one is aligned as given and reverse-complemented, and the orientation with the higher end-cell
+        score is added (ties go forward). A list with one StrandRecord per set: consensus; reversed (a bool per given sequence: its
+        reverse complement was added); scores (per given sequence (forward, reverse-complemented), (0, 0) for an empty sequence and the
+        first non-empty one); rows (msa=True: the alignment text as poa_msa has it, a reversed sequence's row being its gapped reverse
+        complement, with include_consensus the consensus last), coverage and profile (as poa_weighted has them, counting the letters as
+        added), each None unless asked for. gap_extend None (or equal to gap_open) is the linear gap model; gap_open2 and gap_extend2
+        (both or neither) give the convex one. weights / qualities: as for poa_weighted, with its checks and errors; a reversed
+        sequence's weights are reversed with it. With stats=True returns (records, counters): dp_cells (both orientations), seq_bases,
+        n_aligned, third_passes (the sequences whose reverse complement won) and slot_reruns."""
+        import numpy as np
+        _check_type(type)
+        ge = gap_open if gap_extend is None else gap_extend
+        cp = _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
+        if cp is None:   # one piece: a second one that is the first again never wins
+            cp = T.PoaConvexParams(match, mismatch, gap_open, ge, gap_open, ge, T.POA_TYPES[type])
+        wbytes = _weight_bytes(sets, weights, qualities)
+        want = T.PoaStrandWant(int(bool(msa)), int(bool(msa and include_consensus)), int(bool(coverage)), int(bool(profile)))
+        o = T.StrandOut()
+        n_sets, set_off, seq_off, bases = _flatten_sets(sets)
+        self._chk(lib().hx_poa_strand(self._h, n_sets, set_off, seq_off, bases, wbytes, C.byref(cp), C.byref(want), C.byref(o)))
+        try:
+            n_seq = int(o.n_seq)
+            cns, cov, prof = T.wcns_to_lists(o)
+            rows = T.msa_to_lists(o)[0] if msa else None
+            flags, sf, sr = T.arr(o.reversed, n_seq, np.uint8).tolist(), T.arr(o.score_fwd, n_seq, np.int32).tolist(), T.arr(o.score_rev, n_seq, np.int32).tolist()
+            res, k = [], 0
+            for i, st in enumerate(sets):
+                n = len(st)
+                res.append(StrandRecord(cns[i], [bool(f) for f in flags[k:k + n]], list(zip(sf[k:k + n], sr[k:k + n])), rows[i] if msa else None,
+                                        cov[i] if coverage else None, prof[i] if profile else None))
+                k += n
+            st = _counters(o, "third_passes", "slot_reruns")
+        finally:
+            lib().hx_free_strand(self._h, C.byref(o))
         return (res, st) if stats else res
 
     def poa_phase_cycles(self):

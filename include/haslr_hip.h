@@ -61,8 +61,9 @@ void hx_ctx_destroy(hx_ctx*);
  *                    its first round of workspace slots, forcing the rerun of sets in larger ones), poa_affine (1: hx_poa_sequences_affine
  *                    with gap_extend == gap_open runs the affine kernel instead of the linear paths), poa_weighted (1: hx_poa_weighted
  *                    without weights runs the weighted kernels on weights of 1 instead of the unit-weight ones), poa_convex (1: the convex
- *                    entries with gap_extend2 <= gap_extend run the convex kernel instead of the affine entries), and poa_graph_aln_cap
- *                    (hx_poa_graph: cap, in pairs, of a set's first share of the alignment pool, forcing its rerun with the exact room).
+ *                    entries with gap_extend2 <= gap_extend run the convex kernel instead of the affine entries), poa_graph_aln_cap
+ *                    (hx_poa_graph: cap, in pairs, of a set's first share of the alignment pool, forcing its rerun with the exact room), and
+ *                    poa_strand_one_h (hx_poa_strand: 1, the default, keeps one score matrix per slot; the only route built).
  *                    Results never depend on any of them. */
 int hx_set_option(hx_ctx*, const char* name, const char* value);
 int hx_get_option(const hx_ctx*, const char* name, double* value);
@@ -157,6 +158,21 @@ int hx_poa_weighted_convex(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, co
  *                     call of a simpler model on the richer kernel, as elsewhere. Not pinned against spoa, like the rest of the general path. */
 int hx_poa_graph(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params*, hx_graph_out* out);
 void hx_free_graph(hx_ctx*, hx_graph_out*);
+/*   hx_poa_strand     the consensus of sets whose sequences may lie on either strand (spoa's command-line switch -s / --strand-ambiguous;
+ *                     DESIGN.md "General POA path", "Strand-ambiguous sets"; the arrays: haslr_types.h, hx_strand_out). For every non-empty
+ *                     sequence of a set, in the given order: the set's first one goes in forward; every later one is aligned to the graph as it
+ *                     stands both as given and reverse-complemented (reversed, every code c replaced by 3 - c: a letter that is not ACGT reads
+ *                     as A and its complement is T), under the call's type and gap model, and the orientation with the higher end-cell score
+ *                     is added (a tie, and a local alignment without a cell above 0 either way, goes forward). With weights a reversed
+ *                     sequence's weights are reversed with it. One entry over the convex parameters, by hx_poa_graph's rules for the gap
+ *                     model (sequences of up to 8191, 16383 and 32767 bases); weights as for hx_poa_weighted (1..255, 0 refused), or NULL.
+ *                     Every type runs the general path. The errors are hx_poa_graph's with this entry's name in front. Options
+ *                     poa_modes_slot_kb and poa_workspace_gb act as on the other entries; poa_strand_one_h (default 1) keeps one score matrix
+ *                     per workspace slot, so that a sequence whose reverse complement wins runs that orientation's DP once more before the
+ *                     traceback: the only route there is, a value of 0 changes nothing. Not pinned against spoa, like the rest of the general
+ *                     path: the rules are written after spoa's main.cpp as published and the tests hold them to a CPU restatement. */
+int hx_poa_strand(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params*, const hx_poa_strand_want*, hx_strand_out* out);
+void hx_free_strand(hx_ctx*, hx_strand_out*);
 void hx_free_chain(hx_ctx*, hx_chain_out*);
 void hx_free_edges(hx_ctx*, hx_edges_out*);
 void hx_free_coords(hx_ctx*, hx_coords_out*);

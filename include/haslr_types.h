@@ -242,6 +242,40 @@ typedef struct {
     uint32_t slot_reruns, aln_reruns;
 } hx_graph_out;
 
+/* hx_poa_strand: what is wanted beside the consensus, the flags and the scores. */
+typedef struct {
+    int32_t want_msa;          /* 0 / 1: the alignment text of every set */
+    int32_t include_consensus; /* 0 / 1: with want_msa, the consensus is the last row of every set */
+    int32_t want_coverage;     /* 0 / 1: the coverage of every consensus base */
+    int32_t want_profile;      /* 0 / 1: and the four letter counts of its column (the coverage is filled in as well) */
+} hx_poa_strand_want;
+
+/* hx_poa_strand: the consensus of sets whose sequences may lie on either strand (DESIGN.md "General POA path", "Strand-ambiguous
+ * sets"). Per GIVEN sequence k of the call (all sets, in order; n_seq of them): reversed[k] is 1 when its reverse complement was the
+ * orientation added to the graph, score_fwd[k] and score_rev[k] are the end-cell scores of the sequence and of its reverse complement
+ * against the graph as it stood (both 0 for an empty sequence and for a set's first non-empty one, which meet no DP). Everything else
+ * sees a sequence as it was added: the MSA row of a reversed sequence is its gapped reverse complement, coverage and profile count its
+ * complemented letters. n_rows / n_cols / msa_off / msa are hx_msa_out's (NULL unless want_msa), coverage / profile hx_wcns_out's (NULL
+ * unless asked for). dp_cells counts both orientations (2 x nodes x length per aligned sequence); third_passes the sequences whose
+ * reverse complement won, each of which cost one more DP pass; slot_reruns the sets that ran again in a larger workspace slot. */
+typedef struct {
+    uint32_t n_set;
+    uint64_t n_seq;
+    uint64_t* cns_off; /* n_set+1 */
+    char* cns;
+    uint8_t* reversed;  /* n_seq */
+    int32_t* score_fwd; /* n_seq */
+    int32_t* score_rev; /* n_seq */
+    uint32_t* n_rows;   /* n_set, or NULL */
+    uint32_t* n_cols;   /* n_set, or NULL */
+    uint64_t* msa_off;  /* n_set+1, or NULL */
+    char* msa;          /* or NULL */
+    uint32_t* coverage; /* cns_off[n_set], or NULL */
+    uint32_t* profile;  /* 4 * cns_off[n_set], or NULL */
+    uint64_t dp_cells, seq_bases, n_aligned, third_passes;
+    uint32_t slot_reruns;
+} hx_strand_out;
+
 #ifdef __cplusplus
 }
 #endif

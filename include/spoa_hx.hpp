@@ -394,6 +394,64 @@ inline std::vector<GraphData> graph_batch(const std::vector<std::vector<std::str
     return graph_batch(detail::pointers(sets), detail::pointers(weights), type, m, n, g, e, q, c);
 }
 
+// strand-ambiguous sets (spoa's command-line switch -s / --strand-ambiguous) in ONE device call (hx_poa_strand): every sequence after a
+// set's first non-empty one is aligned to the graph as given and reverse-complemented, and the orientation with the higher end-cell score
+// is added, ties forward. Per set: the consensus; per GIVEN sequence whether its reverse complement was added and the scores of the two
+// orientations; with msa the rows (a reversed sequence's row is its gapped reverse complement; with include_consensus the consensus is
+// the last row). weights as for weighted_batch (a reversed sequence's weights are reversed with it), or empty: every weight is 1.
+// (q, c) == (g, e) is one gap piece, and then e == g the linear model.
+struct Stranded {
+    std::string consensus;
+    std::vector<bool> reversed;
+    std::vector<std::int32_t> score_forward, score_reversed;
+    std::vector<std::string> rows;   // empty unless asked for
+};
+inline std::vector<Stranded> strand_batch(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights,
+                                          AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, std::int8_t q = -8, std::int8_t c = -8,
+                                          bool msa = false, bool include_consensus = false) {
+    if (!weights.empty() && weights.size() != sets.size()) throw std::invalid_argument("spoa_hx: strand_batch needs one set of weights per set of sequences, or none");
+    const detail::Flat f(sets);
+    std::vector<std::uint8_t> w;
+    for (std::size_t i = 0; i < sets.size() && !weights.empty(); i++) {
+        const auto& st = *sets[i];
+        if (weights[i]->size() != st.size()) throw std::invalid_argument("spoa_hx: strand_batch: a set has another number of weight vectors than of sequences");
+        for (std::size_t k = 0; k < st.size(); k++) {
+            const auto& wk = (*weights[i])[k];
+            if (wk.size() != st[k].size()) throw std::invalid_argument("spoa_hx: strand_batch: a sequence has another number of weights than of bases");
+            w.insert(w.end(), wk.begin(), wk.end());
+        }
+    }
+    if (!weights.empty() && w.empty()) w.push_back(1);   // (no base at all: a pointer that is not null, nothing behind it is read)
+    const hx_poa_convex_params cp{m, n, g, e, q, c, static_cast<std::int32_t>(type)};
+    const hx_poa_strand_want want{msa ? 1 : 0, msa && include_consensus ? 1 : 0, 0, 0};
+    hx_strand_out out;
+    return detail::locked_call([&](hx_ctx* ctx) { return hx_poa_strand(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), weights.empty() ? nullptr : w.data(), &cp, &want, &out); },
+                               [&](hx_ctx* ctx) -> std::vector<Stranded> {
+        std::vector<Stranded> res(sets.size());
+        for (std::size_t i = 0; i < sets.size(); i++) {
+            Stranded& d = res[i];
+            d.consensus.assign(out.cns + out.cns_off[i], out.cns + out.cns_off[i + 1]);
+            for (std::uint64_t k = f.set_off[i]; k < f.set_off[i + 1]; k++) {
+                d.reversed.push_back(out.reversed[k] != 0);
+                d.score_forward.push_back(out.score_fwd[k]);
+                d.score_reversed.push_back(out.score_rev[k]);
+            }
+            if (msa)
+                for (std::uint32_t r = 0; r < out.n_rows[i]; r++) {
+                    const char* p = out.msa + out.msa_off[i] + static_cast<std::uint64_t>(r) * out.n_cols[i];
+                    d.rows.emplace_back(p, p + out.n_cols[i]);
+                }
+        }
+        hx_free_strand(ctx, &out);
+        return res;
+    });
+}
+inline std::vector<Stranded> strand_batch(const std::vector<std::vector<std::string>>& sets, const std::vector<std::vector<std::vector<std::uint8_t>>>& weights, AlignmentType type,
+                                          std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, std::int8_t q = -8, std::int8_t c = -8, bool msa = false,
+                                          bool include_consensus = false) {
+    return strand_batch(detail::pointers(sets), detail::pointers(weights), type, m, n, g, e, q, c, msa, include_consensus);
+}
+
 // Graphviz text of a graph, after spoa's Graph::print_dot: per node `id [label = "id - LETTER"]`, filled for the nodes of the consensus;
 // per out-edge, in out-list order, `from -> to [label = "weight"]`; one dotted line without arrowhead per pair of aligned nodes (nodes that
 // share a column), from the smaller to the larger id

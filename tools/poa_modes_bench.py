@@ -21,7 +21,12 @@ compared with the convex restatement (tests/poa_convex_ref.cpp). And rows (a) an
 (hx_poa_graph, linear scores, unit weights; part "graph", which needs general and outputs): kernel time against the MSA's in the same
 process ("over_msa") and against the consensus-only general path, the gather kernel on its own (time by device events, the bytes it has to
 move, GB/s), the sets that were rerun because their alignments outgrew their share of the alignment pool under the default estimate, and
-the sample compared with the graph restatement (tests/poa_graph_ref.cpp). --only picks the parts to run; --package-root runs the parts another
+the sample compared with the graph restatement (tests/poa_graph_ref.cpp). And the rows of workload (a) run the strand-ambiguous entry (hx_poa_strand,
+linear scores, unit weights, with the rows and the consensus row; part "strand", which needs general and outputs) on the same sets with
+every member after the first reverse-complemented with probability 1/2: kernel time against the MSA's on the sets as they are, which is
+the same call on the sets oriented beforehand ("over_msa", with the smallest and largest ratio the repeats allow), the sequences whose
+reverse complement won and with them the ratio the DP passes alone predict (2 + third_passes / aligned sequences), and a sample compared
+with the strand restatement (tests/poa_strand_ref.cpp). --rows picks the rows, --only picks the parts to run; --package-root runs the parts another
 build of the package has (a checkout of the parent commit, say) in the same way, for a comparison on one machine. Prints one JSON line,
 and writes it to --out when given."""
 import argparse
@@ -38,7 +43,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
-PARTS = ["general", "tuned_nw", "cpu", "affine", "outputs", "convex", "graph"]   # outputs: the MSA and the weighted entry
+PARTS = ["general", "tuned_nw", "cpu", "affine", "outputs", "convex", "graph", "strand"]   # outputs: the MSA and the weighted entry
 
 
 def text(a):
@@ -110,6 +115,7 @@ def main():
     ap.add_argument("--affine-scores", type=int, nargs=4, default=[5, -4, -8, -6], metavar=("M", "N", "G", "E"), help="match, mismatch, gap open, gap extend of the affine rows")
     ap.add_argument("--convex-scores", type=int, nargs=6, default=[5, -4, -8, -6, -10, -4], metavar=("M", "N", "G", "E", "Q", "C"), help="match, mismatch and the two gap pieces of the convex rows")
     ap.add_argument("--only", nargs="+", default=PARTS, choices=PARTS, help="the parts of every row to run (outputs: the MSA and the weighted entry, which need general; ratios are given against the parts that ran)")
+    ap.add_argument("--rows", nargs="+", default=["a_sw", "a_nw", "a_ov", "b_ov"], choices=["a_sw", "a_nw", "a_ov", "b_ov"], help="the rows to run")
     ap.add_argument("--package-root", default=ROOT, help="the tree whose built haslr_amd package runs (default: this one); parts it does not have are left out")
     ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args()
@@ -125,6 +131,8 @@ def main():
         only.discard("convex")
     if not hasattr(hip.HipContext, "poa_graph"):
         only.discard("graph")
+    if not hasattr(hip.HipContext, "poa_strand"):
+        only.discard("strand")
     rng = np.random.default_rng(a.seed)
     loads = {"a_sw": ("sw", workload_a(rng, a.sets_a, True)), "a_nw": ("nw", workload_a(rng, a.sets_a, False))}
     loads["a_ov"] = ("ov", loads["a_nw"][1])
@@ -139,6 +147,8 @@ def main():
         cref = cvxlib.ConvexRef(d)
         wrng = np.random.default_rng(a.seed + 1000)   # (a generator of its own: the workloads are those of the earlier lines)
         for name, (mode, sets) in loads.items():
+            if name not in a.rows:
+                continue
             r = {"mode": mode, "sets": len(sets)}
             note(name, "sets", len(sets))
             for path, opts in (("general", {"poa_general": 1}), ("tuned_nw", {})):
@@ -253,6 +263,28 @@ def main():
                     out = list(ex.map(lambda st: gref.graph(st, mode), sample))
                 r["graph_sample_equal"] = all(grflib.same(x, y) for x, y in zip(ctx.poa_graph(sample, mode), out))
                 note(name, "graph", r["graph"]["kernel_ms_median"], "ms")
+            if "strand" in only and name.startswith("a_"):
+                import strlib
+                srng = np.random.default_rng(a.seed + 2000)   # (a generator of its own, as for the weights)
+                mixed = [[q if k == 0 or srng.random() < 0.5 else strlib.rc(q) for k, q in enumerate(st)] for st in sets]
+                sst = {}
+
+                def strand_call():
+                    nonlocal sst
+                    sst = ctx.poa_strand(mixed, mode, msa=True, include_consensus=True, stats=True)[1]
+                ms = gpu_time(ctx, strand_call, a.repeats)
+                med, msa = float(np.median(ms)), r["msa"]
+                r["strand"] = {"kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
+                               "over_msa": round(med / msa["kernel_ms_median"], 4), "over_msa_min": round(min(ms) / msa["kernel_ms_max"], 4), "over_msa_max": round(max(ms) / msa["kernel_ms_min"], 4),
+                               "third_passes": int(sst["third_passes"]), "n_aligned": int(sst["n_aligned"]), "dp_cells": int(sst["dp_cells"]),
+                               "dp_passes_per_sequence": round(2 + sst["third_passes"] / max(1, sst["n_aligned"] - len(sets)), 4), "slot_reruns": int(sst["slot_reruns"])}
+                sref = strlib.StrandRef(d)
+                few = mixed[:max(1, a.cpu_sample // 4)]   # (the restatement aligns every sequence twice, on full matrices)
+                with ThreadPoolExecutor(16) as ex:
+                    out = list(ex.map(lambda st: sref.strand(st, mode, include_consensus=True), few))
+                got = ctx.poa_strand(few, mode, msa=True, include_consensus=True, coverage=True, profile=True)
+                r["strand_sample_equal"] = got == out
+                note(name, "strand", r["strand"]["kernel_ms_median"], "ms")
             res[name] = r
     ctx.close()
     print(json.dumps(res))
