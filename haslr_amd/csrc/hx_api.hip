@@ -296,8 +296,9 @@ static int finish_edges(hx_ctx* c, uint64_t n, hx_edges_out* out) {
     HIPCHK(c->rec.reserve(n));
     c->tick();
     hxk::iota_u32(perm.p, n, s);
-    hxk::radix_sort_pairs(c->rec_un.key.p, perm.p, key_tmp.p, perm_tmp.p, n, bits, bits, s, c->ws);
+    // the keys are sorted in the copy: rec_un stays the record set as it was emitted or imported, for a later hx_edge_records_export
     if (n) HIPCHK(hipMemcpyAsync(c->rec.key.p, c->rec_un.key.p, n * 8, hipMemcpyDeviceToDevice, s));
+    hxk::radix_sort_pairs(c->rec.key.p, perm.p, key_tmp.p, perm_tmp.p, n, bits, bits, s, c->ws);
     hxk::edge_gather(c->rec_un.view(), perm.p, n, c->rec.view(), s);
     hxk::segment_flags(c->rec.key.p, n, flag.p, s);
     hxk::exclusive_scan_u32(flag.p, fscan.p, n, s, c->ws);

@@ -184,7 +184,8 @@ void hx_free_wcns(hx_ctx*, hx_wcns_out*);
  *   hx_edge_emit            emit this shard's records (unsorted) on the device, returns their number
  *   hx_edge_records_bytes   bytes per record in the packed exchange layout (44: a forward record and its twin travel as one
  *                           88-byte unit - key, read id, compact indices and the two trimmed anchor alignments, once)
- *   hx_edge_records_export  pack the local records into a caller-owned DEVICE buffer (n * bytes; n is even)
+ *   hx_edge_records_export  pack the local records into a caller-owned DEVICE buffer (n * bytes; n is even): the set as hx_edge_emit or
+ *                           hx_edge_records_import left it, in that order - the sort of hx_edge_support / _import works on a copy
  *   hx_edge_records_import  replace the record set by n records unpacked from a DEVICE buffer (all ranks,
  *                           rank order), then sort + segment; fills `out` like hx_edge_support */
 int hx_edge_emit(hx_ctx*, const hx_params*, uint64_t* n_records);

@@ -26,6 +26,8 @@ import math
 import os
 import random
 
+import numpy as np
+
 import util
 
 OTHER = "=XSNH"
@@ -166,6 +168,20 @@ class Case:
 
     def tagged(self, tag):
         return [h.index for h in self.hits if h.tag == tag]
+
+    def spread(self, n_reads, at):
+        """move read r to index at[r] among n_reads reads; every other read has 4 bases and no hit. The manifest follows."""
+        assert len(at) == len(self.reads) and len(set(at)) == len(at) and max(at) < n_reads
+        fill = [4, "ACGT"]
+        reads = [fill] * n_reads
+        for old, new in enumerate(at):
+            reads[new] = self.reads[old]
+        self.reads = reads
+        for h in self.hits:
+            h.read = at[h.read]
+        self.man["n_aln"] = {at[r]: n for r, n in self.man["n_aln"].items()}
+        for k in ("serial_reads", "model_reads"):
+            self.man[k] = [at[r] for r in self.man[k]]
 
 
 # =====================================================================================================================
@@ -521,10 +537,41 @@ ADD = {"hit_counts": add_hit_counts, "trims": add_trims, "thresholds": add_thres
        "ties_large": add_ties_large, "coords": add_coords}
 
 
-def build(out_dir, names, seed=1):
-    """write the families `names` into one data set under out_dir; -> (file prefix, Case)"""
+def many_reads_edges(n_reads):
+    """read indices on both sides of the scans' ownership edges over the reads (4 per thread, 1 024 per block, 2^20 per block of
+    blocks), the first and the last"""
+    return [i for i in (0, 1023, 1024, 1025, (1 << 20) - 1, 1 << 20) if i < n_reads - 1] + [n_reads - 1]
+
+
+def many_reads_at(n_reads):
+    """where the ten reads of hit_counts (1, 2, 16, 17, 63, 64, 65, 130, 1000 and 90 raw hits) go among n_reads reads: those with
+    alignments and pairs to the indices of many_reads_edges (the 1000-hit read last), the others to small indices in between"""
+    e = many_reads_edges(n_reads)
+    at = dict(zip((1, 2, 3, 4, 6, 7), e[:-1]))
+    at[8] = e[-1]
+    free = (i for i in range(2, n_reads) if i not in e)
+    return [at[r] if r in at else next(free) for r in range(10)]
+
+
+def check_many_reads(case, n_reads, chain, edges):
+    """the planted reads kept their alignments where they went, and the reads at the scans' edges carry alignments, compact
+    alignments and pairs: the three scans over the reads have non-zero values on both sides of every edge"""
+    n_aln, n_cmp = np.diff(chain["read_off"]), np.diff(chain["cmp_off"])
+    assert len(n_aln) == n_reads
+    for r, n in case.man["n_aln"].items():
+        assert n_aln[r] == n, f"read {r}: {n_aln[r]} alignments, planted {n}"
+    with_pairs = set((edges["lr"][edges["lr"] < 0x80000000]).tolist())
+    for r in many_reads_edges(n_reads):
+        assert n_aln[r] > 0 and n_cmp[r] > 1 and r in with_pairs, f"read {r} carries nothing across the scan's edge"
+    assert int((n_aln > 0).sum()) == len([n for n in case.man["n_aln"].values() if n])
+
+
+def build(out_dir, names, seed=1, n_reads=None, reads_at=None):
+    """write the families `names` into one data set under out_dir; -> (file prefix, Case). n_reads, reads_at: Case.spread"""
     case = Case(seed)
     for n in names:
         ADD[n](case)
+    if n_reads is not None:
+        case.spread(n_reads, reads_at)
     os.makedirs(out_dir, exist_ok=True)
     return case.write(os.path.join(out_dir, "in")), case

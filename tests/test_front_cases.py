@@ -128,3 +128,17 @@ def test_manifest_holds(family, cases):
     if family == "hit_counts":
         assert max(np.diff(run.chain_out()["read_off"])) >= 1000
     run.close(); be.close(); ds.close()
+
+
+@pytest.mark.parametrize("n_reads", [1025, (1 << 20) + 1030])
+def test_many_reads_manifest_holds(n_reads, tmp_path):
+    """hit_counts spread over 1 025 and 2^20 + 1 030 reads (the GPU test of the scans over the reads, test_edge_records_gpu.py): the
+    reads keep what the family planted, and those at the scans' edges carry alignments and pairs"""
+    pre, case = fc.build(str(tmp_path / "in"), ["hit_counts"], n_reads=n_reads, reads_at=fc.many_reads_at(n_reads))
+    assert fc.many_reads_edges(n_reads) == ([0, 1023, 1024] if n_reads == 1025 else [0, 1023, 1024, 1025, (1 << 20) - 1, 1 << 20, n_reads - 1])
+    assert set(fc.many_reads_edges(n_reads)) <= set(fc.many_reads_at(n_reads)) and len(set(fc.many_reads_at(n_reads))) == 10
+    ds, be, run = oracle(pre, None)
+    assert ds.reads.n == n_reads
+    check_manifest(case, run.chain_out(), run.edges_out(sides=False))
+    fc.check_many_reads(case, n_reads, run.chain_out(), run.edges_out(sides=False))
+    run.close(); be.close(); ds.close()
