@@ -105,6 +105,9 @@ void hxh_run_timings(const hxh_run*, double out[5]);
 /* results for tests: number of surviving undirected edges this run processed (= all of them unless sharded) / in total; their consensus */
 uint32_t hxh_run_n_edges(const hxh_run*);
 uint32_t hxh_run_n_edges_total(const hxh_run*);
+/* the edges this run processed, in the order of the entries of hxh_run_coords_out / hxh_run_cns_out (the order of the reference's work queue,
+ * Assemble.cpp:365-434): entry i is the arc from vertex[i] to key[i], both contig << 1 | strand; hxh_run_n_edges entries each (needs hxh_run_coords) */
+void hxh_run_selected_edges(const hxh_run*, uint32_t* vertex, uint32_t* key);
 const hx_chain_out* hxh_run_chain_out(const hxh_run*);
 const hx_edges_out* hxh_run_edges_out(const hxh_run*);
 const hx_coords_out* hxh_run_coords_out(const hxh_run*);

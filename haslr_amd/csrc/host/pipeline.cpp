@@ -288,7 +288,9 @@ void write_stage_logs(Run& r) {
         if (fc && x.have_cns) {
             fprintf(fc, "calc_cns %u:%c -> %u:%c\n", v >> 1, "+-"[v & 1], key >> 1, "+-"[key & 1]);
             fprintf(fc, "[shared_region] head_end:%u\ttail_beg:%u\n", a->head_end, a->tail_beg);
-            fprintf(fc, ">CONSENSUS\n%s\n", x.cns.c_str());
+            // the string the arc ends with: on an arc that is its own twin (hairpin) the reference logs edge1.cns_seq after the twin's
+            // assignment has overwritten it with the reverse complement (Assemble.cpp:554-557)
+            fprintf(fc, ">CONSENSUS\n%s\n", a->cns_id >= 0 ? r.cns[(size_t)a->cns_id].c_str() : x.cns.c_str());
         }
     }
     if (fk) fclose(fk);
@@ -676,6 +678,10 @@ extern "C" int hxh_run_write_longread_index(const hxh_run* p, const char* path) 
 extern "C" void hxh_run_timings(const hxh_run* p, double out[5]) { memcpy(out, reinterpret_cast<const Run*>(p)->t, sizeof(double) * 5); }
 extern "C" uint32_t hxh_run_n_edges(const hxh_run* p) { return (uint32_t)reinterpret_cast<const Run*>(p)->mine.size(); }
 extern "C" uint32_t hxh_run_n_edges_total(const hxh_run* p) { return (uint32_t)reinterpret_cast<const Run*>(p)->work.size(); }
+extern "C" void hxh_run_selected_edges(const hxh_run* p, uint32_t* vertex, uint32_t* key) {
+    const Run* r = reinterpret_cast<const Run*>(p);
+    for (size_t i = 0; i < r->mine.size(); i++) { vertex[i] = r->work[r->mine[i]].first; key[i] = r->work[r->mine[i]].second; }
+}
 extern "C" const hx_chain_out* hxh_run_chain_out(const hxh_run* p) { return &reinterpret_cast<const Run*>(p)->chain; }
 extern "C" const hx_edges_out* hxh_run_edges_out(const hxh_run* p) { return &reinterpret_cast<const Run*>(p)->edges; }
 extern "C" const hx_coords_out* hxh_run_coords_out(const hxh_run* p) { return &reinterpret_cast<const Run*>(p)->coords; }

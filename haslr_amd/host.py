@@ -53,6 +53,7 @@ def lib():
         L.hxh_run_timings.argtypes = [C.c_void_p, C.POINTER(C.c_double * 5)]
         L.hxh_run_n_edges.argtypes = [C.c_void_p]
         L.hxh_run_n_edges.restype = C.c_uint32
+        L.hxh_run_selected_edges.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         for name, ty in (("chain_out", T.ChainOut), ("edges_out", T.EdgesOut), ("coords_out", T.CoordsOut), ("cns_out", T.CnsOut)):
             f = getattr(L, "hxh_run_" + name)
             f.argtypes = [C.c_void_p]
@@ -189,6 +190,13 @@ class Run:
 
     @property
     def n_edges(self): return lib().hxh_run_n_edges(self._h)
+    def selected_edges(self):
+        """[(contig1, rev1, contig2, rev2)] of the edges this run processed, in the order of coords_out() / cns_out() (needs coords())"""
+        n = self.n_edges
+        v, k = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+        lib().hxh_run_selected_edges(self._h, v, k)
+        return [(v[i] >> 1, v[i] & 1, k[i] >> 1, k[i] & 1) for i in range(n)]
+
     def chain_out(self): return T.chain_to_dict(lib().hxh_run_chain_out(self._h).contents)
     def edges_out(self, sides=True): return T.edges_to_dict(lib().hxh_run_edges_out(self._h).contents, sides)
     def coords_out(self): return T.coords_to_dict(lib().hxh_run_coords_out(self._h).contents)

@@ -359,7 +359,7 @@ extern "C" void orc_free_edges(hx_edges_out* o) {
 }
 
 // =====================================================================================================
-// a8: edge coordinates (asm_calc_single_edge_coordinates, Assemble.cpp:157-363)   [PARITY UNPINNED]
+// a8: edge coordinates (asm_calc_single_edge_coordinates, Assemble.cpp:157-363)   [pinned: oracle/_ref/ref_back]
 // =====================================================================================================
 namespace {
 // asm_best_supported_interval_contig1/2 (Assemble.cpp:24-126): sweep over sorted (t_start,i) / (t_end,i);

@@ -7,11 +7,16 @@
  *   orc_chain_reads, orc_edge_support : PINNED against the real reference's own front half
  *       (oracle/_ref/ref_front, built from /root/reference sources) — compact_uniq.txt,
  *       alignments.fixed.paf, edge_supp dumps, on seeded inputs; golden copies in tests/golden/.
- *   orc_edge_coords, orc_poa_batch    : PARITY UNPINNED. Assemble.cpp cannot be built here
- *       (needs spoa.hpp from rvaser/spoa 1.1.3, un-vendored, no network) and the reference has
- *       no tests or golden vectors. orc_edge_coords restates Assemble.cpp:24-363 line by line;
- *       orc_poa_batch restates the published algorithm of rvaser/spoa tag 1.1.3 (graph.cpp,
- *       sisd_alignment_engine.cpp) as called from Assemble.cpp:499-554.
+ *   orc_edge_coords (with the sub-sequence rule and the host pipeline's stitching) : PINNED to the
+ *       compiled Assemble.cpp, GIVEN THE ORACLE'S CONSENSUS STRINGS (oracle/_ref/ref_back: the
+ *       reference's whole program, built against oracle/spoa_shim/spoa.hpp, which only lets it link
+ *       and hands every sequence set to orc_poa_consensus) - asm.final.fa / .ann, log_asmfinal.txt,
+ *       log_coordinate.txt and the sub-sequences of log_consensus.txt on seeded and hand-built
+ *       inputs (tests/backlib.py, tests/backcases.py); stored copies in tests/golden/.
+ *   orc_poa_batch                     : PARITY UNPINNED. spoa.hpp (rvaser/spoa 1.1.3) is un-vendored,
+ *       there is no network and the reference has no tests or golden vectors. It restates the
+ *       published algorithm of rvaser/spoa tag 1.1.3 (graph.cpp, sisd_alignment_engine.cpp) as
+ *       called from Assemble.cpp:499-554. Nothing ref_back returns is evidence about SPOA.
  */
 #ifndef HASLR_ORACLE_H
 #define HASLR_ORACLE_H

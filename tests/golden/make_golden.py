@@ -11,6 +11,15 @@ its outputs are stored as data:
   expected/*.gz          larger dumps (edge_supp; alignments.fixed.paf when small) gzip-compressed; the rest by sha256
 The `committed_inputs` case additionally stores contigs + PAF (+ read lengths) so that the front half can be
 replayed without the generator.
+
+Back half (oracle/_ref/ref_back: the reference's whole program, every consensus string computed by liboracle.so through
+oracle/spoa_shim/spoa.hpp - see tests/backlib.py for what that does and does not pin). Per case, from a `-t 1` run on the same inputs:
+  manifest.json "back"   sha256 of asm.final.fa, asm.final.ann and log_asmfinal.txt, and the census of the branches the run reached
+  expected_back/         asm.final.ann verbatim; the coordinate log and the consensus log in the pipeline's reduced form, gzip-compressed
+`committed_inputs` also gets "back_committed" / expected_back_committed/ from a run on reads of the stored lengths made of 'A' only (what
+the replay without the generator uses: coordinates and stitching depend on the reads' lengths, not on their bases). The hand-built
+`back` family of tests/backcases.py is stored under back_family/ (back_manifest.json: sha256 of its three input files, "back").
+`make_golden.py --back-only` adds the back-half data to the fixtures that are there and leaves everything else as it is.
 """
 import gzip
 import hashlib
@@ -23,6 +32,7 @@ import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 CASES = {
     "pacbio_100k_s12": ["--genome-len", "100000", "--seed", "12", "--variant-per-mb", "40", "--cov", "14"],
     # Nanopore-like with missed-adapter (hairpin) reads; every counter of RICH below must be non-zero for it (checked when the fixture is made)
@@ -80,7 +90,74 @@ def gfa_skeleton(src, dst):
                 o.write(line)
 
 
+def contig_lengths(pre):
+    return [len(line.strip()) for line in open(pre + ".contigs.fa") if not line.startswith(">")]
+
+
+def back_half(pre, out, sub, reads=None):
+    """ref_back on pre.contigs.fa / pre.paf and the reads (pre.reads.fa unless given) -> the manifest entry; files under out/<sub>"""
+    import backlib
+    with tempfile.TemporaryDirectory() as d:
+        run_pre = pre
+        if reads is not None:
+            run_pre = os.path.join(d, "in")
+            for k in (".contigs.fa", ".paf"):
+                os.symlink(pre + k, run_pre + k)
+            shutil.copy(reads, run_pre + ".reads.fa")
+        rd = backlib.run_ref(run_pre, os.path.join(d, "ref"))
+        shutil.rmtree(os.path.join(out, sub), ignore_errors=True)
+        return backlib.golden_back_store(rd, contig_lengths(pre), os.path.join(out, sub))
+
+
+def reads_of_lengths(lengths, path):
+    with open(path, "w") as f:
+        for i, n in enumerate(lengths):
+            f.write(f">{i}\n{'A' * int(n)}\n")
+
+
+def back_half_of_case(name, pre, out, man):
+    man["back"] = back_half(pre, out, "expected_back")
+    if name.startswith("committed_inputs"):
+        with tempfile.TemporaryDirectory() as d:
+            reads_of_lengths([len(line.strip()) for line in open(pre + ".reads.fa") if not line.startswith(">")], os.path.join(d, "a.fa"))
+            man["back_committed"] = back_half(pre, out, "expected_back_committed", os.path.join(d, "a.fa"))
+
+
+def back_family():
+    import backcases
+    out = os.path.join(HERE, "back_family")
+    os.makedirs(out, exist_ok=True)
+    with tempfile.TemporaryDirectory() as d:
+        pre, case = backcases.build(os.path.join(d, "in"))
+        man = {"inputs": {k: sha(pre + k) for k in (".contigs.fa", ".reads.fa", ".paf")}, "back": back_half(pre, out, "expected_back")}
+        want = case.man["back"]["census"]
+        assert all(man["back"]["census"].get(k, 0) == v for k, v in want.items() if not k.startswith("case")), (man["back"]["census"], want)
+    with open(os.path.join(out, "back_manifest.json"), "w") as f:
+        json.dump(man, f, indent=1, sort_keys=True)
+    print("back_family ok")
+
+
+def back_only():
+    sim = os.path.join(ROOT, "tools", "hxsim")
+    for name in sorted(os.listdir(HERE)):
+        mp = os.path.join(HERE, name, "manifest.json")
+        if not os.path.isfile(mp):
+            continue
+        man = json.load(open(mp))
+        with tempfile.TemporaryDirectory() as d:
+            pre = os.path.join(d, "in")
+            subprocess.check_call([sim] + man["hxsim_args"] + ["--out-prefix", pre], stderr=subprocess.DEVNULL)
+            assert {k: sha(pre + k) for k in man["inputs"]} == man["inputs"], f"{name}: tools/hxsim no longer produces the fixture's inputs"
+            back_half_of_case(name, pre, os.path.join(HERE, name), man)
+        with open(mp, "w") as f:
+            json.dump(man, f, indent=1, sort_keys=True)
+        print(name, "back half ok")
+    back_family()
+
+
 def main():
+    if sys.argv[1:] == ["--back-only"]:
+        return back_only()
     sim, ref = os.path.join(ROOT, "tools", "hxsim"), os.path.join(ROOT, "oracle", "_ref", "ref_front")
     if not os.path.exists(ref):
         sys.exit("oracle/_ref/ref_front missing: run `make -C oracle ref` where /root/reference exists")
@@ -117,9 +194,11 @@ def main():
                     for line in fi:
                         if not line.startswith(">"):
                             fo.write(f"{len(line.strip())}\n")
+            back_half_of_case(name, pre, out, man)
             with open(os.path.join(out, "manifest.json"), "w") as f:
                 json.dump(man, f, indent=1, sort_keys=True)
         print(name, "ok")
+    back_family()
 
 
 if __name__ == "__main__":

@@ -99,7 +99,8 @@ def test_nondefault_parameters(sim, ctx, tmp_path):
 
 @pytest.mark.parametrize("case", sorted(d for d in os.listdir(GOLD) if os.path.isfile(os.path.join(GOLD, d, "manifest.json"))))
 def test_golden_fixtures_through_hip(case, sim, ctx, tmp_path):
-    """front-half outputs of the HIP path against the files the compiled reference produced"""
+    """front-half outputs of the HIP path against the files the compiled reference produced; and its back half (edge coordinates,
+    sub-sequences, stitching) against what the reference's whole program wrote with the oracle's consensus strings (tests/backlib.py)"""
     import gzip
     cd = os.path.join(GOLD, case)
     man = json.load(open(os.path.join(cd, "manifest.json")))
@@ -121,6 +122,11 @@ def test_golden_fixtures_through_hip(case, sim, ctx, tmp_path):
             assert open(os.path.join(out, f)).read() == open(os.path.join(exp, f)).read(), f
     assert util.sha256_bytes(util.alignments_paf(ds, run.chain_out()).encode()) == man["outputs"]["alignments.fixed.paf"]
     assert util.edge_supp_text(run.edges_out(sides=False)) == gzip.open(os.path.join(exp, "edge_supp.01.txt.gz"), "rt").read()
+    import backlib
+    run.coords()
+    run.consensus()
+    run.assemble()
+    backlib.golden_back_check(man["back"], os.path.join(cd, "expected_back"), run, out)
 
 
 def test_cli_with_threaded_cleaning_equals_the_reference_fixture(sim, built, tmp_path):

@@ -1,12 +1,19 @@
 """The CPU oracle (and the product's host-side graph cleaning / writers) against golden vectors that were
 produced by the UNMODIFIED reference front half (tests/golden/make_golden.py, oracle/_ref/ref_front).
-This is what pins the oracle for SURVEY.md rows a1-a7 and a10."""
+This is what pins the oracle for SURVEY.md rows a1-a7 and a10.
+
+The back half of the same runs (edge coordinates, sub-sequence rule, stitching: row a8) is checked against what the compiled
+reference's WHOLE program wrote for these inputs with the oracle's consensus strings (oracle/_ref/ref_back, tests/backlib.py):
+asm.final.fa / .ann / log_asmfinal.txt, the normalised coordinate table and the arrays. The hand-built `back` family of
+tests/backcases.py has its stored results under golden/back_family/."""
 import gzip
 import json
 import os
 
 import pytest
 
+import backcases
+import backlib
 import orclib
 import util
 from haslr_amd import host
@@ -21,11 +28,15 @@ def run_oracle(pre_contigs, pre_reads, pre_paf, out):
     run = host.Run(ds, ds.params(), be.table, out)
     run.chain()
     run.graph()
+    run.coords()
+    run.consensus()
+    run.assemble()
     return ds, be, run
 
 
-def check_against(case_dir, ds, run, out):
+def check_against(case_dir, ds, run, out, back="back"):
     man = json.load(open(os.path.join(case_dir, "manifest.json")))
+    backlib.golden_back_check(man[back], os.path.join(case_dir, "expected_" + back), run, out)
     exp = os.path.join(case_dir, "expected")
     # files the pipeline writes itself: compact_uniq.txt, .stat, .log, GFA
     for f in sorted(os.listdir(exp)):
@@ -67,4 +78,23 @@ def test_committed_inputs_match_reference(case, built, tmp_path):
         for i, line in enumerate(open(os.path.join(cd, "inputs", "read_len.txt"))):
             f.write(f">{i}\n{'A' * int(line)}\n")
     ds, be, run = run_oracle(os.path.join(cd, "inputs", "in.contigs.fa.gz"), str(reads), os.path.join(cd, "inputs", "in.paf.gz"), str(tmp_path / "o"))
-    check_against(cd, ds, run, str(tmp_path / "o"))
+    check_against(cd, ds, run, str(tmp_path / "o"), "back_committed")   # the reference's back half on the same stand-in reads
+
+
+def test_back_family_matches_reference(built, tmp_path):
+    """the hand-built back-half cases (tests/backcases.py) through the oracle, against the stored results of the compiled reference"""
+    cd = os.path.join(GOLD, "back_family")
+    man = json.load(open(os.path.join(cd, "back_manifest.json")))
+    pre, case = backcases.build(str(tmp_path / "in"))
+    for k, h in man["inputs"].items():
+        if util.sha256_file(pre + k) != h:
+            pytest.skip("tests/backcases.py produced different bytes than when the fixture was made")
+    ds = host.Dataset(pre + ".contigs.fa", pre + ".reads.fa", pre + ".paf")
+    be = orclib.OracleBackend(ds, 2)
+    run = host.Run(ds, ds.params(), be.table, str(tmp_path / "o"))
+    run.all()
+    backlib.golden_back_check(man["back"], os.path.join(cd, "expected_back"), run, str(tmp_path / "o"))
+    for k, v in case.man["back"]["census"].items():
+        if not k.startswith("case"):
+            assert man["back"]["census"].get(k, 0) == v, f"{k}: the stored reference run shows {man['back']['census'].get(k, 0)}, planted {v}"
+    run.close(); be.close(); ds.close()
