@@ -10,6 +10,8 @@
 // gaps above 2047 columns - for the few costliest edges of a small call WIDE members: 1024 lanes of which the first 256 run the DP, all of
 // them the graph phases, one spare wave relays the carries arriving through HBM; sequences of an edge are aligned one after the other,
 // edges run concurrently (persistent workgroups pulling edges off a counter when a launch class has more edges than workspace slots).
+// poa_edge below is the loop over an edge's sequences and DP attempts; the graph and the reference's order are in poa_graph.inl, the DP in poa_dp.inl, what follows
+// an alignment in poa_update.inl; poa_edge.inl names the state that crosses the phases (enum EdgeState, ClusterWord, WalkWord) and holds the members' handshake.
 //   * sequence k is decoded from the 2-bit packed read arena into a byte row
 //   * DP (dp_rows): rows = graph nodes in topological order, columns = sequence positions, CM contiguous columns per lane kept in
 //     registers. Cells are keys (64 x DE-RAMPED score, H - gap x column, + 6 tie-break bits), so one max() per decision reproduces the
@@ -33,7 +35,30 @@ namespace {
 
 #include "poa_graph.inl"    // the graph of an edge, the reference's topological order, heaviest bundle
 #include "poa_dp.inl"       // scans, stores, the wave pipeline's mailboxes, the row loop
+#include "poa_edge.inl"     // names of the edge's state, the handshake words and the walk's words; the steps of the handshake, the edge's views
 #include "poa_update.inl"   // CSR rebuild, graph update, order update
+
+// poa_edge's timers: lane 0 adds the cycles since the previous PHASE to the edge's word k (ph, tc: poa_edge's)
+#define PHASE(k) do { if (tid == 0) { long long _n = clock64(); ph[k] += (unsigned long long)(_n - tc); tc = _n; } } while (0)
+#if POA_PHASE_FLAVOUR == POA_PHASE_GUSTAGES   // development: where the graph update (PW_GU_STAGE0 ...) and the CSR rebuild (PW_GU_CSR: its first half) spend their cycles - printed by HX_PROF2 (its labels are the DP's)
+#define GU_T0() do { __syncthreads(); if (tid == 0) tg = clock64(); } while (0)
+#define GU_T(k) do { __syncthreads(); if (tid == 0) { long long _n = clock64(); ph[k] += (unsigned long long)(_n - tg); tg = _n; } } while (0)
+#else
+#define GU_T0() do { } while (0)
+#define GU_T(k) do { } while (0)
+#endif
+#if POA_PHASE_FLAVOUR == POA_PHASE_DPSUB
+#define SUBT(k) do { if (tid == 0) { long long _n = clock64(); ph[k] += (unsigned long long)(_n - tc2); tc2 = _n; } } while (0)
+#define SUBT0() do { if (tid == 0) tc2 = clock64(); } while (0)
+#else
+#define SUBT(k) do { } while (0)
+#define SUBT0() do { } while (0)
+#endif
+// one DP of poa_edge over its own columns (every name is poa_edge's)
+#define HX_DP_DISPATCH(Lq, Vq, nsq, Tq) do { \
+        if (((Lq) + 1 + GM * NP * DL - 1) / (GM * NP * DL) <= (uint32_t)CM) {    /* the host puts an edge into a launch whose columns per lane hold its longest sequence */ \
+            dp_rows<CM, DIR, PRUNE, MAXNT == 64>(g, H, Dm, Dw, W, WH, seq, Lq, Vq, ring, R, ring_w, match, mismatch, gap, wmail.box, wmail.consumed, sink_row, sink_score, SINK_LDS, nsq, cl, ph + PW_BUILD0, Tq, (prune_pct >> 16) & 1u, ph + PW_PRUNE0, ED.hrows); \
+        } else sOk = ES_INTERNAL; } while (0)
 
 // One kernel per (largest workgroup, columns per lane, traceback flavour): the register budget of a launch is that of ITS row loop, so the
 // many short gaps (one wavefront, 4-8 columns per lane) run with a fraction of the registers - and several times the waves per SIMD - of
@@ -47,40 +72,18 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
     __shared__ unsigned long long ph[POA_PHASE_WORDS];   // the edge's diagnostic words (enum PoaPhaseWord, poa_phase_words.h), written by lane 0
     __shared__ long long tc;
     if (threadIdx.x == 0) { for (int k = 0; k < POA_PHASE_WORDS; k++) ph[k] = 0; tc = clock64(); ph[PW_BEGIN] = pw_pack(pw_lo(wall_clock64(), PW_SPLIT_CLOCK), (unsigned long long)((__builtin_amdgcn_s_getreg(63492) & 0x7fffu) | ((__builtin_amdgcn_s_getreg(63508) & 15u) << 15)), PW_SPLIT_CLOCK); }   // (begin; where: HW_ID bits 0-14 = wave, SIMD, pipe, CU, SH, SE and the XCC)
-#define PHASE(k) do { if (tid == 0) { long long _n = clock64(); ph[k] += (unsigned long long)(_n - tc); tc = _n; } } while (0)
-#if POA_PHASE_FLAVOUR == POA_PHASE_GUSTAGES   // development: where the graph update (PW_GU_STAGE0 ...) and the CSR rebuild (PW_GU_CSR: its first half) spend their cycles - printed by HX_PROF2 (its labels are the DP's)
-#define GU_T0() do { __syncthreads(); if (tid == 0) tg = clock64(); } while (0)
-#define GU_T(k) do { __syncthreads(); if (tid == 0) { long long _n = clock64(); ph[k] += (unsigned long long)(_n - tg); tg = _n; } } while (0)
+#if POA_PHASE_FLAVOUR == POA_PHASE_GUSTAGES
     long long tg = 0;
-#else
-#define GU_T0() do { } while (0)
-#define GU_T(k) do { } while (0)
 #endif
 #if POA_PHASE_FLAVOUR == POA_PHASE_DPSUB
     __shared__ long long tc2;
-#define SUBT(k) do { if (tid == 0) { long long _n = clock64(); ph[k] += (unsigned long long)(_n - tc2); tc2 = _n; } } while (0)
-#define SUBT0() do { if (tid == 0) tc2 = clock64(); } while (0)
-#else
-#define SUBT(k) do { } while (0)
-#define SUBT0() do { } while (0)
 #endif
     const PoaEdge ED = edges[eidx];
     const uint32_t tid = threadIdx.x, NT = blockDim.x;
     const uint32_t DL = dp_lanes ? dp_lanes : NT;   // lanes in the DP: the whole workgroup, or the first waves of a "wide" cluster member (one wave per SIMD in the DP, sixteen in the graph phases)
     extern __shared__ int32_t ring[];   // (no alignment attribute: the packed rows' table reads are split by the compiler; with aligned(16) the int32 row loop of this build came out 10 % slower - same instructions, another layout)
     G g;
-    {
-        const uint64_t no = SL.node_off, eo = SL.edge_off;
-        g.code = P.code + no; g.n_aligned = P.n_aligned + no; g.aligned = P.aligned + 3 * no;
-        g.in_head = P.in_head + no; g.in_tail = P.in_tail + no; g.out_head = P.out_head + no; g.out_tail = P.out_tail + no;
-        g.rank2node = P.rank2node + no; g.node2rank = P.node2rank + no; g.mark = P.mark + no; g.check = P.check + no;
-        g.stack = P.stack + SL.stack_off; g.score = P.score + no; g.pred = P.pred + no;
-        g.row_code = P.row_code + no; g.row_sink = P.row_sink + no; g.row_pred_off = P.row_pred_off + no; g.pred_rank = P.pred_rank + eo; g.pred_w = P.pred_w + eo;
-        g.row_meta = P.row_meta + no; g.row_pred0 = P.row_pred0 + no; g.row_pred1 = P.row_pred1 + no; g.nrec = P.nrec + no; g.nrec2 = P.nrec2 + no; g.row_al = P.row_al + no; g.wslot = P.wslot + no;
-        g.e_from = P.e_from + eo; g.e_to = P.e_to + eo; g.e_next_in = P.e_next_in + eo; g.e_next_out = P.e_next_out + eo; g.e_w = P.e_w + eo;
-        g.aln_node = P.aln_node + SL.aln_off; g.aln_pos = P.aln_pos + SL.aln_off;
-        g.vcap = ED.vcap; g.ecap = ED.ecap;
-    }
+    bind_graph(g, P, SL, ED);
     int32_t* H = P.H + SL.h_off;
     uint8_t* Dm = DIR ? P.dir + SL.d_off : nullptr;   // direction nibbles: (vcap + 1) rows of W / 2 bytes; with them H holds only ED.hrows far-read rows
     uint8_t* Dw = DIR ? P.dirw + SL.w_off : nullptr;  // direction bytes of the rows with more than 4 predecessors: ED.wrows rows of W
@@ -112,30 +115,25 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
     // 256 entries left room for fourteen; round 5)
     constexpr uint32_t SINK_LDS = MAXNT <= 256 ? 128 : MAXNT < 1024 ? 256 : SINK_CAP;
     __shared__ WaveMailT<MAXNT / 64> wmail;
-    __shared__ uint32_t lds_u[16];
-    __shared__ uint32_t sV, sE, sNaln, sOk, sNsink, sNcand, sBestKey, sWalkN, sWalkI, sWalkJ;   // (sWalk*: entries of the traceback walk still in (rank, column) form, and where the walk stopped)
+    __shared__ uint32_t lds_u[16];   // scratch of the graph phases' scans; during the traceback the walk's result and the helper's mailbox (enum WalkWord)
+    __shared__ uint32_t sV, sE, sNaln, sOk, sNsink, sNcand, sBestKey, sWalkN, sWalkI, sWalkJ;   // (sOk: enum EdgeState; sWalk*: entries of the traceback walk still in (rank, column) form, and where the walk stopped)
     __shared__ int sBestI;
     __shared__ uint32_t sink_row[SINK_LDS];
     __shared__ int sink_score[SINK_LDS];
     __shared__ uint32_t sCtl;
     __shared__ unsigned long long sCells;   // DP cells of this edge (reported only when the edge completes: retried edges count once)
     __shared__ int sPrevScore, sNewT; __shared__ uint32_t sPrevLen, sRetry;   // PRUNE: score and length of the edge's previous alignment (the source of the threshold), the verdict on an attempt
-    if (tid == 0) { sV = 0; sE = 0; sOk = R != 0xffffffffu ? 1 : 2; sCells = 0; sPrevScore = 0; sPrevLen = 0; sRetry = 0; sNewT = PRUNE_OFF; }   // (the host gives every launch LDS for at least the latest row)
+    if (tid == 0) { sV = 0; sE = 0; sOk = R != 0xffffffffu ? ES_OK : ES_INTERNAL; sCells = 0; sPrevScore = 0; sPrevLen = 0; sRetry = 0; sNewT = PRUNE_OFF; }   // (the host gives every launch LDS for at least the latest row)
     if constexpr (MAXNT > 64) {
         for (uint32_t q = tid; q < (MAXNT / 64 - 1) * WAVE_MBOX; q += NT) wmail.box[q] = 0ull;   // tag 0 = nothing published
         if (tid < MAXNT / 64) wmail.consumed[tid] = 0u;
     }
     __syncthreads();
-    uint32_t* csy = P.csync + (uint64_t)eidx * 8;                 // go, done, V, L, error
+    uint32_t* csy = P.csync + (uint64_t)eidx * CW_STRIDE;         // the members' handshake (enum ClusterWord)
     int32_t* sinkbuf = P.sinkbuf + (uint64_t)eidx * (1 + 2 * SINK_CAP);
     DpCl cl;
     cl.mem = mem; cl.members = GM; cl.stride = ED.vcap + 1; cl.tag0 = 0;
-    cl.mbox = P.mbox + (NP > 1 ? SL.mbox_off : ED.cl_off); cl.err = csy + 4; cl.poll_limit = poll_limit; cl.lanes = DL;
-    constexpr uint32_t CL_ABORT = 0xffffffffu;
-#define HX_DP_DISPATCH(Lq, Vq, nsq, Tq) do { \
-        if (((Lq) + 1 + GM * NP * DL - 1) / (GM * NP * DL) <= (uint32_t)CM) {    /* the host puts an edge into a launch whose columns per lane hold its longest sequence */ \
-            dp_rows<CM, DIR, PRUNE, MAXNT == 64>(g, H, Dm, Dw, W, WH, seq, Lq, Vq, ring, R, ring_w, match, mismatch, gap, wmail.box, wmail.consumed, sink_row, sink_score, SINK_LDS, nsq, cl, ph + PW_BUILD0, Tq, (prune_pct >> 16) & 1u, ph + PW_PRUNE0, ED.hrows); \
-        } else sOk = 2; } while (0)
+    cl.mbox = P.mbox + (NP > 1 ? SL.mbox_off : ED.cl_off); cl.err = csy + CW_ERR; cl.poll_limit = poll_limit; cl.lanes = DL;
     // The reference's topological order (spoa's DFS, inherently serial) is needed in two places only: to break ties between equally scored
     // end nodes of an alignment, and for the heaviest-bundle traversal of the finished graph. The DP itself runs on a cheaper order that
     // is maintained incrementally (see "order update" below): row values do not depend on which valid topological order is used.
@@ -179,13 +177,14 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
         __syncthreads();
     };
 
-    // Cluster protocol (round 6: DP ATTEMPTS, not sequences). Member 0 publishes every DP it wants - a new sequence, or the same one again under another threshold
-    // (PRUNE) - as {V, L, threshold} and a rising attempt number in csy[0]; the other members run one DP per attempt, whatever it is, add themselves to csy[1], and wait
-    // for the next number or for the release (CL_ABORT, written by member 0 when it leaves the loop for whatever reason). They do not count sequences.
+    // Cluster protocol (round 6: DP ATTEMPTS, not sequences; enum ClusterWord and the cluster_* steps in poa_edge.inl). Member 0 publishes every DP it wants - a new
+    // sequence, or the same one again under another threshold (PRUNE) - as {V, L, threshold} and a rising attempt number in CW_GO; the other members run one DP per attempt,
+    // whatever it is, add themselves to CW_DONE, and wait for the next number or for the release (CL_ABORT, written by member 0 when it leaves the loop for whatever reason).
+    // They do not count sequences.
     uint32_t att = 0;   // DP attempts of this edge so far (uniform; member 0 publishes att, the others wait for att + 1)
     for (uint32_t k = ED.seq_begin; mem > 0 || k < ED.seq_end; k += (mem == 0 ? 1u : 0u)) {
         uint32_t L, V;
-        if (mem == 0 && sOk != 1) break;
+        if (mem == 0 && sOk != ES_OK) break;
         if (mem == 0) {
             const PoaSeq q = seqs[k];
             L = q.len;
@@ -207,10 +206,10 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
             // ---- other member of a cluster: only the DP, over its own columns; everything else happens in member 0
             if (tid == 0) {
                 uint32_t v = 0;
-                for (uint32_t spin = 0;; spin++) {
-                    v = ld_dev(csy + 0);
+                for (uint32_t spin = 0;; spin++) {   // (the members' other wait is cluster_wait; this one stays here: as a function its exit test compiles to other code)
+                    v = ld_dev(csy + CW_GO);
                     if (v == CL_ABORT || v >= att + 1) break;
-                    if (spin > poll_limit) { st_dev(csy + 4, 1u); v = CL_ABORT; break; }
+                    if (spin > poll_limit) { st_dev(csy + CW_ERR, 1u); v = CL_ABORT; break; }
                     __builtin_amdgcn_s_sleep(32);
                 }
                 sCtl = v;
@@ -218,7 +217,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
             __syncthreads();
             if (sCtl == CL_ABORT) break;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // graph rows, sequence and counts written by member 0
-            V = ld_dev(csy + 2); L = ld_dev(csy + 3);
+            V = ld_dev(csy + CW_V); L = ld_dev(csy + CW_L);
         }
         // =================================================== DP over (rank, column): every member, its own columns
         if (mem == 0) SUBT(PW_P2_PUBLISH);   // publish
@@ -237,11 +236,8 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
     redo_dp:
         att++;
         if (GM > 1) {
-            if (mem == 0) {   // publish this attempt to the other members: graph rows (CSR), decoded sequence, V, L, the threshold
-                __threadfence();
-                __syncthreads();
-                if (tid == 0) { st_dev(csy + 2, V); st_dev(csy + 3, L); st_dev(csy + 5, (uint32_t)thrT); __threadfence(); st_dev(csy + 0, att); }
-            } else if constexpr (PRUNE) thrT = (int)ld_dev(csy + 5);
+            if (mem == 0) cluster_publish(csy, V, L, thrT, att);
+            else if constexpr (PRUNE) thrT = (int)ld_dev(csy + CW_THRESHOLD);
         }
         if (V > 0) {
             uint32_t ns = 0xffffffffu;
@@ -265,7 +261,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
             if (ns != 0xffffffffu) sNsink = ns;   // written by the lane that owns column L
             cl.tag0 += V;
         }
-        if (mem > 0) {
+        if (mem > 0) {   // another member reports its DP done
             __syncthreads();
             if (V > 0 && L / (DL * (uint32_t)CM) == mem) {   // this member owns the last column: hand the sink rows to member 0
                 const uint32_t nsk = min(sNsink, SINK_LDS);
@@ -274,52 +270,41 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
             }
             __threadfence();                                       // direction bytes, sink rows: visible before "done"
             __syncthreads();
-            if (tid == 0) __hip_atomic_fetch_add(csy + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) __hip_atomic_fetch_add(csy + CW_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             continue;
         }
         SUBT(PW_P2_OWN);   // own columns
         if (V > 0) {
-            {
-                if (GM > 1) {   // wait for the other members' columns (direction bytes, sinks)
-                    __syncthreads();
-                    if (tid == 0) {
-                        const uint32_t need = (GM - 1) * att;
-                        for (uint32_t spin = 0;; spin++) {
-                            if (ld_dev(csy + 1) >= need) break;
-                            if (spin > poll_limit) { st_dev(csy + 4, 1u); break; }
-                            __builtin_amdgcn_s_sleep(32);
-                        }
-                    }
-                    __syncthreads();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    if (L / (DL * (uint32_t)CM) != 0) {   // the last column lives in another member: fetch its sink rows
-                        const uint32_t nsk_all = (uint32_t)sinkbuf[0], nsk = min(nsk_all, SINK_LDS);
-                        for (uint32_t q = tid; q < nsk; q += NT) { sink_row[q] = (uint32_t)sinkbuf[1 + q]; sink_score[q] = sinkbuf[1 + SINK_CAP + q]; }
-                        if (tid == 0) sNsink = nsk_all;
-                    }
+            if (GM > 1) {   // wait for the other members' columns (direction bytes, sinks)
+                cluster_wait_members(csy, GM, att, poll_limit);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                if (L / (DL * (uint32_t)CM) != 0) {   // the last column lives in another member: fetch its sink rows
+                    const uint32_t nsk_all = (uint32_t)sinkbuf[0], nsk = min(nsk_all, SINK_LDS);
+                    for (uint32_t q = tid; q < nsk; q += NT) { sink_row[q] = (uint32_t)sinkbuf[1 + q]; sink_score[q] = sinkbuf[1 + SINK_CAP + q]; }
+                    if (tid == 0) sNsink = nsk_all;
                 }
             }
             __syncthreads();
-            if (tid == 0 && ld_dev(csy + 4) && sOk == 1) sOk = ld_dev(csy + 4) == 2u ? 2 : 8;   // a wave gave up waiting for a carry (never seen within one workgroup; between workgroups
+            if (tid == 0 && ld_dev(csy + CW_ERR) && sOk == ES_OK) sOk = ld_dev(csy + CW_ERR) == 2u ? ES_INTERNAL : ES_STALLED;   // a wave gave up waiting for a carry (never seen within one workgroup; between workgroups
                                                                     // when the members of an edge are not resident together): the host redoes the edge unshared
             __syncthreads();
-            if (sOk != 1) break;                                    // (the matrix of this sequence is not to be walked)
+            if (sOk != ES_OK) break;                                    // (the matrix of this sequence is not to be walked)
             SUBT(PW_P2_WAIT);   // wait for the other members, sinks
             // ---- end node of the global alignment: the best-scoring sink; ties go to the smallest rank in the REFERENCE's order
             if (tid == 0) {
-                if (sNsink > SINK_LDS) sOk = 6;   // more sink rows than the launch keeps: the host redoes the edge in a launch with the full list
+                if (sNsink > SINK_LDS) sOk = ES_SINKS;   // more sink rows than the launch keeps: the host redoes the edge in a launch with the full list
                 int best = INT32_MIN + 1024; uint32_t ncand = 0, first = 0;
                 const uint32_t nsk = min(sNsink, SINK_LDS);
                 for (uint32_t q = 0; q < nsk; q++) if (sink_score[q] > best) best = sink_score[q];
                 for (uint32_t q = 0; q < nsk; q++) if (sink_score[q] == best) { if (!ncand) first = q; sink_row[ncand++] = sink_row[q]; }   // compact candidates to the front
                 (void)first;
                 if constexpr (PRUNE) {   // did the alignment reach its threshold? (else: again, with the score it did reach - a real path's - or, no sink computed at all, unpruned)
-                    sRetry = thrT > PRUNE_OFF && sOk == 1 && best < thrT;
+                    sRetry = thrT > PRUNE_OFF && sOk == ES_OK && best < thrT;
                     if (sRetry) { sNewT = nsk ? max(best, PRUNE_OFF) : PRUNE_OFF; ph[PW_PRUNE_REPEATED]++; }
                     else { sPrevScore = best; sPrevLen = L; ph[PW_PRUNE_THRESHOLDS] += thrT > PRUNE_OFF; }
                 }
                 sNcand = ncand; sBestI = ncand ? (int)sink_row[0] : -1; sBestKey = 0xffffffffu;
-                lds_u[8] = 0; lds_u[9] = 0; lds_u[10] = 0;   // (traceback helper: nowhere yet, not done)
+                lds_u[WALK_AT_I] = 0; lds_u[WALK_AT_J] = 0; lds_u[WALK_DONE] = 0;   // (traceback helper: nowhere yet, not done)
                 // Ties (a quarter of all alignments have one): the winner is the candidate the REFERENCE's topological order lists first. That order is a DFS
                 // over in-edges and aligned nodes with the roots taken in node-id order (toposort above) - the whole graph, serial, 1 500 cycles per node
                 // when it has to run (36 M cycles per tie on a 20 000-node graph: 22 ties were HALF the chain of the longest edge of a 3 316-edge call).
@@ -400,7 +385,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                     goto redo_dp;
                 }
             }
-            if (sNcand > 1 && sOk == 1) {
+            if (sNcand > 1 && sOk == ES_OK) {
                 if (tid == 0) ph[PW_P2_TIES] += 1;
                 exact_order(V, tmp_u32);
                 const uint32_t nc = sNcand;
@@ -434,7 +419,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                         // (every step leaves a row or a column behind: a walk of more entries than rows + columns is walking a matrix that is not one - a bug somewhere
                         // else. It ends here, the edge comes back with an internal error and the call fails loudly, instead of a kernel that never ends; the entry
                         // arrays have 64 entries of slack for the tile that runs over: need_of)
-                        if (__builtin_expect(na > V + L + 2u, 0)) { if (ln == 0) sOk = 2; break; }
+                        if (__builtin_expect(na > V + L + 2u, 0)) { if (ln == 0) sOk = ES_INTERNAL; break; }
                         if (i == 0) {   // only horizontal moves are left in the virtual row: written in their final form
                             if (na & 63u) { const uint32_t base = na & ~63u; if (ln < na - base) { g.aln_node[base + ln] = pn; g.aln_pos[base + ln] = pp; } }
                             tail = true;
@@ -448,7 +433,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                         // cycles with the helper wave ahead of the walk, 30 % of a walk's time - and graphs have ~2 ranks per column: the walk left a tile of 16
                         // columns through its columns after 16.5 steps on average, whatever its rows; 64 x 32 is the shape it leaves through both at once.)
                         const uint32_t ti = i, ct = j | 1u;
-                        if (NT > 64 && ln == 0) { st_wg(&lds_u[8], ti); st_wg(&lds_u[9], ct); }   // (where the walk is: the helper wave fetches ahead of it)
+                        if (NT > 64 && ln == 0) { st_wg(&lds_u[WALK_AT_I], ti); st_wg(&lds_u[WALK_AT_J], ct); }   // (where the walk is: the helper wave fetches ahead of it)
                         const int32_t bs = ((int32_t)ct - 31) >> 1;   // first byte of the tile in its rows (ct < 31: negative - bytes before the row, never looked at)
                         uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0, mt = 0, pv0 = 0, pv1 = 0, qo = 0, qw = 0;
                         if (ti > ln) {
@@ -519,7 +504,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                         if (na & 63u) { const uint32_t base = na & ~63u; if (ln < na - base) { g.aln_node[base + ln] = pn; g.aln_pos[base + ln] = pp; } }
                         nwalk = na; iend = 0; jend = 0;
                     }
-                    if (ln == 0) { sNaln = na; lds_u[0] = nwalk; lds_u[1] = iend; lds_u[2] = jend; st_wg(&lds_u[10], 1u); }
+                    if (ln == 0) { sNaln = na; lds_u[WALK_N] = nwalk; lds_u[WALK_I] = iend; lds_u[WALK_J] = jend; st_wg(&lds_u[WALK_DONE], 1u); }
                 } else if (tid < 128) {
                     // Helper wavefront of the walk (any workgroup with a second wave; it sits on another SIMD): touches what the walk reaches in the
                     // next one to three tiles - the nibble rows around the path's expected column (graphs have ~2 ranks per column), the rows'
@@ -530,8 +515,8 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                     const uint32_t hl = tid - 64u;
                     uint32_t last_i = 0xffffffffu, sink = 0;
                     for (uint32_t spin = 0; spin < (1u << 26); spin++) {
-                        if (ld_wg(&lds_u[10])) break;
-                        const uint32_t pi_ = ld_wg(&lds_u[8]), pc = ld_wg(&lds_u[9]);
+                        if (ld_wg(&lds_u[WALK_DONE])) break;
+                        const uint32_t pi_ = ld_wg(&lds_u[WALK_AT_I]), pc = ld_wg(&lds_u[WALK_AT_J]);
                         if (pi_ == last_i) { __builtin_amdgcn_s_sleep(8); continue; }
                         last_i = pi_;
                         for (uint32_t hk = 0; hk < 2; hk++) {                        // rows pi_ - 64 .. pi_ - 191, 64 at a time
@@ -554,7 +539,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                 __syncthreads();
                 // (the walk's entries - the cell it stood on before every move - become alignment entries in graph_update: "the node of its row unless the move
                 // stayed in the row, its column unless the move stayed in the column" is read off neighbouring entries there, on the way to the bases)
-                if (tid == 0) { sWalkN = lds_u[0]; sWalkI = lds_u[1]; sWalkJ = lds_u[2]; }
+                if (tid == 0) { sWalkN = lds_u[WALK_N]; sWalkI = lds_u[WALK_I]; sWalkJ = lds_u[WALK_J]; }
                 __syncthreads();
             } else if (tid == 0) {
                 sCells += (unsigned long long)V * L;
@@ -590,28 +575,17 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
             }
         } else {
             if (tid == 0) { sNaln = 0; sWalkN = 0; }
-            if (GM > 1) {   // nothing to align against yet: the other members only count the sequence (and must have read V = 0 before it changes)
-                __syncthreads();
-                if (tid == 0) {
-                    const uint32_t need = (GM - 1) * att;
-                    for (uint32_t spin = 0;; spin++) {
-                        if (ld_dev(csy + 1) >= need) break;
-                        if (spin > poll_limit) { st_dev(csy + 4, 1u); break; }
-                        __builtin_amdgcn_s_sleep(32);
-                    }
-                }
-                __syncthreads();
-            }
+            if (GM > 1) cluster_wait_members(csy, GM, att, poll_limit);   // nothing to align against yet: the other members only count the sequence (and must have read V = 0 before it changes)
         }
         __syncthreads();
-        if (sOk != 1) break;                                        // (a walk that did not end: see there)
+        if (sOk != ES_OK) break;                                        // (a walk that did not end: see there)
         PHASE(PW_TRACEBACK);
         // =================================================== graph update + order update (all lanes): graph_update / order_update above
         const uint32_t V_old = sV;
         graph_update(g, seq, L, sNaln, sWalkN, sWalkI, sWalkJ, lds_u, &sV, &sE, &sNcand, &sOk);
         PHASE(PW_GRAPH);
         __syncthreads();
-        if (sOk != 1) break;
+        if (sOk != ES_OK) break;
         order_update(g, V_old, sV, L, lds_u);
         PHASE(PW_ORDER);
         __syncthreads();
@@ -621,10 +595,10 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
         PHASE(PW_CSR);
     }
     if (mem > 0) return;
-    if (GM > 1 && tid == 0) st_dev(csy + 0, CL_ABORT);   // release the other members (they wait for the next attempt: done or not, there is none)
+    if (GM > 1 && tid == 0) st_dev(csy + CW_GO, CL_ABORT);   // release the other members (they wait for the next attempt: done or not, there is none)
     long long t_cns = 0;
     if (tid == 0) t_cns = clock64();
-    if (sOk == 1 && sV) {
+    if (sOk == ES_OK && sV) {
         // heaviest bundle: first on the maintained order (exact whenever the heaviest node is unique and a sink); else on the reference's
         // topological order of the finished graph
         if (tid < 64) { const uint32_t cl_ = consensus_fast_wave(g, sV, cns + ED.cns_off); if (tid == 0) sCtl = cl_; }
@@ -644,13 +618,13 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
         }
     }
     if (tid == 0) {
-        if (sOk == 2) { status[eidx] = HXE_SPOS_RANGE << 8; cns_len[eidx] = 0; }   // internal: kernel variant cannot hold this many columns per lane
-        else if (!sOk) { status[eidx] = HXE_POA_OVERFLOW; cns_len[eidx] = 0; }
-        else if (sOk == 4) { status[eidx] = HXE_POA_NODIR; cns_len[eidx] = 0; }
-        else if (sOk == 5) { status[eidx] = HXE_POA_FARROWS; cns_len[eidx] = 0; }
-        else if (sOk == 6) { status[eidx] = HXE_POA_SINKS; cns_len[eidx] = 0; }
-        else if (sOk == 7) { status[eidx] = HXE_POA_WIDEROWS; cns_len[eidx] = 0; }
-        else if (sOk == 8) { status[eidx] = HXE_POA_STALLED; cns_len[eidx] = 0; }
+        if (sOk == ES_INTERNAL) { status[eidx] = HXE_SPOS_RANGE << 8; cns_len[eidx] = 0; }   // internal: kernel variant cannot hold this many columns per lane
+        else if (sOk == ES_OVERFLOW) { status[eidx] = HXE_POA_OVERFLOW; cns_len[eidx] = 0; }
+        else if (sOk == ES_NODIR) { status[eidx] = HXE_POA_NODIR; cns_len[eidx] = 0; }
+        else if (sOk == ES_FARROWS) { status[eidx] = HXE_POA_FARROWS; cns_len[eidx] = 0; }
+        else if (sOk == ES_SINKS) { status[eidx] = HXE_POA_SINKS; cns_len[eidx] = 0; }
+        else if (sOk == ES_WIDEROWS) { status[eidx] = HXE_POA_WIDEROWS; cns_len[eidx] = 0; }
+        else if (sOk == ES_STALLED) { status[eidx] = HXE_POA_STALLED; cns_len[eidx] = 0; }
         else {
             status[eidx] = 0; cns_len[eidx] = !sV ? 0 : sCtl; atomicAdd(cells, sCells);
 #if POA_PHASE_FLAVOUR == POA_PHASE_ROWSTATS
@@ -667,6 +641,12 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
 #endif
     }
 }
+#undef HX_DP_DISPATCH
+#undef SUBT0
+#undef SUBT
+#undef GU_T
+#undef GU_T0
+#undef PHASE
 
 // The launch. An edge that is shared by several workgroups gets one workgroup per member and a workspace slot of its own (`order` entry =
 // edge | member << 24, the slot is the edge's PoaEdge::slot). Everything else runs PERSISTENT: the grid is a number of workspace slots, each

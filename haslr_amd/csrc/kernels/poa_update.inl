@@ -115,7 +115,7 @@ __device__ __forceinline__ void csr_rebuild(const G& g_in, const uint32_t V2, co
                     if (np[u] >= 1) { g.pred_rank[off] = pf0[u]; g.pred_w[off] = w0[u]; }
                     if (np[u] >= 2) { g.pred_rank[off + 1] = pf1[u]; g.pred_w[off + 1] = w1[u]; }
                     g.row_meta[r] = cd[u] | (sink << 2) | (kept[u] << 4) | (np[u] > 4u ? 32u : 0u) | ((kept[u] && R ? (kx & (R - 1)) : 15u) << META_SLOT) | (np[u] << META_NP);   // slot 15: no non-adjacent reader (or no ring at all) - the row is not written to the ring
-                    if (DIR && np[u] > max_indeg) *sOk = 4;         // the direction bytes hold a 4-bit predecessor slot (max_indeg <= 16)
+                    if (DIR && np[u] > max_indeg) *sOk = ES_NODIR;         // the direction bytes hold a 4-bit predecessor slot (max_indeg <= 16)
                     g.row_pred0[r] = pf0[u]; g.row_pred1[r] = pf1[u];
                     st_multi += np[u] >= 2; st_wide += np[u] > 4; st_fifth += np[u] > 4 ? np[u] - 4 : 0;
                 }
@@ -222,8 +222,8 @@ __device__ __forceinline__ void csr_rebuild(const G& g_in, const uint32_t V2, co
                     far_base += tf; wide_base += tw;
                 }
             }
-            if (tid == 0 && far_base > hrows && *sOk == 1) *sOk = 5;    // more far rows than the estimate: the host retries with a row per node
-            if (tid == 0 && wide_base > wrows && *sOk == 1) *sOk = 7;   // more wide rows than the estimate: the host retries with more
+            if (tid == 0 && far_base > hrows && *sOk == ES_OK) *sOk = ES_FARROWS;    // more far rows than the estimate: the host retries with a row per node
+            if (tid == 0 && wide_base > wrows && *sOk == ES_OK) *sOk = ES_WIDEROWS;   // more wide rows than the estimate: the host retries with more
             CSR_T(6, wide_base);
         }
 #ifdef HX_CSR_PROF
@@ -259,7 +259,7 @@ __device__ __forceinline__ void graph_update(const G& g_in, const uint8_t* seq_,
     const uint32_t V0 = *sV_, E0 = *sE_;
     int32_t* anode = reinterpret_cast<int32_t*>(g.stack);   // node aligned to base p, -1 = none (horizontal move)
     const bool room = E0 + L + 1 <= g.ecap && L <= g.vcap;   // edges: worst case (every base a new edge); per-base scratch lives in node pools; nodes are counted exactly below
-    if (!room) { if (tid == 0) (*sOk_) = 0; }
+    if (!room) { if (tid == 0) (*sOk_) = ES_OVERFLOW; }
     else {
         if (tid == 0) (*sNcand_) = 0;
         for (uint32_t p = tid; p < L; p += NT) anode[p] = -2;
@@ -298,7 +298,7 @@ __device__ __forceinline__ void graph_update(const G& g_in, const uint8_t* seq_,
                     const int32_t r = g.aln_node[k], c = g.aln_pos[k], r2 = k + 1 < nw ? g.aln_node[k + 1] : (int32_t)w_ie, c2 = k + 1 < nw ? g.aln_pos[k + 1] : (int32_t)w_je;
                     g.aln_node[k] = r == r2 ? -1 : (int32_t)g.rank2node[r - 1]; g.aln_pos[k] = c == c2 ? -1 : c - 1;
                 }
-                uint32_t V2 = V0, E2 = E0; if (!add_alignment(g, V2, E2, na, seq, L, path, colref)) (*sOk_) = 0; else { (*sV_) = V2; (*sE_) = E2; }
+                uint32_t V2 = V0, E2 = E0; if (!add_alignment(g, V2, E2, na, seq, L, path, colref)) (*sOk_) = ES_OVERFLOW; else { (*sV_) = V2; (*sE_) = E2; }
             }
         } else {
             // (round 5: lane = base. Bases are taken NT at a time - coalesced accesses by position, one scan per block with a running base for the ids -
@@ -336,7 +336,7 @@ __device__ __forceinline__ void graph_update(const G& g_in, const uint8_t* seq_,
                 nbase += tot;
             }
             const uint32_t newV = nbase;
-            if (ovf) { if (tid == 0) (*sOk_) = 0; }
+            if (ovf) { if (tid == 0) (*sOk_) = ES_OVERFLOW; }
             else {
             __syncthreads();
             uint32_t ebase = 0;

@@ -197,6 +197,21 @@ def other_letters(rnd, n_sets=24):
     return sets
 
 
+WALK_EDGE_LENGTHS = (63, 64, 65, 127, 128, 129)
+
+
+def walk_edges(rnd):
+    """second members whose traceback meets the walk's edges, around the 64 entries the tile walk (kernels/poa_traceback.inl) keeps in registers
+    before it stores them: per template t of n bases (an A, random bases, an A or a T: a "CG" before or behind it matches nothing at its ends)
+    [t, t] a walk of exactly n entries to the origin; [t, "CG" + t] n entries, then two columns left in the virtual row; [t, t[2:]] a walk that
+    ends through two vertical moves into a source; [t, t + "CG"] a walk that starts with horizontal moves"""
+    sets = []
+    for n in WALK_EDGE_LENGTHS:
+        t = "A" + _rand(rnd, n - 2) + rnd.choice("AT")
+        sets += [[t, t], [t, "CG" + t], [t, t[2:]], [t, t + "CG"]]
+    return sets
+
+
 def as_read(seq):
     """the sequence as every entry point reads it: A, C, G, T in either case are those letters, every other character is an A (the
     reference's table: Compressed_sequence.cpp:10-19 with "& 3")"""
@@ -209,6 +224,7 @@ def _build():
                                        ("haplotypes", haplotypes), ("fragments", fragments), ("fan_in", fan_in), ("prefix_mismatch", prefix_mismatch),
                                        ("many_members", many_members), ("other_letters", other_letters)]):
         fam[name] = fn(random.Random(7100 + seed))
+    fam["walk_edges"] = walk_edges(random.Random(7311))   # (appended last, a seed of its own: the families above keep their streams and their places in CORPUS)
     return fam
 
 

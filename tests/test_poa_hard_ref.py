@@ -6,19 +6,22 @@ closure U of 32 nodes, the sort fallback the rest), nodes with more than 16 in-e
 is redone on the score matrix) and rows with more than 4 predecessors (the wide-row pool). Five one-line tie-break mutants of the
 restatement (PMR_MUTANT) say whether the inputs tell the tie rules apart. The floors are the issue's; measured:
 
-                                         the 320 random SETS        the corpus (241 sets, 1 087 972 bases)    floor
+                                         the 320 random SETS        the corpus (265 sets, 1 092 592 bases)    floor
     alignments with an end-node tie      9                          619                                       200
     most tie candidates                  2                          6 (SLOW_SETS: 12)                         SLOW_SETS > 8
     ties whose closure U > 32 nodes      0                          23 (SLOW_SETS: 167)                       10
     sets with an in-degree above 16      0 (largest in-degree 5)    7 (largest in-degree 31)                  3
     most wide rows in a set              1                          125                                       100
     most sinks met by an alignment       3                          21 (SLOW_SETS: 46)                        -
-    consensus changed by a mutant        nw / sw / ov               nw / sw / ov                              5 % = 13 sets
+    consensus changed by a mutant        nw / sw / ov               nw / sw / ov                              5 % = 14 sets
       last best end cell                 1 / 5 / 1                  23 / 58 / 56
       vertical before diagonal           83 / 74 / 77               133 / 82 / 88
       horizontal first                   63 / 56 / 56               137 / 75 / 80
       last matching predecessor          45 / 45 / 45               121 / 69 / 77
       `<` in the heaviest-bundle tie     77 / 74 / 76               80 / 74 / 76
+
+(The 24 two-member sets of the family walk_edges are in these figures and add nothing to them: no tie, in-degree 1, no mutant changes their consensus.
+They are there for the shapes of their alignments: test_walk_edges_alignments_have_the_shapes_the_family_is_for.)
 
 Under kSW and kOV (every cell, or every sink row and the last column, is an end candidate) the corpus has 749 and 1 304 tied
 alignments, with up to 56 and 52 tied end cells.
@@ -74,8 +77,9 @@ def linear_results(lin):
 
 def test_the_corpus_is_what_it_says():
     assert sorted(poasets.FAMILIES) == ["fan_in", "fragments", "haplotypes", "homopolymers", "many_members", "other_letters", "prefix_mismatch", "tandem_repeats",
-                                        "two_letters", "unrelated"]
-    assert 200 <= len(CORPUS) <= 400 and len({f for f, _, _ in THIRD}) == 10
+                                        "two_letters", "unrelated", "walk_edges"]
+    assert list(poasets.FAMILIES)[-1] == "walk_edges" and CORPUS[-1][0] == "walk_edges"   # appended last: the other families keep their places
+    assert 200 <= len(CORPUS) <= 400 and len({f for f, _, _ in THIRD}) == 11
     assert sum(len(q) for _, _, st in CORPUS for q in st) < 1_200_000
     assert all(st and all(1 <= len(q) <= 1200 for q in st) for _, _, st in CORPUS + [("slow", k, s) for k, s in enumerate(SLOW_SETS)])
     assert min(len(q) for _, _, st in CORPUS for q in st) <= 3 and max(len(q) for _, _, st in CORPUS for q in st) >= 700
@@ -103,6 +107,25 @@ def test_the_corpus_reaches_ties_in_degrees_and_wide_rows(linear_results, lin):
     slow = [lin.consensus_stats(s, "nw")[2] for s in SLOW_SETS]
     print("SLOW_SETS:", slow)
     assert sum(s["ties_above_8"] for s in slow) >= 1 and max(s["max_candidates"] for s in slow) > 8
+
+
+def test_walk_edges_alignments_have_the_shapes_the_family_is_for(lin):
+    """kNW 5 / -4 / -8: the second member of every walk_edges set aligns to the chain of the first (nodes 0 .. n - 1) exactly as the family says -
+    n pairs to the origin; two leading insertions; two leading nodes without a base; two trailing insertions - at every n around 64 and 128"""
+    sets = poasets.FAMILIES["walk_edges"]
+    assert len(sets) == 4 * len(poasets.WALK_EDGE_LENGTHS)
+    for k, n in enumerate(poasets.WALK_EDGE_LENGTHS):
+        same, lead, cut, trail = sets[4 * k:4 * k + 4]
+        t = same[0]
+        assert len(t) == n and t[0] == "A" and t[-1] in "AT" and all(st[0] == t and len(st) == 2 for st in (same, lead, cut, trail))
+        assert same[1] == t and lead[1] == "CG" + t and cut[1] == t[2:] and trail[1] == t + "CG"
+        diag = [(i, i) for i in range(n)]
+        for st, want in ((same, diag),
+                         (lead, [(-1, 0), (-1, 1)] + [(i, i + 2) for i in range(n)]),
+                         (cut, [(0, -1), (1, -1)] + [(i, i - 2) for i in range(2, n)]),
+                         (trail, diag + [(-1, n), (-1, n + 1)])):
+            lin.consensus(st, "nw")
+            assert lin.last_alignment() == want, (n, st[1][:4])
 
 
 @pytest.mark.parametrize("mutant", sorted(pmrlib.MUTANTS))
