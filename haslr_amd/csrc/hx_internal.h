@@ -23,6 +23,7 @@
 #include "kernels/kernels.h"
 #include "kernels/poa_modes.h"
 #include "hx_poa_report.h"
+#include "hx_poa_pools.h"
 
 namespace hxi {
 
@@ -91,18 +92,7 @@ struct Timer {
 // The POA workspace is ONE device allocation (round 6): an arena that every pool of a batch is carved out of. Forty pools used to be forty synchronous
 // hipMalloc calls inside the first consensus call of a context - seconds of a one-shot run at 140 Mb (215 GB), against a 0.5 s hot path. The arena can be
 // reserved ahead of the first call (hx_poa_reserve: the CLI does it on a thread of its own while the text inputs are parsed), grows when a batch needs
-// more (never shrinks), and is carved anew for every batch: nothing in it outlives a batch.
-template <class T> struct AP { T* p = nullptr; size_t off = 0; };   // a pool: pointer into the arena, byte offset of the current carving
-struct PoaPoolBufs {
-    AP<uint8_t> code, n_aligned, mark, check, row_code, row_sink, seq;
-    AP<uint32_t> aligned, in_head, in_tail, out_head, out_tail, rank2node, node2rank, stack, row_pred_off, pred_rank, e_from, e_to, e_next_in, e_next_out;
-    AP<int32_t> score, pred, e_w, aln_node, aln_pos, H, pred_w;
-    AP<uint32_t> row_meta, row_pred0, row_pred1;
-    AP<uint4> nrec, nrec2;
-    AP<uint8_t> dir, dirw; AP<uint32_t> wslot;
-    AP<unsigned long long> mbox; AP<int32_t> sinkbuf; AP<uint32_t> csync; AP<uint16_t> row_al;   // cluster mode (edges shared by several workgroups)
-    AP<char> cns;                                                                                  // consensus strings as the kernels leave them (capacity = node estimate per edge)
-};
+// more (never shrinks), and is carved anew for every batch: nothing in it outlives a batch. The pools and their list: hx_poa_pools.h.
 struct PoaArena {
     uint8_t* p = nullptr;
     size_t cap = 0;

@@ -22,6 +22,8 @@ static int scratch_warm_once(hx_ctx* c) {
     return 0;
 }
 
+static double since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }   // milliseconds
+
 namespace {
 // One consensus call: the PLAN (PoaPlanner, hx_poa_plan.hip: sub-sequences, per-edge capacities, launch classes, workspace slots and batches against the
 // memory budget), the LAUNCH of a batch, and the COLLECTION of its results with the verdict on every edge (done / again with more room / again another way).
@@ -33,51 +35,21 @@ struct PoaCall : PoaPlanner {
     std::vector<std::unique_ptr<char[]>> cns_blocks;     // ... the download of its batch (kept to the end of the call: no copy per edge, no zero fill)
 
     PoaCall(hx_ctx* c_, const PoaInput& in_, const hx_poa_params* pp_) : PoaPlanner(in_, pp_, c_->opt, c_->poa_block, c_->poa_no_dir), c(c_), cns(in_.n_edge) {}
-    double ms_since_start() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-    // ---- launch of one batch; what the collection needs afterwards
-    struct Launched { std::vector<uint32_t> edges; uint64_t cns_bytes = 0, bytes = 0; std::vector<Cls> classes; };
+    double ms_since_start() const { return since(t0); }
+    // ---- launch of one batch: what needs the device. The arithmetic is the layout's three steps (PoaPlanner::layout_slots, ::layout_order, ::layout_launches), each
+    // taken where it has always stood among the HIP calls: the device works on what is queued meanwhile, and the launches leave when their inputs are on the way
+    struct Launched { std::vector<uint32_t> edges; uint64_t bytes = 0; };   // what the collection needs afterwards
     int launch_batch(const std::vector<uint32_t>& batch, uint32_t shrink, Launched& lb) {
         hipStream_t s = c->stream;
         PoaPoolBufs& B = c->poa_pools;
-        lb.edges = batch;
-        std::vector<Cls>& classes = lb.classes;
-        if (build_classes(batch, classes)) return -1;
-        // ---- slots and their offsets into the pools
-        std::vector<hxk::PoaSlot> h_slots;
-        uint64_t no = 0, eo = 0, ho = 0, dro = 0, wo = 0, so = 0, co = 0, sto = 0, ao = 0, clo = 0;
-        auto add_slot = [&](const Need& n) {
-            h_slots.push_back(hxk::PoaSlot{no, eo, ho, dro, wo, so, sto, ao, clo});
-            no += n.nn; eo += n.ec; ho += n.hc; dro += n.dc; wo += n.wc; so += n.lm; sto += n.st; ao += n.al; clo += n.mb;
-        };
-        arrange(classes, shrink);
-        for (Cls& q : classes) {
-            q.slot_at = h_slots.size();
-            for (size_t k = 0; k < q.n_slots; k++) {
-                if (!q.persistent) P.edges[q.edges[k]].slot = (uint32_t)h_slots.size();   // one workgroup (or cluster) per edge: the edge's own slot
-                add_slot(slot_need(q, k));
-            }
-            for (uint32_t e : q.edges) {
-                P.edges[e].cns_off = co; co += P.edges[e].vcap;
-                if (q.shared) { P.edges[e].cl_off = clo; clo += (uint64_t)P.edges[e].members * ((uint64_t)P.edges[e].vcap + 1); }
-            }
-        }
-        lb.cns_bytes = co;
-        const uint64_t bytes = no * 106 + eo * 28 + ho * 4 + dro + wo + so + sto * 4 + ao * 8 + clo * 8 + co;
-        lb.bytes = bytes;
-        // The pools of the batch, carved out of the context's arena (256-byte aligned). The arena grows when a batch needs more than it holds - by an eighth
-        // more than asked, so that the retries of a call (a few edges with more room) do not each allocate again - and never shrinks.
+        BatchLayout Y;
+        if (layout_slots(batch, shrink, Y)) return -1;
+        lb.edges = batch; lb.bytes = Y.bytes;
+        // ---- the arena. It grows when a batch needs more than it holds - by an eighth more than asked, so that the retries of a call (a few edges with more
+        // room) do not each allocate again - and never shrinks.
         {
             const auto tw0 = std::chrono::steady_clock::now();
-            size_t at = 0;
-            auto place = [&at](auto& buf, uint64_t n) { buf.off = at; at += (std::max<uint64_t>(1, n) * sizeof(*buf.p) + 255) & ~(size_t)255; };
-            auto bind = [this](auto& buf, uint64_t) { buf.p = reinterpret_cast<decltype(buf.p)>(c->poa_arena.p + buf.off); };
-#define HX_POOLS(F) \
-            F(B.H, ho); F(B.dir, dro); F(B.dirw, wo); F(B.wslot, no); F(B.code, no); F(B.n_aligned, no); F(B.mark, no); F(B.check, no); F(B.row_code, no); F(B.row_sink, no); \
-            F(B.row_al, no); F(B.aligned, 3 * no); F(B.in_head, no); F(B.in_tail, no); F(B.out_head, no); F(B.out_tail, no); F(B.rank2node, no); F(B.node2rank, no); \
-            F(B.row_pred_off, no); F(B.score, no); F(B.pred, no); F(B.pred_rank, eo); F(B.pred_w, eo); F(B.e_from, eo); F(B.e_to, eo); F(B.e_next_in, eo); F(B.e_next_out, eo); \
-            F(B.e_w, eo); F(B.stack, sto); F(B.aln_node, ao); F(B.aln_pos, ao); F(B.row_meta, no); F(B.row_pred0, no); F(B.row_pred1, no); F(B.nrec, no); F(B.nrec2, no); \
-            F(B.seq, so); F(B.cns, co); F(B.mbox, clo); F(B.csync, (uint64_t)ne * 8); F(B.sinkbuf, (uint64_t)ne * (1 + 2 * 1024));
-            HX_POOLS(place)
+            const size_t at = Y.at;
             std::lock_guard<std::mutex> lk(c->poa_arena_mu);
             if (at > c->poa_arena.cap) {
                 HIPCHK(hipStreamSynchronize(s));   // (nothing of an earlier batch is in flight: collect_batch has read its results)
@@ -91,143 +63,75 @@ struct PoaCall : PoaPlanner {
                     return 1;
                 }
             }
-            HX_POOLS(bind)
-#undef HX_POOLS
-            c->poa_host_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+            B.bind(c->poa_arena.p, Y.off);
+            c->poa_host_ms[1] += since(tw0);
         }
-        c->poa_workspace_bytes = std::max<uint64_t>(c->poa_workspace_bytes, bytes);
-        c->poa_last_workspace_bytes = std::max<uint64_t>(c->poa_last_workspace_bytes, bytes);
+        c->poa_workspace_bytes = std::max<uint64_t>(c->poa_workspace_bytes, Y.bytes);
+        c->poa_last_workspace_bytes = std::max<uint64_t>(c->poa_last_workspace_bytes, Y.bytes);
+        // ---- memsets and uploads: the edges, the order list, the slots, the counters, the groups' tables
         const auto te0 = std::chrono::steady_clock::now();
-        HIPCHK(hipMemsetAsync(B.csync.p, 0, (size_t)ne * 8 * 4, s));
-        if (clo) HIPCHK(hipMemsetAsync(B.mbox.p, 0, clo * 8, s));   // tag 0 = nothing published
+        HIPCHK(hipMemsetAsync(B.csync, 0, (size_t)ne * 8 * 4, s));
+        if (Y.tot.clo) HIPCHK(hipMemsetAsync(B.mbox, 0, Y.tot.clo * 8, s));   // tag 0 = nothing published
         HIPCHK(c->poa_edges.reserve(ne)); HIPCHK(c->poa_len.reserve(ne)); HIPCHK(c->poa_status.reserve(ne));
-        std::vector<uint32_t> order_all;   // shared launches: one entry per workgroup (edge | member << 24); persistent launches: the class's edges, costliest first
-        for (Cls& q : classes) {
-            q.order_at = order_all.size();
-            if (q.shared) {
-                // Workgroups are handed to the 8 XCDs round-robin by index: put the members of one edge 8 indices apart so that they share an
-                // XCD (one L2 for the carries, the handshakes and the direction bytes member 0 walks back over). Holes are no-op workgroups.
-                for (size_t g0 = 0; g0 < q.edges.size(); g0 += 8) {
-                    const size_t g1 = std::min(q.edges.size(), g0 + 8);
-                    uint32_t gmax = 0;
-                    for (size_t j = g0; j < g1; j++) gmax = std::max(gmax, P.edges[q.edges[j]].members);
-                    for (uint32_t m = 0; m < gmax; m++)
-                        for (size_t j = g0; j < g0 + 8; j++)
-                            order_all.push_back(j < g1 && m < P.edges[q.edges[j]].members ? (q.edges[j] | (m << 24)) : 0x00ffffffu);
-                }
-            } else
-                for (uint32_t e : q.edges) order_all.push_back(e);
-            q.blocks = q.shared ? order_all.size() - q.order_at : q.n_slots;   // (not shared: one workgroup per slot - per edge unless persistent)
-        }
-        if (ne >= (1u << 24)) return fail("hx_poa_batch: more than 2^24 edges in one call");
+        layout_order(Y);   // (beside the memsets)
         HIPCHK(hipMemcpyAsync(c->poa_edges.p, P.edges.data(), (size_t)ne * sizeof(hxk::PoaEdge), hipMemcpyHostToDevice, s));
-        HIPCHK(c->poa_order.reserve(order_all.size()));
-        HIPCHK(hipMemcpyAsync(c->poa_order.p, order_all.data(), order_all.size() * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(c->poa_slots.reserve(h_slots.size()));
-        HIPCHK(hipMemcpyAsync(c->poa_slots.p, h_slots.data(), h_slots.size() * sizeof(hxk::PoaSlot), hipMemcpyHostToDevice, s));
-        HIPCHK(c->poa_counters.reserve(classes.size()));
-        HIPCHK(hipMemsetAsync(c->poa_counters.p, 0, classes.size() * 4, s));
-        hxk::PoaPools pools{B.code.p, B.n_aligned.p, B.aligned.p, B.in_head.p, B.in_tail.p, B.out_head.p, B.out_tail.p, B.rank2node.p, B.node2rank.p,
-                            B.mark.p, B.check.p, B.stack.p, B.score.p, B.pred.p, B.row_code.p, B.row_sink.p, B.row_pred_off.p, B.pred_rank.p, B.row_meta.p, B.row_pred0.p, B.row_pred1.p, B.nrec.p, B.nrec2.p,
-                            B.e_from.p, B.e_to.p, B.e_next_in.p, B.e_next_out.p, B.e_w.p, B.aln_node.p, B.aln_pos.p, B.H.p, B.dir.p, B.dirw.p, B.wslot.p, B.seq.p,
-                            B.mbox.p, B.csync.p, B.sinkbuf.p, B.row_al.p, B.pred_w.p};
-        const size_t n_streams = (size_t)std::min(8, std::max(1, o.poa_streams));   // (8: a stream per launch class of a 140 Mb call - with 6, the two one-wave classes waited 130 / 300 ms behind the shared edges)
-        size_t wg_total = 0;
-        for (const Cls& q : classes) wg_total += q.blocks;
+        HIPCHK(c->poa_order.reserve(Y.order_all.size()));
+        HIPCHK(hipMemcpyAsync(c->poa_order.p, Y.order_all.data(), Y.order_all.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(c->poa_slots.reserve(Y.h_slots.size()));
+        HIPCHK(hipMemcpyAsync(c->poa_slots.p, Y.h_slots.data(), Y.h_slots.size() * sizeof(hxk::PoaSlot), hipMemcpyHostToDevice, s));
+        HIPCHK(c->poa_counters.reserve(Y.classes.size()));
+        HIPCHK(hipMemsetAsync(c->poa_counters.p, 0, Y.classes.size() * 4, s));
         c->tick();
-        // The launches. Persistent classes that differ only in their need bucket (build_classes) leave in ONE launch: their slots, lists and counters
-        // lie side by side in class order (largest need first), `btab` tells a workgroup which bucket its slot belongs to (kernels/poa.hip k_poa).
-        std::vector<uint32_t> h_btab;
-        std::vector<std::array<size_t, 3>> groups;   // first class, one past the last, offset of the group's table in h_btab
-        for (size_t i = 0; i < classes.size();) {
-            size_t j = i + 1;
-            const Cls& a = classes[i];
-            while (j < classes.size() && same_instance(a, classes[j])) j++;
-            groups.push_back({i, j, h_btab.size()});
-            if (a.persistent) {
-                h_btab.push_back((uint32_t)(j - i) | (o.poa_own_bucket_first ? 1u << 16 : 0u));
-                uint32_t se = 0, ib = 0;
-                for (size_t k = i; k < j; k++) { se += (uint32_t)classes[k].blocks; h_btab.push_back(se); }
-                for (size_t k = i; k < j; k++) { h_btab.push_back(ib); ib += (uint32_t)classes[k].edges.size(); }
-                h_btab.push_back(ib);
-                for (size_t k = i; k < j; k++) for (uint32_t e : classes[k].edges) h_btab.push_back((uint32_t)std::min(4.0e9, (double)chain_ms[e] * 1000.0));   // est[]: microseconds
-            }
-            i = j;
-        }
-        HIPCHK(c->poa_btab.reserve(std::max<size_t>(1, h_btab.size())));
-        if (!h_btab.empty()) HIPCHK(hipMemcpyAsync(c->poa_btab.p, h_btab.data(), h_btab.size() * 4, hipMemcpyHostToDevice, s));
+        layout_launches(Y);   // (beside the uploads)
+        HIPCHK(c->poa_btab.reserve(std::max<size_t>(1, Y.h_btab.size())));
+        if (!Y.h_btab.empty()) HIPCHK(hipMemcpyAsync(c->poa_btab.p, Y.h_btab.data(), Y.h_btab.size() * 4, hipMemcpyHostToDevice, s));
         if (scratch_warm_once(c)) return -1;
         HIPCHK(hipEventRecord(c->poa_ev[8], s));
-        size_t gi = 0;
-        for (const auto& grp : groups) {
-            const size_t ci = grp[0];
-            const Cls& q = classes[ci];
-            size_t g_blocks = 0, g_items = 0;
-            for (size_t k = grp[0]; k < grp[1]; k++) { g_blocks += classes[k].blocks; g_items += classes[k].edges.size(); }
-            const int sk = (int)(gi % n_streams);   // stream / event of the launch (launches that share a stream run one after the other)
-            // LDS of the launch: the ring its row width allows, a power of two of kept rows
-            uint64_t ring_need = 0;
-            const uint32_t dp_nt = q.dpl ? q.dpl : q.nt;   // lanes in the DP
-            const uint32_t R = ring_rows_of(dp_nt, q.cm, ring_need);
-            // few edges: ask for enough LDS per workgroup that the dispatcher cannot stack them on a handful of CUs while others idle
-            // (a lone wave runs at twice the speed of two waves sharing a SIMD); many edges: request only what the ring needs
-            uint64_t lds_bytes = ring_need;
-            {
-                const uint64_t per_cu = (wg_total + 255) / 256;
-                if (per_cu < 8) lds_bytes = std::max<uint64_t>(lds_bytes, std::min<uint64_t>(kPoaLdsMax, (158 * 1024) / per_cu - 18 * 1024));
-                // hundreds of edges: the longest ones set the duration, and their waves run faster with two neighbours on a SIMD than with
-                // three - 10 KB of LDS per wave keeps a CU at 12 waves (thousands of edges: 16, the ring alone is 8.3 KB per wave)
-                if (!many_edges) lds_bytes = std::max<uint64_t>(lds_bytes, std::min<uint64_t>(kPoaLdsMax, 10 * 1024 * (uint64_t)(dp_nt / 64)));
-                if (o.poa_ring_zero) lds_bytes = ring_need;   // (one row's worth: the kernel then finds room for no kept row either)
-            }
-            const int dcls = q.shared ? 0 : q.nt >= 1024 ? 1 : q.nt >= 512 ? 2 : q.nt >= 256 ? 3 : q.nt >= 128 ? 4 : 5;
-            for (size_t k = grp[0]; k < grp[1]; k++)
-                for (uint32_t e : classes[k].edges) { c->poa_shape.cls[e] = (uint8_t)(dcls + (q.dir ? 0 : 5)); c->poa_shape.shape[e] = q.nt | std::min<uint32_t>(255, P.edges[e].passes) << 16 | std::min<uint32_t>(255, P.edges[e].members) << 24; }
-            c->poa_shape.ring[dcls + (q.dir ? 0 : 5)] = R;
+        // ---- the launches: a record of the layout + the addresses
+        const hxk::PoaPools pools = B.view();
+        for (size_t gi = 0, si = 0; gi < Y.launches.size(); gi++) {
+            const PoaLaunchRec& rec = Y.launches[gi];
+            const int sk = rec.stream;
+            for (; si < rec.shapes_end; si++) { const auto& es = Y.shapes[si]; c->poa_shape.cls[es[0]] = (uint8_t)es[1]; c->poa_shape.shape[es[0]] = es[2]; }   // (the launch's own, as ever between two launches)
+            c->poa_shape.ring[rec.code] = rec.R;
             HIPCHK(hipStreamWaitEvent(c->poa_streams[sk], c->poa_ev[8], 0));
-            hxk::PoaLaunch L{};
-            L.edges = c->poa_edges.p; L.order = c->poa_order.p + q.order_at; L.n_items = q.persistent ? (uint32_t)g_items : (uint32_t)q.blocks;
-            L.slots = c->poa_slots.p + (q.persistent ? q.slot_at : 0); L.counter = q.persistent ? c->poa_counters.p + ci : nullptr; L.n_blocks = (uint32_t)g_blocks;
-            L.btab = q.persistent ? c->poa_btab.p + grp[2] : nullptr;
-            L.seqs = c->poa_seqs.p; L.packed = in.d_packed; L.read_off = in.d_roff; L.read_len = in.d_rlen; L.pools = pools;
-            L.match = pp->match; L.mismatch = pp->mismatch; L.gap = pp->gap; L.cns = B.cns.p; L.cns_len = c->poa_len.p; L.status = c->poa_status.p;
-            L.cells = c->poa_cells_d.p; L.phase = c->poa_phase_d.p; L.block_threads = (int)q.nt; L.cm = (int)q.cm; L.poll_limit = (uint32_t)o.poa_poll_limit; L.ring_bytes = (uint32_t)lds_bytes;
-            L.use_dir = q.dir; L.max_indeg = (uint32_t)std::min(16, std::max(1, o.poa_max_indeg)); L.dp_lanes = q.dpl;
-            const bool wide_q = q.dpl || (balanced && q.nt >= balance_nt && q.nt >= 512 && q.persistent), shared_first = many_edges && q.shared && (o.poa_resident_first & 1);
-            L.started = ((wide_q && (o.poa_resident_first & 2)) || shared_first) && gi < 16 ? c->poa_started + gi : nullptr;
+            hxk::PoaLaunch L = rec.L;   // every scalar; now every pointer
+            L.edges = c->poa_edges.p; L.seqs = c->poa_seqs.p; L.packed = in.d_packed; L.read_off = in.d_roff; L.read_len = in.d_rlen; L.pools = pools;
+            L.cns = B.cns; L.cns_len = c->poa_len.p; L.status = c->poa_status.p; L.cells = c->poa_cells_d.p; L.phase = c->poa_phase_d.p;
+            L.order = c->poa_order.p + rec.order_at; L.slots = c->poa_slots.p + rec.slot_at;
+            L.counter = rec.persistent ? c->poa_counters.p + rec.counter_at : nullptr; L.btab = rec.persistent ? c->poa_btab.p + rec.btab_at : nullptr;
+            L.started = rec.started_at >= 0 ? c->poa_started + rec.started_at : nullptr;
             if (L.started) *(volatile uint32_t*)L.started = 0u;
-            L.prune_pct = launch_pruned(q) ? (std::min<uint32_t>(q.shared ? prune_shared_pct : prune_pct, 1000u) | (o.poa_prune_lazy ? 1u << 16 : 0u)) : 0u;
-            if (o.debug) { int occ = 0; L.occupancy = &occ; hxk::poa_run(L, c->poa_streams[sk]); L.occupancy = nullptr; fprintf(stderr, "[hx] launch %zu: %zu workgroups of %u lanes, %.1f KB of ring: %d workgroups per CU\n", gi, g_blocks, q.nt, lds_bytes / 1024.0, occ); }
+            if (o.debug) { int occ = 0; L.occupancy = &occ; hxk::poa_run(L, c->poa_streams[sk]); L.occupancy = nullptr; fprintf(stderr, "[hx] launch %zu: %zu workgroups of %u lanes, %.1f KB of ring: %d workgroups per CU\n", gi, (size_t)L.n_blocks, (unsigned)L.block_threads, rec.lds_bytes / 1024.0, occ); }
             hxk::poa_run(L, c->poa_streams[sk]);
             HIPCHK(hipEventRecord(c->poa_ev[sk], c->poa_streams[sk]));
             HIPCHK(hipStreamWaitEvent(s, c->poa_ev[sk], 0));
-            if (wide_q || shared_first) {
-                // a 1024-lane workgroup needs an EMPTY CU: give the dispatcher a head start before the other launches fill the chip with small
-                // workgroups (once they have, a CU only empties when its longest resident workgroup ends)
+            if (rec.wait != PoaLaunchRec::kNoWait) {   // the head start of a wide or a shared launch (layout_launches)
                 HIPCHK(hipEventSynchronize(c->poa_ev[8]));   // (what precedes the launches on `s` is done: the wide launch is starting)
                 const auto tw = std::chrono::steady_clock::now();
-                if (L.started) {
+                if (rec.wait == PoaLaunchRec::kWaitStarted) {
                     // (round 6: not a fixed delay but the launch's own word - every workgroup adds itself when it begins. One pass in five of the 140 Mb call took 610-650 ms
                     // instead of 440-470: no edge redone, the same launches - in another order of arrival on the CUs. The shared edges' members and the wide classes
                     // must be the oldest waves where they sit; the next launch leaves when they have all begun, or after 2 ms)
                     volatile uint32_t* w = L.started;
-                    while (*w < L.n_blocks && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count() < 2000.0) { }
-                    if (o.debug) fprintf(stderr, "[hx] launch %zu: %u of %u workgroups had begun %.0f us after the launch\n", gi, (unsigned)*w, L.n_blocks, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count());
+                    while (*w < L.n_blocks && since(tw) < 2.0) { }
+                    if (o.debug) fprintf(stderr, "[hx] launch %zu: %u of %u workgroups had begun %.0f us after the launch\n", gi, (unsigned)*w, L.n_blocks, since(tw) * 1000.0);
                 } else
-                    while (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count() < o.poa_wide_delay_us) { }
+                    while (since(tw) * 1000.0 < o.poa_wide_delay_us) { }
             }
-            gi++;
         }
+        // ---- the laps
+        const double enqueue_ms = since(te0);
         const auto te1 = std::chrono::steady_clock::now();
         c->tock(3);
-        c->poa_host_ms[2] += std::chrono::duration<double, std::milli>(te1 - te0).count();
-        c->poa_host_ms[3] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te1).count();
+        c->poa_host_ms[2] += enqueue_ms;
+        c->poa_host_ms[3] += since(te1);
         HIPCHK(hipGetLastError());
         if (o.debug) {
             HIPCHK(hipStreamSynchronize(s));
-            fprintf(stderr, "[hx] POA batch: %zu edges, %.2f GB workspace, workgroups", batch.size(), bytes / 1e9);
-            for (const Cls& q : classes) fprintf(stderr, " %s%s%s%s%ux%u:%zu(%zu edges, largest %.1f MB)", q.shared ? "shared/" : "", q.persistent ? "persistent/" : "", q.dir ? "" : "matrix/",
-                                                 launch_pruned(q) ? (q.pk ? "pruned/passes/" : "pruned/") : "", q.nt, q.cm, q.blocks, q.edges.size(), need_bytes(q.need) / 1e6);
+            fprintf(stderr, "[hx] POA batch: %zu edges, %.2f GB workspace, workgroups", batch.size(), Y.bytes / 1e9);
+            for (const Cls& q : Y.classes) fprintf(stderr, " %s%s%s%s%ux%u:%zu(%zu edges, largest %.1f MB)", q.shared ? "shared/" : "", q.persistent ? "persistent/" : "", q.dir ? "" : "matrix/",
+                                                   launch_pruned(q) ? (q.pk ? "pruned/passes/" : "pruned/") : "", q.nt, q.cm, q.blocks, q.edges.size(), need_bytes(q.need) / 1e6);
             fprintf(stderr, ", %.1f ms since the call began\n", ms_since_start());
         }
         return 0;
@@ -235,7 +139,6 @@ struct PoaCall : PoaPlanner {
 
     // ---- collection: consensus strings of the edges that are done; the others go to `retry` (worst-case workspace next) / `retry_same` (another way)
     int collect_batch(const Launched& lb, std::vector<uint32_t>& retry, std::vector<uint32_t>& retry_same) {
-        const auto tc0 = std::chrono::steady_clock::now();
         hipStream_t s = c->stream;
         std::vector<uint32_t> h_len(ne), h_status(ne);
         HIPCHK(hipMemcpy(h_len.data(), c->poa_len.p, (size_t)ne * 4, hipMemcpyDeviceToHost));
@@ -258,11 +161,10 @@ struct PoaCall : PoaPlanner {
         if (!desc.empty()) {
             HIPCHK(c->poa_gather.reserve(desc.size())); HIPCHK(c->poa_cns_dense.reserve(dense_off.back()));
             HIPCHK(hipMemcpyAsync(c->poa_gather.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, s));
-            hxk::gather_bytes(c->poa_pools.cns.p, c->poa_gather.p, (uint32_t)(desc.size() / 5), c->poa_cns_dense.p, s);
+            hxk::gather_bytes(c->poa_pools.cns, c->poa_gather.p, (uint32_t)(desc.size() / 5), c->poa_cns_dense.p, s);
             HIPCHK(hipMemcpyAsync(cns_blocks.back().get(), c->poa_cns_dense.p, dense_off.back(), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
         }
-        struct Lap { double& ms; std::chrono::steady_clock::time_point t0; ~Lap() { ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } lap{c->poa_host_ms[4], tc0};
         {
             size_t n_far = 0, n_nodir = 0, n_over = 0, n_wide = 0, n_sinks = 0, n_stall = 0;
             for (uint32_t e : lb.edges) { n_far += !!(h_status[e] & HXE_POA_FARROWS); n_nodir += !!(h_status[e] & HXE_POA_NODIR); n_over += !!(h_status[e] & HXE_POA_OVERFLOW); n_wide += !!(h_status[e] & HXE_POA_WIDEROWS); n_sinks += !!(h_status[e] & HXE_POA_SINKS); n_stall += !!(h_status[e] & HXE_POA_STALLED); }
@@ -302,7 +204,6 @@ static int poa_consensus(hx_ctx* c, const PoaInput& in, const hx_poa_params* pp,
     std::vector<uint32_t> todo;
     for (double& v : c->poa_host_ms) v = 0;
     for (uint64_t& v : c->poa_retry) v = 0;
-    auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
     if (K.plan_input(todo)) return -1;
     c->poa_host_ms[0] += K.ms_since_start();
     if (c->opt.debug) fprintf(stderr, "[hx] POA call: %u edges prepared in %.1f ms\n", (unsigned)ne, K.ms_since_start());
@@ -357,7 +258,11 @@ static int poa_consensus(hx_ctx* c, const PoaInput& in, const hx_poa_params* pp,
                 for (size_t bj = bi; bj < batches.size(); bj++) retry_same.insert(retry_same.end(), batches[bj].begin(), batches[bj].end());
                 break;
             }
-            if (rc || K.collect_batch(lb, retry, retry_same)) return -1;
+            if (rc) return -1;
+            const auto tc0 = std::chrono::steady_clock::now();
+            const int rc_collect = K.collect_batch(lb, retry, retry_same);
+            c->poa_host_ms[4] += since(tc0);
+            if (rc_collect) return -1;
         }
         todo.swap(retry);
         todo.insert(todo.end(), retry_same.begin(), retry_same.end());

@@ -1,5 +1,5 @@
 // hx_poa_plan.h - the planner of a POA consensus call: sub-sequences, per-edge capacities, launch classes, workspace slots and batches
-// against the memory budget. Pure host heuristics: no HIP runtime call, no context - the context's two settings it reads come in as values.
+// against the memory budget, and the layout of every batch (what its launch uploads and is given). Pure host heuristics: no HIP runtime call, no context - the context's two settings it reads come in as values.
 #pragma once
 #include "hx_internal.h"
 
@@ -28,7 +28,13 @@ inline void need_max(Need& a, const Need& b) {
     a.nn = std::max(a.nn, b.nn); a.ec = std::max(a.ec, b.ec); a.hc = std::max(a.hc, b.hc); a.dc = std::max(a.dc, b.dc); a.wc = std::max(a.wc, b.wc);
     a.lm = std::max(a.lm, b.lm); a.st = std::max(a.st, b.st); a.al = std::max(a.al, b.al); a.mb = std::max(a.mb, b.mb);
 }
+// bytes of a slot. The figures are the pool table's (hx_poa_pools.h), but for the node's: the slot counts under a binding budget depend on them,
+// so 106 stays. (The slack: the per-node pools sum to 104 bytes - two bytes a node counted that no pool takes, an over-estimate.)
 inline uint64_t need_bytes(const Need& n) { return n.nn * 106 + n.ec * 28 + n.hc * 4 + n.dc + n.wc + n.lm + n.st * 4 + n.al * 8 + n.mb * 8; }
+static_assert(poa_pool_bytes_per(PoaPoolTotal::no) <= 106 && poa_pool_bytes_per(PoaPoolTotal::eo) == 28, "need_bytes: a node or a graph edge costs more than the pools' list says");
+static_assert(poa_pool_bytes_per(PoaPoolTotal::ho) == 4 && poa_pool_bytes_per(PoaPoolTotal::dro) == 1 && poa_pool_bytes_per(PoaPoolTotal::wo) == 1 && poa_pool_bytes_per(PoaPoolTotal::so) == 1 &&
+              poa_pool_bytes_per(PoaPoolTotal::sto) == 4 && poa_pool_bytes_per(PoaPoolTotal::ao) == 8 && poa_pool_bytes_per(PoaPoolTotal::clo) == 8 && poa_pool_bytes_per(PoaPoolTotal::co) == 1,
+              "need_bytes: the other figures are the pools' list's");
 
 // launch classes: (shared?, lanes per workgroup, columns per lane, traceback flavour) - one kernel instance each, so that every
 // launch runs with the registers ITS row loop needs (kernels/poa.hip)
@@ -48,6 +54,36 @@ constexpr int NCLS = 11;
 constexpr uint64_t kPoaLdsMax = 140 * 1024;   // dynamic LDS of a POA workgroup at most (160 KB per CU less the 1024-lane kernel's static 16.5 KB: sink lists, wave mailboxes)
 const int kClassNT[NCLS] = {0, 1024, 512, 256, 128, 64, 1024, 512, 256, 128, 64};
 constexpr size_t kManyEdges = 3000;
+
+// One launch of a batch as the layout leaves it: everything but the addresses. Persistent classes that differ only in their need bucket
+// (build_classes) leave in ONE launch.
+struct PoaLaunchRec {
+    int stream = 0;                  // index of the stream / event of the launch (launches that share a stream run one after the other)
+    uint32_t R = 0;                  // kept rows of the LDS ring
+    uint64_t lds_bytes = 0;          // dynamic LDS of a workgroup
+    int code = 0;                    // shape-class code of the launch's edges (PoaCallShape::cls, ::ring)
+    size_t shapes_end = 0;           // one past the launch's last entry of BatchLayout::shapes (its first: where the launch before ends)
+    hxk::PoaLaunch L{};              // every scalar field filled, every pointer null (launch_batch copies it whole and sets the pointers)
+    bool persistent = false;         // (else: no counter, no btab, slots from 0)
+    size_t order_at = 0, slot_at = 0, counter_at = 0, btab_at = 0;   // what the pointers order / slots / counter / btab get added
+    int started_at = -1;             // index of the launch's `started` word, -1: none
+    enum Wait { kNoWait, kWaitStarted, kWaitDelay } wait = kNoWait;   // the head start after it: until its workgroups have all begun (or 2 ms), or option poa_wide_delay_us
+};
+
+// Everything the launch of a batch computes before and between its HIP calls (PoaPlanner::layout_slots, ::layout_order, ::layout_launches). The edges' slot / cns_off / cl_off
+// are written into PoaPlan::edges.
+struct BatchLayout {
+    std::vector<Cls> classes;                    // after build_classes and arrange, with slot_at / order_at / blocks
+    std::vector<hxk::PoaSlot> h_slots;
+    PoaPoolTotals tot;                           // of the pools
+    uint64_t bytes = 0;                          // workspace of the batch as the budget counts it (total_bytes)
+    PoaPoolOffsets off; size_t at = 0;           // the pools in the arena, its size
+    std::vector<uint32_t> order_all;             // shared launches: one entry per workgroup (edge | member << 24, 0x00ffffff: a hole); persistent launches: the class's edges, costliest first
+    std::vector<uint32_t> h_btab;                // per launch group of persistent classes: {buckets | own-bucket-first << 16, slot_end[], item_begin[], est[]} (kernels/kernels.h PoaLaunch)
+    std::vector<std::array<size_t, 3>> groups;   // first class, one past the last, offset of the group's table in h_btab
+    std::vector<PoaLaunchRec> launches;          // one per group, in launch order
+    std::vector<std::array<uint32_t, 3>> shapes; // edge, class code, lanes | passes << 16 | members << 24 (PoaCallShape), in launch order
+};
 
 // The plan of one consensus call, and the per-edge retry state that the collection of every batch updates (hx_poa.hip: PoaCall).
 struct PoaPlanner {
@@ -103,7 +139,15 @@ struct PoaPlanner {
     void arrange(std::vector<Cls>& classes, uint32_t shrink) const;
     static bool same_instance(const Cls& a, const Cls& b) { return a.persistent && b.persistent && a.nt == b.nt && a.cm == b.cm && a.dir == b.dir && a.dpl == b.dpl && a.pk == b.pk; }
     Need slot_need(const Cls& q, size_t b) const { return q.persistent ? q.need : need_of(q.edges[b]); }   // per slot: the edge's own need, or (persistent) the largest of the class
+    // what an edge takes beside its slot: the consensus output and, shared, the cluster mailboxes (words of 8 bytes)
+    uint64_t cluster_words(uint32_t e) const { return (uint64_t)P.edges[e].members * ((uint64_t)P.edges[e].vcap + 1); }
+    uint64_t edge_out_bytes(uint32_t e, bool shared) const { return P.edges[e].vcap + (shared ? cluster_words(e) * 8 : 0); }
     uint64_t total_bytes(std::vector<Cls>& classes, uint32_t shrink) const;
+    // plan, part 5: the layout of a batch (no HIP call, no context, no clock), in the three steps its launch takes, in this order, each where that
+    // arithmetic has always stood among the HIP calls
+    int layout_slots(const std::vector<uint32_t>& batch, uint32_t shrink, BatchLayout& Y);   // classes, slots, pools
+    void layout_order(BatchLayout& Y) const;                                                  // the order list (and the classes' blocks)
+    void layout_launches(BatchLayout& Y) const;                                               // groups and tables, launches, shape entries
     int plan_batches(const std::vector<uint32_t>& todo, std::vector<std::vector<uint32_t>>& batches, std::vector<uint32_t>& batch_shrink);
     bool launch_pruned(const Cls& q) const;
 };

@@ -1,4 +1,4 @@
-// hx_poa_plan.hip - the planner of a POA consensus call (hx_poa_plan.h): parts 1-4 of the plan and the launch-class decisions the
+// hx_poa_plan.hip - the planner of a POA consensus call (hx_poa_plan.h): parts 1-5 of the plan and the launch-class decisions the
 // launch reads back. Host code only.
 #include "hx_poa_plan.h"
 
@@ -487,9 +487,136 @@ uint64_t PoaPlanner::total_bytes(std::vector<Cls>& classes, uint32_t shrink) con
     arrange(classes, shrink);
     for (Cls& q : classes) {
         for (size_t b = 0; b < q.n_slots; b++) t += need_bytes(slot_need(q, b));
-        for (uint32_t e : q.edges) t += P.edges[e].vcap + (q.shared ? (uint64_t)P.edges[e].members * ((uint64_t)P.edges[e].vcap + 1) * 8 : 0);   // consensus output, cluster mailboxes
+        for (uint32_t e : q.edges) t += edge_out_bytes(e, q.shared);
     }
     return t;
+}
+
+// ---- plan, part 5: the layout of one batch in three steps - layout_slots: classes, slots and pools; layout_order: the order list; layout_launches: the launch
+// groups with their tables, and every launch but its addresses. (Three, because the launch of a batch takes each where that arithmetic has always stood among
+// its HIP calls - the device works on what is queued meanwhile, and how the uploads and launches are spaced decides in which order workgroups reach the CUs.)
+int PoaPlanner::layout_slots(const std::vector<uint32_t>& batch, uint32_t shrink, BatchLayout& Y) {
+    Y = BatchLayout{};
+    if (ne >= (1u << 24)) return fail("hx_poa_batch: more than 2^24 edges in one call");   // (an order entry is edge | member << 24)
+    std::vector<Cls>& classes = Y.classes;
+    if (build_classes(batch, classes)) return -1;
+    arrange(classes, shrink);
+    // ---- slots and their offsets into the pools. `bytes` is total_bytes' sum: a total is the sum of its slots' needs (clo: and the cluster words), need_bytes is linear
+    PoaPoolTotals& T = Y.tot;
+    T.ne = ne;
+    auto add_slot = [&](const Need& n) {
+        Y.h_slots.push_back(hxk::PoaSlot{T.no, T.eo, T.ho, T.dro, T.wo, T.so, T.sto, T.ao, T.clo});
+        T.no += n.nn; T.eo += n.ec; T.ho += n.hc; T.dro += n.dc; T.wo += n.wc; T.so += n.lm; T.sto += n.st; T.ao += n.al; T.clo += n.mb;
+        Y.bytes += need_bytes(n);
+    };
+    for (Cls& q : classes) {
+        q.slot_at = Y.h_slots.size();
+        for (size_t k = 0; k < q.n_slots; k++) {
+            if (!q.persistent) P.edges[q.edges[k]].slot = (uint32_t)Y.h_slots.size();   // one workgroup (or cluster) per edge: the edge's own slot
+            add_slot(slot_need(q, k));
+        }
+        for (uint32_t e : q.edges) {
+            P.edges[e].cns_off = T.co; T.co += P.edges[e].vcap;
+            if (q.shared) { P.edges[e].cl_off = T.clo; T.clo += cluster_words(e); }
+            Y.bytes += edge_out_bytes(e, q.shared);
+        }
+    }
+    Y.at = Y.off.place(T);   // the pools of the batch in the arena
+    return 0;
+}
+
+static size_t edges_of(const std::vector<Cls>& classes) { size_t n = 0; for (const Cls& q : classes) n += q.edges.size(); return n; }
+
+void PoaPlanner::layout_order(BatchLayout& Y) const {
+    std::vector<Cls>& classes = Y.classes;
+    Y.order_all.reserve(edges_of(classes));   // (what it holds at least)
+    for (Cls& q : classes) {
+        q.order_at = Y.order_all.size();
+        if (q.shared) {
+            // Workgroups are handed to the 8 XCDs round-robin by index: put the members of one edge 8 indices apart so that they share an
+            // XCD (one L2 for the carries, the handshakes and the direction bytes member 0 walks back over). Holes are no-op workgroups.
+            for (size_t g0 = 0; g0 < q.edges.size(); g0 += 8) {
+                const size_t g1 = std::min(q.edges.size(), g0 + 8);
+                uint32_t gmax = 0;
+                for (size_t j = g0; j < g1; j++) gmax = std::max(gmax, P.edges[q.edges[j]].members);
+                for (uint32_t m = 0; m < gmax; m++)
+                    for (size_t j = g0; j < g0 + 8; j++)
+                        Y.order_all.push_back(j < g1 && m < P.edges[q.edges[j]].members ? (q.edges[j] | (m << 24)) : 0x00ffffffu);
+            }
+        } else
+            for (uint32_t e : q.edges) Y.order_all.push_back(e);
+        q.blocks = q.shared ? Y.order_all.size() - q.order_at : q.n_slots;   // (not shared: one workgroup per slot - per edge unless persistent)
+    }
+}
+
+void PoaPlanner::layout_launches(BatchLayout& Y) const {
+    const std::vector<Cls>& classes = Y.classes;
+    const size_t n_edges = edges_of(classes);
+    Y.h_btab.reserve(n_edges + 4 * classes.size()); Y.shapes.reserve(n_edges);   // (what they hold at most / exactly)
+    // ---- the launch groups. Persistent classes that differ only in their need bucket (build_classes) leave in ONE launch: their slots, lists and counters
+    // lie side by side in class order (largest need first), `btab` tells a workgroup which bucket its slot belongs to (kernels/poa.hip k_poa).
+    for (size_t i = 0; i < classes.size();) {
+        size_t j = i + 1;
+        const Cls& a = classes[i];
+        while (j < classes.size() && same_instance(a, classes[j])) j++;
+        Y.groups.push_back({i, j, Y.h_btab.size()});
+        if (a.persistent) {
+            Y.h_btab.push_back((uint32_t)(j - i) | (o.poa_own_bucket_first ? 1u << 16 : 0u));
+            uint32_t se = 0, ib = 0;
+            for (size_t k = i; k < j; k++) { se += (uint32_t)classes[k].blocks; Y.h_btab.push_back(se); }
+            for (size_t k = i; k < j; k++) { Y.h_btab.push_back(ib); ib += (uint32_t)classes[k].edges.size(); }
+            Y.h_btab.push_back(ib);
+            for (size_t k = i; k < j; k++) for (uint32_t e : classes[k].edges) Y.h_btab.push_back((uint32_t)std::min(4.0e9, (double)chain_ms[e] * 1000.0));   // est[]: microseconds
+        }
+        i = j;
+    }
+    // ---- the launches
+    const size_t n_streams = (size_t)std::min(8, std::max(1, o.poa_streams));   // (8: a stream per launch class of a 140 Mb call - with 6, the two one-wave classes waited 130 / 300 ms behind the shared edges)
+    size_t wg_total = 0;
+    for (const Cls& q : classes) wg_total += q.blocks;
+    Y.launches.resize(Y.groups.size());
+    for (size_t gi = 0; gi < Y.groups.size(); gi++) {
+        const auto& grp = Y.groups[gi];
+        const size_t ci = grp[0];
+        const Cls& q = classes[ci];
+        size_t g_blocks = 0, g_items = 0;
+        for (size_t k = grp[0]; k < grp[1]; k++) { g_blocks += classes[k].blocks; g_items += classes[k].edges.size(); }
+        PoaLaunchRec& rec = Y.launches[gi];
+        rec.stream = (int)(gi % n_streams);
+        // LDS of the launch: the ring its row width allows, a power of two of kept rows
+        uint64_t ring_need = 0;
+        const uint32_t dp_nt = q.dpl ? q.dpl : q.nt;   // lanes in the DP
+        rec.R = ring_rows_of(dp_nt, q.cm, ring_need);
+        // few edges: ask for enough LDS per workgroup that the dispatcher cannot stack them on a handful of CUs while others idle
+        // (a lone wave runs at twice the speed of two waves sharing a SIMD); many edges: request only what the ring needs
+        rec.lds_bytes = ring_need;
+        {
+            const uint64_t per_cu = (wg_total + 255) / 256;
+            if (per_cu < 8) rec.lds_bytes = std::max<uint64_t>(rec.lds_bytes, std::min<uint64_t>(kPoaLdsMax, (158 * 1024) / per_cu - 18 * 1024));
+            // hundreds of edges: the longest ones set the duration, and their waves run faster with two neighbours on a SIMD than with
+            // three - 10 KB of LDS per wave keeps a CU at 12 waves (thousands of edges: 16, the ring alone is 8.3 KB per wave)
+            if (!many_edges) rec.lds_bytes = std::max<uint64_t>(rec.lds_bytes, std::min<uint64_t>(kPoaLdsMax, 10 * 1024 * (uint64_t)(dp_nt / 64)));
+            if (o.poa_ring_zero) rec.lds_bytes = ring_need;   // (one row's worth: the kernel then finds room for no kept row either)
+        }
+        const int dcls = q.shared ? 0 : q.nt >= 1024 ? 1 : q.nt >= 512 ? 2 : q.nt >= 256 ? 3 : q.nt >= 128 ? 4 : 5;
+        rec.code = dcls + (q.dir ? 0 : 5);
+        for (size_t k = grp[0]; k < grp[1]; k++)
+            for (uint32_t e : classes[k].edges) Y.shapes.push_back({e, (uint32_t)rec.code, q.nt | std::min<uint32_t>(255, P.edges[e].passes) << 16 | std::min<uint32_t>(255, P.edges[e].members) << 24});
+        rec.shapes_end = Y.shapes.size();
+        rec.persistent = q.persistent;
+        rec.order_at = q.order_at; rec.slot_at = q.persistent ? q.slot_at : 0; rec.counter_at = ci; rec.btab_at = grp[2];
+        hxk::PoaLaunch& L = rec.L;
+        L.n_items = q.persistent ? (uint32_t)g_items : (uint32_t)q.blocks; L.n_blocks = (uint32_t)g_blocks;
+        L.match = pp->match; L.mismatch = pp->mismatch; L.gap = pp->gap;
+        L.block_threads = (int)q.nt; L.cm = (int)q.cm; L.poll_limit = (uint32_t)o.poa_poll_limit; L.ring_bytes = (uint32_t)rec.lds_bytes;
+        L.use_dir = q.dir; L.max_indeg = (uint32_t)std::min(16, std::max(1, o.poa_max_indeg)); L.dp_lanes = q.dpl;
+        // a 1024-lane workgroup needs an EMPTY CU: give the dispatcher a head start before the other launches fill the chip with small
+        // workgroups (once they have, a CU only empties when its longest resident workgroup ends)
+        const bool wide_q = q.dpl || (balanced && q.nt >= balance_nt && q.nt >= 512 && q.persistent), shared_first = many_edges && q.shared && (o.poa_resident_first & 1);
+        if (((wide_q && (o.poa_resident_first & 2)) || shared_first) && gi < 16) rec.started_at = (int)gi;
+        rec.wait = !(wide_q || shared_first) ? PoaLaunchRec::kNoWait : rec.started_at >= 0 ? PoaLaunchRec::kWaitStarted : PoaLaunchRec::kWaitDelay;
+        L.prune_pct = launch_pruned(q) ? (std::min<uint32_t>(q.shared ? prune_shared_pct : prune_pct, 1000u) | (o.poa_prune_lazy ? 1u << 16 : 0u)) : 0u;
+    }
 }
 
 // ---- plan, part 4: batches and slot counts against the budget
