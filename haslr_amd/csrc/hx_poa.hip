@@ -325,9 +325,7 @@ extern "C" int hx_poa_sequences(hx_ctx* c, uint32_t n_sets, const uint64_t* set_
     std::vector<uint8_t> packed(std::max<uint64_t>(4, off[nseq]), 0);
     for (uint64_t i = 0; i < nseq; i++)
         for (uint32_t j = 0; j < len[i]; j++) {
-            const char ch = bases[seq_off[i] + j];
-            const uint8_t code = ch == 'C' || ch == 'c' ? 1 : ch == 'G' || ch == 'g' ? 2 : ch == 'T' || ch == 't' ? 3 : 0;
-            packed[off[i] + (j >> 2)] |= (uint8_t)(code << ((j & 3) * 2));
+            packed[off[i] + (j >> 2)] |= (uint8_t)(hxk::base_code(bases[seq_off[i] + j]) << ((j & 3) * 2));
         }
     DV<uint8_t> d_packed; DV<uint64_t> d_off; DV<uint32_t> d_len;
     if (up(d_packed, packed.data(), packed.size()) || up(d_off, off.data(), off.size()) || up(d_len, len.data(), std::max<size_t>(1, len.size()))) return -1;
@@ -362,7 +360,7 @@ static int poa_general_run(hx_ctx* c, const char* tag, hxk::PoaModesArgs& a, hxk
         if (a.weighted) snprintf(part, sizeof part, " (coverage %.3f ms)", o.cov_ms);
         if (a.strand) snprintf(part, sizeof part, " (%llu of %llu sequences reversed)", (unsigned long long)o.third_passes, (unsigned long long)o.n_aligned);
         if (a.graph) { snprintf(rows, sizeof rows, "%zu nodes, %zu edges, %zu pairs, ", o.node_base.size(), o.edge_w.size(), o.aln_pos.size()); snprintf(part, sizeof part, " (gather %.3f ms, %u sets rerun for their alignments)", o.gather_ms, o.aln_retried); }
-        fprintf(stderr, "[hx] POA %s call%s: %u sets, %.3g cells, %skernels %.2f ms%s, %u sets rerun in a larger slot\n", tag, a.gap_model == 2 ? " (convex)" : a.gap_model == 1 ? " (affine)" : "", a.n_sets, (double)o.cells, rows, o.kernel_ms, part, o.retried);
+        fprintf(stderr, "[hx] POA %s call%s: %u sets, %.3g cells, %skernels %.2f ms%s, %u sets rerun in a larger slot\n", tag, hxk::gap_model_label(a.gap_model), a.n_sets, (double)o.cells, rows, o.kernel_ms, part, o.retried);
     }
     return 0;
 }
@@ -415,6 +413,12 @@ static int check_convex_call(const std::string& who, const hx_poa_convex_params&
 // unless option poa_convex keeps it on the convex kernel (the cross-check of that kernel against the affine one)
 static bool convex_is_affine(const hx_ctx* c, const hx_poa_convex_params& p) { return p.gap_extend2 <= p.gap_extend && !c->opt.poa_convex; }
 static GapScores convex_scores(const hx_poa_convex_params& p) { return GapScores{p.match, p.mismatch, p.gap_open, p.gap_extend, p.gap_open2, p.gap_extend2, p.type, 2}; }
+// the scores of hx_poa_graph and hx_poa_strand, which have the convex entries' parameters only: when the second piece never wins, the call takes the affine route
+static GapScores convex_or_affine_scores(const hx_ctx* c, const hx_poa_convex_params& p) {
+    GapScores sc = convex_scores(p);
+    if (convex_is_affine(c, p)) { sc.open2 = sc.extend2 = 0; sc.model = p.gap_extend != p.gap_open || c->opt.poa_affine; }
+    return sc;
+}
 
 extern "C" int hx_poa_sequences_affine(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_affine_params* ap, hx_cns_out* out) {
     memset(out, 0, sizeof(*out));
@@ -535,9 +539,7 @@ extern "C" int hx_poa_graph(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off,
     if (!cp) return fail("hx_poa_graph: no parameters");
     if (check_convex_call("hx_poa_graph", *cp, set_off[n_sets])) return -1;
     if (check_weights("hx_poa_graph", n_sets, set_off, seq_off, weights)) return -1;
-    GapScores sc = convex_scores(*cp);
-    if (convex_is_affine(c, *cp)) { sc.open2 = sc.extend2 = 0; sc.model = cp->gap_extend != cp->gap_open || c->opt.poa_affine; }   // the second piece never wins: the call takes the affine route
-    hxk::PoaModesArgs a = general_args("hx_poa_graph", n_sets, set_off, seq_off, bases, sc);
+    hxk::PoaModesArgs a = general_args("hx_poa_graph", n_sets, set_off, seq_off, bases, convex_or_affine_scores(c, *cp));
     a.graph = 1; a.weights = weights;
     hxk::PoaModesOut o;
     if (poa_general_run(c, "graph", a, o)) return -1;
@@ -566,9 +568,7 @@ extern "C" int hx_poa_strand(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off
     if (!cp || !want) return fail("hx_poa_strand: no parameters");
     if (check_convex_call("hx_poa_strand", *cp, set_off[n_sets])) return -1;
     if (check_weights("hx_poa_strand", n_sets, set_off, seq_off, weights)) return -1;
-    GapScores sc = convex_scores(*cp);
-    if (convex_is_affine(c, *cp)) { sc.open2 = sc.extend2 = 0; sc.model = cp->gap_extend != cp->gap_open || c->opt.poa_affine; }   // the second piece never wins: the call takes the affine route
-    hxk::PoaModesArgs a = general_args("hx_poa_strand", n_sets, set_off, seq_off, bases, sc);
+    hxk::PoaModesArgs a = general_args("hx_poa_strand", n_sets, set_off, seq_off, bases, convex_or_affine_scores(c, *cp));
     a.strand = 1; a.weights = weights;
     a.msa = want->want_msa != 0; a.include_consensus = a.msa && want->include_consensus != 0;
     a.want_coverage = want->want_coverage != 0; a.want_profile = want->want_profile != 0;

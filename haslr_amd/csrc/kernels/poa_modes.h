@@ -17,6 +17,11 @@ struct PoaModesWs {   // the path's workspace: one device allocation, grows to t
     ~PoaModesWs() { release(); }
 };
 
+// a base as the POA kernels take it: A 0, C 1, G 2, T 3 in either case, anything else A
+inline uint8_t base_code(char c) { return c == 'C' || c == 'c' ? 1 : c == 'G' || c == 'g' ? 2 : c == 'T' || c == 't' ? 3 : 0; }
+// what the debug lines call a gap model (PoaModesArgs::gap_model)
+inline const char* gap_model_label(int gm) { return gm == 2 ? " (convex)" : gm == 1 ? " (affine)" : ""; }
+
 struct PoaModesArgs {
     const char* who = "";                // the entry point of the C-ABI that asks: the name every error text begins with
     uint32_t n_sets = 0;

@@ -5,7 +5,8 @@ in one process:
       0-300-base flanks on both sides of every copy, and as kNW / kOV without them
   (b) tiled fragments: 20 fragments of 1-3 kb drawn at random from 5 kb templates (same error model), kOV
 For every mode: sets, cells (sum of V x L, the full matrices spoa computes), kernel time (hipEvents; warmed up, median and spread of
---repeats runs), GCUPS; for context the tuned kNW path on the same sets, and the CPU restatement (tests/poa_modes_ref.cpp) on 16 threads over
+--repeats runs), GCUPS; for the general path, the MSA, the weighted, the graph and the strand calls also the wall time of the whole call
+on the host (wall_ms_*: what the host side of the path adds shows there and nowhere in the kernel time); for context the tuned kNW path on the same sets, and the CPU restatement (tests/poa_modes_ref.cpp) on 16 threads over
 a sample of the sets (GCUPS of the sample). Every row also runs the affine kernel on the same sets (hx_poa_sequences_affine with
 --affine-scores, default 5 -4 -8 -6): same figures, the affine / linear ratio of the median kernel times, and the sample compared with the
 affine restatement (tests/poa_affine_ref.cpp). And every row asks for the multiple sequence alignment of the same sets (hx_poa_msa, linear
@@ -96,13 +97,20 @@ def note(*what):
 
 
 def gpu_time(ctx, fn, repeats):
+    """kernel time (device events) and wall time of the whole call on the host, per repeat"""
     fn()   # warm-up (workspace allocation, code objects)
-    ms = []
+    ms, wall = [], []
     for _ in range(repeats):
         ctx.timing_reset()
+        t0 = time.perf_counter()
         fn()
+        wall.append((time.perf_counter() - t0) * 1e3)
         ms.append(ctx.timing()["poa"]["ms"])
-    return ms
+    return ms, wall
+
+
+def wall_stats(wall):
+    return {"wall_ms_median": round(float(np.median(wall)), 2), "wall_ms_min": round(min(wall), 2), "wall_ms_max": round(max(wall), 2)}
 
 
 def main():
@@ -156,10 +164,12 @@ def main():
                     continue
                 with ctx.options(**opts):
                     cells = ctx.poa_sequences_mode(sets, mode, stats=True)[1]["dp_cells"]
-                    ms = gpu_time(ctx, lambda: ctx.poa_sequences_mode(sets, mode), a.repeats)
+                    ms, wall = gpu_time(ctx, lambda: ctx.poa_sequences_mode(sets, mode), a.repeats)
                 med = float(np.median(ms))
                 r[path] = {"cells": int(cells), "kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
                            "gcups": round(cells / med / 1e6, 2)}
+                if path == "general":
+                    r[path].update(wall_stats(wall))
                 note(name, path, r[path]["kernel_ms_median"], "ms")
             sample = sets[:a.cpu_sample]
             if "cpu" in only:
@@ -173,7 +183,7 @@ def main():
                 r["sample_equal"] = got == [c for c, _ in out]
             if "affine" in only:
                 cells = ctx.poa_sequences_affine(sets, mode, *a.affine_scores, stats=True)[1]["dp_cells"]
-                ms = gpu_time(ctx, lambda: ctx.poa_sequences_affine(sets, mode, *a.affine_scores), a.repeats)
+                ms, _ = gpu_time(ctx, lambda: ctx.poa_sequences_affine(sets, mode, *a.affine_scores), a.repeats)
                 med = float(np.median(ms))
                 r["affine"] = {"cells": int(cells), "kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
                                "gcups": round(cells / med / 1e6, 2)}
@@ -185,7 +195,7 @@ def main():
                 note(name, "affine", r["affine"]["kernel_ms_median"], "ms")
             if "convex" in only:
                 cells = ctx.poa_sequences_convex(sets, mode, *a.convex_scores, stats=True)[1]["dp_cells"]
-                ms = gpu_time(ctx, lambda: ctx.poa_sequences_convex(sets, mode, *a.convex_scores), a.repeats)
+                ms, _ = gpu_time(ctx, lambda: ctx.poa_sequences_convex(sets, mode, *a.convex_scores), a.repeats)
                 med = float(np.median(ms))
                 r["convex"] = {"cells": int(cells), "kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
                                "gcups": round(cells / med / 1e6, 2)}
@@ -209,7 +219,7 @@ def main():
                 st = ctx.poa_msa(sets, mode, include_consensus=True, stats=True)[2]
                 rows_ms.append(st["rows_kernel_ms"])
                 moved = st["rows_kernel_bytes"]
-            ms = gpu_time(ctx, msa_call, a.repeats)
+            ms, wall = gpu_time(ctx, msa_call, a.repeats)
             med, gen = float(np.median(ms)), r["general"]
             rmed = float(np.median(rows_ms[1:]))
             r["msa"] = {"kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
@@ -217,6 +227,7 @@ def main():
                         "over_general_max": round(max(ms) / gen["kernel_ms_min"], 4),
                         "rows_kernel": {"ms_median": round(rmed, 4), "ms_min": round(min(rows_ms[1:]), 4), "ms_max": round(max(rows_ms[1:]), 4),
                                         "bytes": int(moved), "gb_per_s": round(moved / rmed / 1e6, 1)}}
+            r["msa"].update(wall_stats(wall))
             with ThreadPoolExecutor(16) as ex:
                 out = list(ex.map(lambda st: mref.rows(st, mode, include_consensus=True), sample))
             r["msa_sample_equal"] = ctx.poa_msa(sample, mode, include_consensus=True) == out
@@ -228,7 +239,7 @@ def main():
                 st = ctx.poa_weighted(sets, wts, type=mode, coverage=True, profile=True, stats=True)[3]
                 cov_ms.append(st["cov_kernel_ms"])
                 moved = st["cov_kernel_bytes"]
-            ms = gpu_time(ctx, weighted_call, a.repeats)
+            ms, wall = gpu_time(ctx, weighted_call, a.repeats)
             med = float(np.median(ms))
             cmed = float(np.median(cov_ms[1:]))
             r["weighted"] = {"kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
@@ -236,6 +247,7 @@ def main():
                              "over_general_max": round(max(ms) / gen["kernel_ms_min"], 4),
                              "coverage_kernels": {"ms_median": round(cmed, 4), "ms_min": round(min(cov_ms[1:]), 4), "ms_max": round(max(cov_ms[1:]), 4),
                                                   "bytes": int(moved), "gb_per_s": round(moved / cmed / 1e6, 1)}}
+            r["weighted"].update(wall_stats(wall))
             swts = [[w.tolist() for w in ws] for ws in wts[:a.cpu_sample]]
             with ThreadPoolExecutor(16) as ex:
                 out = list(ex.map(lambda k: wref.weighted(sample[k], swts[k], mode), range(len(sample))))
@@ -250,7 +262,7 @@ def main():
                     nonlocal gst
                     gst = ctx.poa_graph(sets, mode, stats=True)[1]
                     gath_ms.append(gst["gather_kernel_ms"])
-                ms = gpu_time(ctx, graph_call, a.repeats)
+                ms, wall = gpu_time(ctx, graph_call, a.repeats)
                 med, gmed, msa = float(np.median(ms)), float(np.median(gath_ms[1:])), r["msa"]
                 r["graph"] = {"kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
                               "over_msa": round(med / msa["kernel_ms_median"], 4), "over_msa_min": round(min(ms) / msa["kernel_ms_max"], 4), "over_msa_max": round(max(ms) / msa["kernel_ms_min"], 4),
@@ -258,6 +270,7 @@ def main():
                               "gather_kernel": {"ms_median": round(gmed, 4), "ms_min": round(min(gath_ms[1:]), 4), "ms_max": round(max(gath_ms[1:]), 4),
                                                 "bytes": int(gst["gather_kernel_bytes"]), "gb_per_s": round(gst["gather_kernel_bytes"] / gmed / 1e6, 1)},
                               "aln_reruns": int(gst["aln_reruns"]), "slot_reruns": int(gst["slot_reruns"])}
+                r["graph"].update(wall_stats(wall))
                 gref = grflib.GraphRef(d)
                 with ThreadPoolExecutor(16) as ex:
                     out = list(ex.map(lambda st: gref.graph(st, mode), sample))
@@ -272,12 +285,13 @@ def main():
                 def strand_call():
                     nonlocal sst
                     sst = ctx.poa_strand(mixed, mode, msa=True, include_consensus=True, stats=True)[1]
-                ms = gpu_time(ctx, strand_call, a.repeats)
+                ms, wall = gpu_time(ctx, strand_call, a.repeats)
                 med, msa = float(np.median(ms)), r["msa"]
                 r["strand"] = {"kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2),
                                "over_msa": round(med / msa["kernel_ms_median"], 4), "over_msa_min": round(min(ms) / msa["kernel_ms_max"], 4), "over_msa_max": round(max(ms) / msa["kernel_ms_min"], 4),
                                "third_passes": int(sst["third_passes"]), "n_aligned": int(sst["n_aligned"]), "dp_cells": int(sst["dp_cells"]),
                                "dp_passes_per_sequence": round(2 + sst["third_passes"] / max(1, sst["n_aligned"] - len(sets)), 4), "slot_reruns": int(sst["slot_reruns"])}
+                r["strand"].update(wall_stats(wall))
                 sref = strlib.StrandRef(d)
                 few = mixed[:max(1, a.cpu_sample // 4)]   # (the restatement aligns every sequence twice, on full matrices)
                 with ThreadPoolExecutor(16) as ex:
