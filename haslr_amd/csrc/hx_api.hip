@@ -102,7 +102,20 @@ extern "C" void hx_ctx_destroy(hx_ctx* c) {
     delete c;
 }
 
-static int upload_inputs(hx_ctx* c, const hx_contigs* ctg, const hx_reads* rd, const hx_hits* h, const uint64_t* rho);
+static int upload_inputs(hx_ctx* c, const hx_contigs* ctg, const hx_reads* rd, const hx_hits* h, const uint64_t* rho) {
+    HIPCHK(hipSetDevice(c->device));
+    c->n_contigs = ctg->n; c->n_reads = rd->n; c->n_hits = h->n; c->n_ops = h->cg_off[h->n];
+    if (up(c->km, ctg->mean_kmer, ctg->n) || up(c->clen, ctg->len, ctg->n)) return -1;
+    HIPCHK(c->cls.reserve(ctg->n));
+    if (up(c->rlen, rd->len, rd->n) || up(c->roff, rd->off, (size_t)rd->n + 1) || up(c->packed, rd->packed, (size_t)rd->off[rd->n])) return -1;
+    if (c->hits.upload(h, c->n_ops) || up(c->rho, rho, (size_t)rd->n + 1)) return -1;
+    c->h_rlen.assign(rd->len, rd->len + rd->n);
+    c->h_rho.assign(rho, rho + rd->n + 1);
+    c->lr_begin = 0; c->lr_end = rd->n;
+    c->prefiltered = false;
+    c->have_chain = c->have_edges = c->have_coords = false;
+    return 0;
+}
 extern "C" int hx_upload(hx_ctx* c, const hx_contigs* ctg, const hx_reads* rd, const hx_hits* h, const uint64_t* rho) {
     if (upload_inputs(c, ctg, rd, h, rho) == 0) return 0;
     // a consensus arena reserved ahead of the inputs (hx_poa_reserve) must never be what keeps them out: give it back and try once more
@@ -114,24 +127,6 @@ extern "C" int hx_upload(hx_ctx* c, const hx_contigs* ctg, const hx_reads* rd, c
     }
     return upload_inputs(c, ctg, rd, h, rho);
 }
-static int upload_inputs(hx_ctx* c, const hx_contigs* ctg, const hx_reads* rd, const hx_hits* h, const uint64_t* rho) {
-    HIPCHK(hipSetDevice(c->device));
-    c->n_contigs = ctg->n; c->n_reads = rd->n; c->n_hits = h->n; c->n_ops = h->cg_off[h->n];
-    if (up(c->km, ctg->mean_kmer, ctg->n) || up(c->clen, ctg->len, ctg->n)) return -1;
-    HIPCHK(c->cls.reserve(ctg->n));
-    if (up(c->rlen, rd->len, rd->n) || up(c->roff, rd->off, (size_t)rd->n + 1) || up(c->packed, rd->packed, (size_t)rd->off[rd->n])) return -1;
-    size_t n = h->n;
-    if (up(c->q_id, h->q_id, n) || up(c->q_start, h->q_start, n) || up(c->q_end, h->q_end, n) || up(c->t_id, h->t_id, n) || up(c->t_len, h->t_len, n) ||
-        up(c->t_start, h->t_start, n) || up(c->t_end, h->t_end, n) || up(c->n_match, h->n_match, n) || up(c->n_block, h->n_block, n) ||
-        up(c->is_rev, h->is_rev, n) || up(c->mapq, h->mapq, n) || up(c->cg_off, h->cg_off, n + 1) || up(c->cg_ops, h->cg_ops, (size_t)c->n_ops) ||
-        up(c->rho, rho, (size_t)rd->n + 1)) return -1;
-    c->h_rlen.assign(rd->len, rd->len + rd->n);
-    c->h_rho.assign(rho, rho + rd->n + 1);
-    c->lr_begin = 0; c->lr_end = rd->n;
-    c->prefiltered = false;
-    c->have_chain = c->have_edges = c->have_coords = false;
-    return 0;
-}
 
 extern "C" void hx_set_prefiltered(hx_ctx* c, int on) { c->prefiltered = on != 0; }
 
@@ -140,7 +135,6 @@ static std::string opt_key(const char* name) {
     std::string k(name ? name : "");
     for (char& ch : k) ch = (char)tolower((unsigned char)ch);
     if (k.rfind("hx_", 0) == 0) k = k.substr(3);
-    if (k == "prof1" || k == "prof2" || k == "prof3") return k;
     return k;
 }
 extern "C" int hx_set_option(hx_ctx* c, const char* name, const char* value) {
@@ -193,6 +187,11 @@ static int check_err(hx_ctx* c, const char* who) {
     return fail(m);
 }
 
+// the end of an operator's download. A result array that could not be allocated or downloaded: the out-struct comes back freed and zeroed, the device side stays as it is
+template <class O> static int downloaded(bool ok, hx_ctx* c, O* out, void (*release)(hx_ctx*, O*), const char* who) {
+    return ok ? 0 : (release(c, out), fail(std::string(who) + ": a result array could not be allocated or downloaded"));
+}
+
 // ================================================================================================ K1-K3
 extern "C" int hx_chain_reads(hx_ctx* c, const hx_params* prm, hx_chain_out* out) {
     memset(out, 0, sizeof(*out));
@@ -202,54 +201,35 @@ extern "C" int hx_chain_reads(hx_ctx* c, const hx_params* prm, hx_chain_out* out
     hipStream_t s = c->stream;
     HIPCHK(hipMemsetAsync(c->err.p, 0, 4, s));
     const double thr_load = prm->uniq_freq * (3 + prm->max_uniq_dev), thr_uniq = prm->uniq_freq * (1 + prm->max_uniq_dev);
-    // scratch at raw-hit granularity
-    auto& S = c->sc_chain;
-    DV<uint32_t>&s_hit = S.hit, &s_qs = S.qs, &s_qe = S.qe, &s_ts = S.ts, &s_te = S.te, &s_nm = S.nm, &s_nb = S.nb, &s_skf = S.skf, &s_skb = S.skb, &s_dp = S.dp, &s_cmp = S.cmp,
-                &s_naln = S.naln, &s_ncmp = S.ncmp;
-    DV<uint64_t>&s_cb = S.cb, &s_ce = S.ce;
-    DV<int32_t>& s_from = S.from;
+    auto& S = c->sc_chain; auto& C = c->chain;   // the scratch at raw-hit granularity, the result
     c->ws.reset(s);
-    HIPCHK(s_hit.reserve(nraw)); HIPCHK(s_qs.reserve(nraw)); HIPCHK(s_qe.reserve(nraw)); HIPCHK(s_ts.reserve(nraw)); HIPCHK(s_te.reserve(nraw));
-    HIPCHK(s_nm.reserve(nraw)); HIPCHK(s_nb.reserve(nraw)); HIPCHK(s_skf.reserve(nraw)); HIPCHK(s_skb.reserve(nraw)); HIPCHK(s_dp.reserve(nraw));
-    HIPCHK(s_cmp.reserve(nraw)); HIPCHK(s_cb.reserve(nraw)); HIPCHK(s_ce.reserve(nraw)); HIPCHK(s_from.reserve(nraw));
-    HIPCHK(s_naln.reserve(nr)); HIPCHK(s_ncmp.reserve(nr));
-    hxk::ChainScratch sc{s_hit.p, s_qs.p, s_qe.p, s_ts.p, s_te.p, s_nm.p, s_nb.p, s_skf.p, s_skb.p, s_cb.p, s_ce.p, s_dp.p, s_from.p, s_cmp.p, s_naln.p, s_ncmp.p};
-    HIPCHK(c->aln_off.reserve((size_t)nr + 1)); HIPCHK(c->cmp_off.reserve((size_t)nr + 1));
+    HIPCHK(S.raw.reserve(nraw)); HIPCHK(S.dp.reserve(nraw)); HIPCHK(S.cmp.reserve(nraw)); HIPCHK(S.from.reserve(nraw));
+    HIPCHK(S.naln.reserve(nr)); HIPCHK(S.ncmp.reserve(nr)); HIPCHK(C.aln_off.reserve((size_t)nr + 1)); HIPCHK(C.cmp_off.reserve((size_t)nr + 1));
+    hxk::ChainScratch sc{}; S.raw.fill(sc); sc.dp = S.dp.p; sc.from = S.from.p; sc.cmp = S.cmp.p; sc.n_aln = S.naln.p; sc.n_cmp = S.ncmp.p;
     c->tick();
     hxk::contig_class(c->km.p, c->n_contigs, thr_load, thr_uniq, c->cls.p, s);
     hxk::chain_reads(c->hits_view(), c->rho.p, c->cls.p, c->n_contigs, c->lr_begin, c->lr_end, prm->min_aln_block, prm->min_aln_sim, prm->min_aln_mapq, sc, c->err.p, c->prefiltered, s);
-    hxk::exclusive_scan_u32(s_naln.p, c->aln_off.p, nr, s, c->ws);
-    hxk::exclusive_scan_u32(s_ncmp.p, c->cmp_off.p, nr, s, c->ws);
+    hxk::exclusive_scan_u32(S.naln.p, C.aln_off.p, nr, s, c->ws);
+    hxk::exclusive_scan_u32(S.ncmp.p, C.cmp_off.p, nr, s, c->ws);
     if (ws_ok(c, "hx_chain_reads")) return -1;
     uint64_t tot[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(&tot[0], c->aln_off.p + nr, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&tot[1], c->cmp_off.p + nr, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&tot[0], C.aln_off.p + nr, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&tot[1], C.cmp_off.p + nr, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    c->n_aln = tot[0]; c->n_cmp = tot[1];
-    if (c->n_aln >= 0xffffffffULL) return fail("hx_chain_reads: more than 2^32-1 alignments in one shard");
-    HIPCHK(c->c_hit.reserve(c->n_aln)); HIPCHK(c->c_qs.reserve(c->n_aln)); HIPCHK(c->c_qe.reserve(c->n_aln)); HIPCHK(c->c_ts.reserve(c->n_aln));
-    HIPCHK(c->c_te.reserve(c->n_aln)); HIPCHK(c->c_nm.reserve(c->n_aln)); HIPCHK(c->c_nb.reserve(c->n_aln)); HIPCHK(c->c_skf.reserve(c->n_aln));
-    HIPCHK(c->c_skb.reserve(c->n_aln)); HIPCHK(c->c_cb.reserve(c->n_aln)); HIPCHK(c->c_ce.reserve(c->n_aln)); HIPCHK(c->c_cmp.reserve(c->n_cmp));
-    hxk::chain_compact(sc, c->rho.p, c->lr_begin, c->lr_end, c->aln_off.p, c->cmp_off.p, c->chain_view(), s);
+    const uint64_t n_aln = C.n_aln = tot[0], n_cmp = C.n_cmp = tot[1];
+    if (n_aln >= 0xffffffffULL) return fail("hx_chain_reads: more than 2^32-1 alignments in one shard");
+    HIPCHK(C.col.reserve(n_aln)); HIPCHK(C.cmp_aln.reserve(n_cmp));
+    hxk::chain_compact(sc, c->rho.p, c->lr_begin, c->lr_end, C.aln_off.p, C.cmp_off.p, c->chain_view(), s);
     c->tock(0);
     HIPCHK(hipGetLastError());
     if (check_err(c, "hx_chain_reads")) return -1;
     c->have_chain = true; c->have_edges = c->have_coords = false;
-    // download
-    out->n_aln = c->n_aln; out->n_reads = nr; out->n_cmp = c->n_cmp;
-    out->hit = host_copy(c->c_hit.p, c->n_aln); out->q_start = host_copy(c->c_qs.p, c->n_aln); out->q_end = host_copy(c->c_qe.p, c->n_aln);
-    out->t_start = host_copy(c->c_ts.p, c->n_aln); out->t_end = host_copy(c->c_te.p, c->n_aln); out->n_match = host_copy(c->c_nm.p, c->n_aln);
-    out->n_block = host_copy(c->c_nb.p, c->n_aln); out->cg_begin = host_copy(c->c_cb.p, c->n_aln); out->cg_end = host_copy(c->c_ce.p, c->n_aln);
-    out->cg_skip_front = host_copy(c->c_skf.p, c->n_aln); out->cg_skip_back = host_copy(c->c_skb.p, c->n_aln);
-    out->read_off = host_copy(c->aln_off.p, (size_t)nr + 1); out->cmp_off = host_copy(c->cmp_off.p, (size_t)nr + 1); out->cmp_aln = host_copy(c->c_cmp.p, c->n_cmp);
-    return 0;
+    out->n_aln = n_aln; out->n_reads = nr; out->n_cmp = n_cmp;
+    const bool ok = C.col.download(out, n_aln) && fetch(out->read_off, C.aln_off.p, (size_t)nr + 1) && fetch(out->cmp_off, C.cmp_off.p, (size_t)nr + 1) && fetch(out->cmp_aln, C.cmp_aln.p, n_cmp);
+    return downloaded(ok, c, out, hx_free_chain, "hx_chain_reads");
 }
 
-extern "C" void hx_free_chain(hx_ctx*, hx_chain_out* o) {
-    free(o->hit); free(o->q_start); free(o->q_end); free(o->t_start); free(o->t_end); free(o->n_match); free(o->n_block);
-    free(o->cg_begin); free(o->cg_end); free(o->cg_skip_front); free(o->cg_skip_back); free(o->read_off); free(o->cmp_off); free(o->cmp_aln);
-    memset(o, 0, sizeof(*o));
-}
+extern "C" void hx_free_chain(hx_ctx*, hx_chain_out* o) { ChainCols::free_host(o); free(o->read_off); free(o->cmp_off); free(o->cmp_aln); memset(o, 0, sizeof(*o)); }
 
 // ================================================================================================ K4
 extern "C" int hx_edge_emit(hx_ctx* c, const hx_params*, uint64_t* n_records) {
@@ -257,30 +237,23 @@ extern "C" int hx_edge_emit(hx_ctx* c, const hx_params*, uint64_t* n_records) {
     HIPCHK(hipSetDevice(c->device));
     const uint32_t nr = c->lr_end - c->lr_begin;
     hipStream_t s = c->stream;
-    DV<uint32_t>& npairs = c->sc_edges.npairs;
-    DV<uint64_t>& pair_off = c->sc_edges.pair_off;
+    auto& E = c->sc_edges;
     c->ws.reset(s);
-    HIPCHK(npairs.reserve(nr)); HIPCHK(pair_off.reserve((size_t)nr + 1));
+    HIPCHK(E.npairs.reserve(nr)); HIPCHK(E.pair_off.reserve((size_t)nr + 1));
     c->tick();
-    hxk::edge_count(c->hits_view(), c->cls.p, c->chain_view(), c->cmp_off.p, c->lr_begin, c->lr_end, npairs.p, s);
-    hxk::exclusive_scan_u32(npairs.p, pair_off.p, nr, s, c->ws);
+    hxk::edge_count(c->hits_view(), c->cls.p, c->chain_view(), c->chain.cmp_off.p, c->lr_begin, c->lr_end, E.npairs.p, s);
+    hxk::exclusive_scan_u32(E.npairs.p, E.pair_off.p, nr, s, c->ws);
     if (ws_ok(c, "hx_edge_emit")) return -1;
     uint64_t tot = 0;
-    HIPCHK(hipMemcpyAsync(&tot, pair_off.p + nr, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&tot, E.pair_off.p + nr, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     c->n_rec_un = 2 * tot;
     HIPCHK(c->rec_un.reserve(c->n_rec_un));
-    hxk::edge_emit(c->hits_view(), c->cls.p, c->chain_view(), c->cmp_off.p, c->lr_begin, c->lr_end, pair_off.p, c->rec_un.view(), s);
+    hxk::edge_emit(c->hits_view(), c->cls.p, c->chain_view(), c->chain.cmp_off.p, c->lr_begin, c->lr_end, E.pair_off.p, c->rec_un.view(), s);
     c->tock(1);
     HIPCHK(hipGetLastError());
     if (n_records) *n_records = c->n_rec_un;
     return 0;
-}
-
-static void download_side(hx_rec_side& h, DevSideBuf& d, size_t n) {
-    h.q_start = host_copy(d.qs.p, n); h.q_end = host_copy(d.qe.p, n); h.t_start = host_copy(d.ts.p, n); h.t_end = host_copy(d.te.p, n);
-    h.is_rev = host_copy(d.rev.p, n); h.cg_begin = host_copy(d.cb.p, n); h.cg_end = host_copy(d.ce.p, n);
-    h.cg_skip_front = host_copy(d.skf.p, n); h.cg_skip_back = host_copy(d.skb.p, n);
 }
 
 // sort the n records sitting in rec_un by key (stable), segment into edges, download
@@ -289,47 +262,41 @@ static int finish_edges(hx_ctx* c, uint64_t n, hx_edges_out* out) {
     if (n >= 0xffffffffULL) return fail("hx_edge_support: more than 2^32-1 edge-support records");
     int bits = 1;
     while (bits < 32 && (1ull << bits) < 2ull * std::max<uint32_t>(1, c->n_contigs)) bits++;
-    DV<uint32_t>&perm = c->sc_edges.perm, &perm_tmp = c->sc_edges.perm_tmp, &flag = c->sc_edges.flag;
-    DV<uint64_t>&key_tmp = c->sc_edges.key_tmp, &fscan = c->sc_edges.fscan;
+    auto& E = c->sc_edges;
     c->ws.reset(s);
-    HIPCHK(perm.reserve(n)); HIPCHK(perm_tmp.reserve(n)); HIPCHK(flag.reserve(n)); HIPCHK(key_tmp.reserve(n)); HIPCHK(fscan.reserve(n + 1));
+    HIPCHK(E.perm.reserve(n)); HIPCHK(E.perm_tmp.reserve(n)); HIPCHK(E.flag.reserve(n)); HIPCHK(E.key_tmp.reserve(n)); HIPCHK(E.fscan.reserve(n + 1));
     HIPCHK(c->rec.reserve(n));
     c->tick();
-    hxk::iota_u32(perm.p, n, s);
+    hxk::iota_u32(E.perm.p, n, s);
     // the keys are sorted in the copy: rec_un stays the record set as it was emitted or imported, for a later hx_edge_records_export
     if (n) HIPCHK(hipMemcpyAsync(c->rec.key.p, c->rec_un.key.p, n * 8, hipMemcpyDeviceToDevice, s));
-    hxk::radix_sort_pairs(c->rec.key.p, perm.p, key_tmp.p, perm_tmp.p, n, bits, bits, s, c->ws);
-    hxk::edge_gather(c->rec_un.view(), perm.p, n, c->rec.view(), s);
-    hxk::segment_flags(c->rec.key.p, n, flag.p, s);
-    hxk::exclusive_scan_u32(flag.p, fscan.p, n, s, c->ws);
+    hxk::radix_sort_pairs(c->rec.key.p, E.perm.p, E.key_tmp.p, E.perm_tmp.p, n, bits, bits, s, c->ws);
+    hxk::edge_gather(c->rec_un.view(), E.perm.p, n, c->rec.view(), s);
+    hxk::segment_flags(c->rec.key.p, n, E.flag.p, s);
+    hxk::exclusive_scan_u32(E.flag.p, E.fscan.p, n, s, c->ws);
     if (ws_ok(c, "hx_edge_support")) return -1;
     uint64_t ne = 0;
-    HIPCHK(hipMemcpyAsync(&ne, fscan.p + n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&ne, E.fscan.p + n, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(c->edge_key.reserve(ne)); HIPCHK(c->edge_off.reserve(ne + 1));
     if (n == 0) HIPCHK(hipMemsetAsync(c->edge_off.p, 0, 8, s));
-    hxk::segment_scatter(c->rec.key.p, fscan.p, n, c->edge_key.p, c->edge_off.p, s);
+    hxk::segment_scatter(c->rec.key.p, E.fscan.p, n, c->edge_key.p, c->edge_off.p, s);
     c->tock(1);
     HIPCHK(hipGetLastError());
-    c->n_rec = n; c->n_edge = ne;
-    c->h_edge_key.resize(ne); c->h_edge_off.resize(ne + 1);
-    if (ne) HIPCHK(hipMemcpy(c->h_edge_key.data(), c->edge_key.p, ne * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(c->h_edge_off.data(), c->edge_off.p, (ne + 1) * 8, hipMemcpyDeviceToHost));
-    c->have_edges = true; c->have_coords = false;
     memset(out, 0, sizeof(*out));
-    out->n_rec = n; out->n_edge = ne;
-    out->key = host_copy(c->rec.key.p, n); out->lr = host_copy(c->rec.lr.p, n); out->cmp_head = host_copy(c->rec.ch.p, n); out->cmp_tail = host_copy(c->rec.ct.p, n);
-    download_side(out->head, c->rec.head, n); download_side(out->tail, c->rec.tail, n);
-    out->edge_key = (uint64_t*)malloc(std::max<size_t>(1, ne) * 8); memcpy(out->edge_key, c->h_edge_key.data(), ne * 8);
-    out->edge_off = (uint64_t*)malloc((ne + 1) * 8); memcpy(out->edge_off, c->h_edge_off.data(), (ne + 1) * 8);
-    return 0;
+    c->n_rec = out->n_rec = n; c->n_edge = out->n_edge = ne;
+    bool ok = fetch(out->edge_key, c->edge_key.p, ne) && fetch(out->edge_off, c->edge_off.p, ne + 1);
+    if (ok) {   // the host keeps the edges too, for hx_edge_coords
+        c->h_edge_key.assign(out->edge_key, out->edge_key + ne); c->h_edge_off.assign(out->edge_off, out->edge_off + ne + 1); c->have_edges = true; c->have_coords = false;
+        ok = c->rec.download(out, n) && c->rec.head.download(&out->head, n) && c->rec.tail.download(&out->tail, n);
+    }
+    return downloaded(ok, c, out, hx_free_edges, "hx_edge_support");
 }
 
 extern "C" int hx_edge_support(hx_ctx* c, const hx_params* prm, hx_edges_out* out) {
     memset(out, 0, sizeof(*out));
     uint64_t n = 0;
-    if (hx_edge_emit(c, prm, &n)) return -1;
-    return finish_edges(c, n, out);
+    return hx_edge_emit(c, prm, &n) ? -1 : finish_edges(c, n, out);
 }
 
 extern "C" uint32_t hx_edge_records_bytes(void) { return hxk::EDGE_REC_WORDS * 4; }
@@ -352,12 +319,8 @@ extern "C" int hx_edge_records_import(hx_ctx* c, const void* src, uint64_t n, hx
     return finish_edges(c, n, out);
 }
 
-static void free_side(hx_rec_side& s) {
-    free(s.q_start); free(s.q_end); free(s.t_start); free(s.t_end); free(s.is_rev); free(s.cg_begin); free(s.cg_end); free(s.cg_skip_front); free(s.cg_skip_back);
-}
 extern "C" void hx_free_edges(hx_ctx*, hx_edges_out* o) {
-    free(o->key); free(o->lr); free(o->cmp_head); free(o->cmp_tail); free_side(o->head); free_side(o->tail); free(o->edge_key); free(o->edge_off);
-    memset(o, 0, sizeof(*o));
+    RecCols::free_host(o); DevSideBuf::free_host(&o->head); DevSideBuf::free_host(&o->tail); free(o->edge_key); free(o->edge_off); memset(o, 0, sizeof(*o));
 }
 
 // ================================================================================================ K5
@@ -374,52 +337,32 @@ extern "C" int hx_edge_coords(hx_ctx* c, uint32_t n_sel, const uint32_t* sel, hx
         cap_off[i + 1] = cap_off[i] + (hairpin ? 2 * n : n);
     }
     const uint64_t cap = cap_off[n_sel];
-    auto& K = c->sc_coords;
-    DV<uint32_t>&d_sel = K.sel, &d_nsupp = K.nsupp, &t_lr = K.t_lr, &t_sp = K.t_sp, &t_ep = K.t_ep, &best_list = K.best_list;
-    DV<uint64_t>&d_cap = K.cap, &d_out_off = K.out_off, &b1 = K.b1, &e1 = K.e1, &b2 = K.b2, &e2 = K.e2;
-    DV<uint8_t>& cur = K.cur;
+    auto& K = c->sc_coords; auto& R = c->coords;   // the scratch, the results
     c->ws.reset(s);
-    HIPCHK(d_sel.reserve(n_sel)); HIPCHK(d_nsupp.reserve(n_sel)); HIPCHK(t_lr.reserve(cap)); HIPCHK(t_sp.reserve(cap)); HIPCHK(t_ep.reserve(cap));
-    HIPCHK(best_list.reserve(cap)); HIPCHK(d_cap.reserve((size_t)n_sel + 1)); HIPCHK(d_out_off.reserve((size_t)n_sel + 1));
-    HIPCHK(b1.reserve(cap)); HIPCHK(e1.reserve(cap)); HIPCHK(b2.reserve(cap)); HIPCHK(e2.reserve(cap)); HIPCHK(cur.reserve(cap));
-    HIPCHK(c->k_head_end.reserve(n_sel)); HIPCHK(c->k_tail_beg.reserve(n_sel));
-    if (n_sel) HIPCHK(hipMemcpyAsync(d_sel.p, sel, (size_t)n_sel * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_cap.p, cap_off.data(), ((size_t)n_sel + 1) * 8, hipMemcpyHostToDevice, s));
-    hxk::CoordsScratch sc{b1.p, e1.p, b2.p, e2.p, cur.p, nullptr, nullptr, best_list.p};
+    HIPCHK(K.reserve(n_sel, cap));
+    HIPCHK(R.edge.reserve(n_sel));
+    if (n_sel) HIPCHK(hipMemcpyAsync(K.sel.p, sel, (size_t)n_sel * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(K.cap.p, cap_off.data(), ((size_t)n_sel + 1) * 8, hipMemcpyHostToDevice, s));
+    hxk::CoordsScratch sc{}; sc.beg1 = K.b1.p; sc.end1 = K.e1.p; sc.beg2 = K.b2.p; sc.end2 = K.e2.p; sc.cur = K.cur.p; sc.best_list = K.best_list.p;
     c->tick();
-    hxk::edge_coords(c->rec.view(), c->edge_key.p, c->edge_off.p, c->cg_ops.p, c->clen.p, c->rlen.p, n_sel, d_sel.p, d_cap.p, sc,
-                     c->k_head_end.p, c->k_tail_beg.p, d_nsupp.p, t_lr.p, t_sp.p, t_ep.p, c->opt.coords_lds_supp, s);
-    hxk::exclusive_scan_u32(d_nsupp.p, d_out_off.p, n_sel, s, c->ws);
+    hxk::edge_coords(c->rec.view(), c->edge_key.p, c->edge_off.p, c->hits.cg_ops.p, c->clen.p, c->rlen.p, n_sel, K.sel.p, K.cap.p, sc,
+                     R.edge.head_end.p, R.edge.tail_beg.p, K.nsupp.p, K.t_lr.p, K.t_sp.p, K.t_ep.p, c->opt.coords_lds_supp, s);
+    hxk::exclusive_scan_u32(K.nsupp.p, K.out_off.p, n_sel, s, c->ws);
     if (ws_ok(c, "hx_edge_coords")) return -1;
     uint64_t tot = 0;
-    HIPCHK(hipMemcpyAsync(&tot, d_out_off.p + n_sel, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&tot, K.out_off.p + n_sel, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(c->k_supp_lr.reserve(tot)); HIPCHK(c->k_spos.reserve(tot)); HIPCHK(c->k_epos.reserve(tot));
-    hxk::coords_compact(d_cap.p, d_out_off.p, n_sel, t_lr.p, t_sp.p, t_ep.p, c->k_supp_lr.p, c->k_spos.p, c->k_epos.p, s);
+    HIPCHK(R.supp.reserve(tot));
+    hxk::coords_compact(K.cap.p, K.out_off.p, n_sel, K.t_lr.p, K.t_sp.p, K.t_ep.p, R.supp.supp_lr.p, R.supp.spos.p, R.supp.epos.p, s);
     c->tock(2);
     HIPCHK(hipGetLastError());
-    c->n_sel = n_sel;
-    c->h_supp_off.resize((size_t)n_sel + 1); c->h_supp_lr.resize(tot); c->h_spos.resize(tot); c->h_epos.resize(tot);
-    HIPCHK(hipMemcpy(c->h_supp_off.data(), d_out_off.p, ((size_t)n_sel + 1) * 8, hipMemcpyDeviceToHost));
-    if (tot) {
-        HIPCHK(hipMemcpy(c->h_supp_lr.data(), c->k_supp_lr.p, tot * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(c->h_spos.data(), c->k_spos.p, tot * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(c->h_epos.data(), c->k_epos.p, tot * 4, hipMemcpyDeviceToHost));
-    }
-    c->have_coords = true;
-    out->n_edge = n_sel;
-    out->head_end = host_copy(c->k_head_end.p, n_sel); out->tail_beg = host_copy(c->k_tail_beg.p, n_sel);
-    out->supp_off = (uint64_t*)malloc(((size_t)n_sel + 1) * 8); memcpy(out->supp_off, c->h_supp_off.data(), ((size_t)n_sel + 1) * 8);
-    out->supp_lr = (uint32_t*)malloc(std::max<size_t>(1, tot) * 4); memcpy(out->supp_lr, c->h_supp_lr.data(), tot * 4);
-    out->spos = (uint32_t*)malloc(std::max<size_t>(1, tot) * 4); memcpy(out->spos, c->h_spos.data(), tot * 4);
-    out->epos = (uint32_t*)malloc(std::max<size_t>(1, tot) * 4); memcpy(out->epos, c->h_epos.data(), tot * 4);
-    return 0;
+    R.n_sel = out->n_edge = n_sel;
+    bool ok = fetch(out->supp_off, K.out_off.p, (size_t)n_sel + 1) && R.supp.download(out, tot);
+    if (ok) { R.keep(out, tot); c->have_coords = true; ok = R.edge.download(out, n_sel); }   // (the host keeps the supports too, for hx_poa_batch)
+    return downloaded(ok, c, out, hx_free_coords, "hx_edge_coords");
 }
 
-extern "C" void hx_free_coords(hx_ctx*, hx_coords_out* o) {
-    free(o->head_end); free(o->tail_beg); free(o->supp_off); free(o->supp_lr); free(o->spos); free(o->epos);
-    memset(o, 0, sizeof(*o));
-}
+extern "C" void hx_free_coords(hx_ctx*, hx_coords_out* o) { CoordEdgeCols::free_host(o); CoordSuppCols::free_host(o); free(o->supp_off); memset(o, 0, sizeof(*o)); }
 
 // ================================================================================================ misc
 extern "C" void hx_timing_reset(hx_ctx* c) { for (int i = 0; i < 4; i++) { c->tm.ms[i] = 0; c->tm.launches[i] = 0; } }

@@ -1,5 +1,5 @@
 // hx_internal.h - what the units of the C-ABI share (hx_api.hip, hx_poa_plan.hip, hx_poa.hip, hx_group.hip): the error helpers, device
-// buffers, the POA workspace arena, the options of a context, the shape of its last consensus call (for hx_poa_report.cpp) and the context itself.
+// buffers (the column buffers of the chain, edge and coordinate operators generated from the lists of hx_columns.h), the POA workspace arena, the options of a context, the shape of its last consensus call (for hx_poa_report.cpp) and the context itself.
 #pragma once
 #include <atomic>
 #include <thread>
@@ -24,6 +24,7 @@
 #include "kernels/poa_modes.h"
 #include "hx_poa_report.h"
 #include "hx_poa_pools.h"
+#include "hx_columns.h"
 
 namespace hxi {
 
@@ -52,36 +53,49 @@ struct DV {   // device vector (capacity grows, never shrinks)
     ~DV() { release(); }
 };
 
-struct DevSideBuf {
-    DV<uint32_t> qs, qe, ts, te, skf, skb;
-    DV<uint8_t> rev;
-    DV<uint64_t> cb, ce;
-    hipError_t reserve(size_t n) {
-        hipError_t e;
-        if ((e = qs.reserve(n)) || (e = qe.reserve(n)) || (e = ts.reserve(n)) || (e = te.reserve(n)) || (e = skf.reserve(n)) ||
-            (e = skb.reserve(n)) || (e = rev.reserve(n)) || (e = cb.reserve(n)) || (e = ce.reserve(n))) return e;
-        return hipSuccess;
-    }
-    DevSide view() { return DevSide{qs.p, qe.p, ts.p, te.p, rev.p, cb.p, ce.p, skf.p, skb.p}; }
-};
-
-struct RecBuf {
-    DV<uint64_t> key;
-    DV<uint32_t> lr, ch, ct;
-    DevSideBuf head, tail;
-    hipError_t reserve(size_t n) {
-        hipError_t e;
-        if ((e = key.reserve(n)) || (e = lr.reserve(n)) || (e = ch.reserve(n)) || (e = ct.reserve(n)) || (e = head.reserve(n)) || (e = tail.reserve(n))) return e;
-        return hipSuccess;
-    }
-    hxk::EdgeRecs view() { return hxk::EdgeRecs{key.p, lr.p, ch.p, ct.p, head.view(), tail.view()}; }
-};
-
-template <class T> T* host_copy(const T* d, size_t n) {
-    T* h = (T*)malloc(std::max<size_t>(1, n) * sizeof(T));
-    if (n) (void)hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost);
-    return h;
+template <class T>
+int up(DV<T>& d, const T* h, size_t n) {
+    HIPCHK(d.reserve(n));
+    if (n) HIPCHK(hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
 }
+
+// A result array on the host: malloc(max(1, n)), so that an empty result still has a pointer. False when the allocation or the download fails; what
+// was allocated stays in `out` for the caller's hx_free_*.
+template <class T> bool fetch(T*& out, const T* d, size_t n) {
+    out = (T*)malloc(std::max<size_t>(1, n) * sizeof(T));
+    return out && (!n || hipMemcpy(out, d, n * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess);
+}
+
+// The buffers of a column list (hx_columns.h): one DV per entry under the kernels' name, reserved together, handed to a kernel's struct by member
+// name (fill: the struct's other members are the caller's), downloaded into and freed from a public struct by field name.
+#define HX_COLUMN_BUFS(Name, LIST) struct Name { \
+        LIST(HX_COL_BUF) \
+        hipError_t reserve(size_t n) { hipError_t e; LIST(HX_COL_RESERVE) return hipSuccess; } \
+        template <class V> void fill(V& v) const { LIST(HX_COL_VIEW) } \
+        template <class O> bool download(O* o, size_t n) const { bool ok = true; LIST(HX_COL_FETCH) return ok; } \
+        template <class O> static void free_host(O* o) { LIST(HX_COL_FREE) } \
+    }
+HX_COLUMN_BUFS(ChainCols, HX_CHAIN_COLUMNS); HX_COLUMN_BUFS(DevSideBuf, HX_SIDE_COLUMNS); HX_COLUMN_BUFS(RecCols, HX_REC_COLUMNS);
+HX_COLUMN_BUFS(CoordEdgeCols, HX_COORD_EDGE_COLUMNS); HX_COLUMN_BUFS(CoordSuppCols, HX_COORD_SUPP_COLUMNS);
+struct HitCols {   // resident raw hits, each uploaded at its own count
+    HX_HIT_COLUMNS(HX_COL_BUF)
+    int upload(const hx_hits* h, uint64_t n_ops) { const size_t n = h->n; HX_HIT_COLUMNS(HX_COL_UPLOAD) return 0; }
+    DevHits view(uint64_t n) const { DevHits v{}; v.n = n; HX_HIT_COLUMNS(HX_COL_VIEW) return v; }
+};
+struct RecBuf : RecCols {
+    DevSideBuf head, tail;
+    hipError_t reserve(size_t n) { hipError_t e; if ((e = RecCols::reserve(n)) || (e = head.reserve(n))) return e; return tail.reserve(n); }
+    hxk::EdgeRecs view() const { hxk::EdgeRecs v{}; fill(v); head.fill(v.head); tail.fill(v.tail); return v; }
+};
+struct CoordCols {   // per selected edge, and per support with the host mirrors that hx_poa_batch reads: copies of what was downloaded
+    CoordEdgeCols edge;
+    CoordSuppCols supp;
+    HX_COORD_SUPP_COLUMNS(HX_COL_MIRROR)
+    std::vector<uint64_t> h_supp_off;   // n_sel + 1: the scan of the supports kept per edge
+    uint32_t n_sel = 0;
+    void keep(const hx_coords_out* o, size_t n) { h_supp_off.assign(o->supp_off, o->supp_off + n_sel + 1); HX_COORD_SUPP_COLUMNS(HX_COL_MIRROR_KEEP) }
+};
 
 struct Timer {
     hipEvent_t a = nullptr, b = nullptr;
@@ -162,13 +176,6 @@ struct PoaCallShape {
     }
 };
 
-template <class T>
-int up(DV<T>& d, const T* h, size_t n) {
-    HIPCHK(d.reserve(n));
-    if (n) HIPCHK(hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
 }  // namespace hxi
 
 struct hx_ctx {
@@ -184,18 +191,15 @@ struct hx_ctx {
     hxi::DV<uint32_t> rlen;
     hxi::DV<uint64_t> roff;
     hxi::DV<uint8_t> packed;
-    hxi::DV<uint32_t> q_id, q_start, q_end, t_id, t_len, t_start, t_end, n_match, n_block, cg_ops;
-    hxi::DV<uint8_t> is_rev, mapq;
-    hxi::DV<uint64_t> cg_off, rho;
+    hxi::HitCols hits;
+    hxi::DV<uint64_t> rho;
     std::vector<uint32_t> h_rlen;
     std::vector<uint64_t> h_rho;
     uint32_t lr_begin = 0, lr_end = 0;
     bool prefiltered = false;   // the resident records are the filtered set of an index.longread
     hxi::DV<uint32_t> err;
     // chain results
-    hxi::DV<uint32_t> c_hit, c_qs, c_qe, c_ts, c_te, c_nm, c_nb, c_skf, c_skb, c_cmp;
-    hxi::DV<uint64_t> c_cb, c_ce, aln_off, cmp_off;
-    uint64_t n_aln = 0, n_cmp = 0;
+    struct { hxi::ChainCols col; hxi::DV<uint32_t> cmp_aln; hxi::DV<uint64_t> aln_off, cmp_off; uint64_t n_aln = 0, n_cmp = 0; } chain;
     bool have_chain = false;
     // edge records
     hxi::RecBuf rec_un, rec;   // unsorted (emission order) and sorted
@@ -204,10 +208,7 @@ struct hx_ctx {
     std::vector<uint64_t> h_edge_key, h_edge_off;
     bool have_edges = false;
     // coords results
-    hxi::DV<uint32_t> k_head_end, k_tail_beg, k_supp_lr, k_spos, k_epos;
-    std::vector<uint64_t> h_supp_off;
-    std::vector<uint32_t> h_supp_lr, h_spos, h_epos;
-    uint32_t n_sel = 0;
+    hxi::CoordCols coords;
     bool have_coords = false;
     hxi::PoaCallShape poa_shape;
     bool poa_no_dir = false;   // diagnostics: force the score-matrix traceback
@@ -219,13 +220,17 @@ struct hx_ctx {
     // scratch of the chain / edge / coordinate operators lives as long as the context too (grows, never shrinks): no allocation, free or
     // synchronisation for temporaries in a call once the sizes have been seen
     hxk::Workspace ws;
-    struct {
-        hxi::DV<uint32_t> hit, qs, qe, ts, te, nm, nb, skf, skb, dp, cmp, naln, ncmp;
-        hxi::DV<uint64_t> cb, ce;
-        hxi::DV<int32_t> from;
-    } sc_chain;
+    struct { hxi::ChainCols raw; hxi::DV<uint32_t> dp, cmp, naln, ncmp; hxi::DV<int32_t> from; } sc_chain;   // at raw-hit size; per read: naln, ncmp
     struct { hxi::DV<uint32_t> npairs, perm, perm_tmp, flag; hxi::DV<uint64_t> pair_off, key_tmp, fscan; } sc_edges;
-    struct { hxi::DV<uint32_t> sel, nsupp, t_lr, t_sp, t_ep, best_list; hxi::DV<uint64_t> cap, out_off, b1, e1, b2, e2; hxi::DV<uint8_t> cur; } sc_coords;
+    struct {   // per selected edge (ns; cap and out_off: + 1) and per record of the selected edges, doubled for hairpins (nc)
+        hxi::DV<uint32_t> sel, nsupp, t_lr, t_sp, t_ep, best_list; hxi::DV<uint64_t> cap, out_off, b1, e1, b2, e2; hxi::DV<uint8_t> cur;
+        hipError_t reserve(size_t ns, size_t nc) {
+            hipError_t e;
+            if ((e = sel.reserve(ns)) || (e = nsupp.reserve(ns)) || (e = cap.reserve(ns + 1)) || (e = out_off.reserve(ns + 1)) || (e = t_lr.reserve(nc)) || (e = t_sp.reserve(nc)) ||
+                (e = t_ep.reserve(nc)) || (e = best_list.reserve(nc)) || (e = b1.reserve(nc)) || (e = e1.reserve(nc)) || (e = b2.reserve(nc)) || (e = e2.reserve(nc))) return e;
+            return cur.reserve(nc);
+        }
+    } sc_coords;
     // POA workspace lives as long as the context: allocating tens of GB per call costs more than the kernel
     hxi::PoaPoolBufs poa_pools;
     hxi::PoaArena poa_arena;
@@ -246,10 +251,8 @@ struct hx_ctx {
     hxi::DV<unsigned long long> poa_phase_d, poa_cells_d;
     std::vector<unsigned long long> poa_phase;   // per edge POA_PHASE_WORDS diagnostic words of the last consensus call (kernels/poa_phase_words.h)
 
-    DevHits hits_view() const {
-        return DevHits{n_hits, q_id.p, q_start.p, q_end.p, t_id.p, t_len.p, t_start.p, t_end.p, n_match.p, n_block.p, is_rev.p, mapq.p, cg_off.p, cg_ops.p};
-    }
-    hxk::ChainFinal chain_view() { return hxk::ChainFinal{c_hit.p, c_qs.p, c_qe.p, c_ts.p, c_te.p, c_nm.p, c_nb.p, c_skf.p, c_skb.p, c_cb.p, c_ce.p, c_cmp.p}; }
+    DevHits hits_view() const { return hits.view(n_hits); }
+    hxk::ChainFinal chain_view() const { hxk::ChainFinal v{}; chain.col.fill(v); v.cmp_aln = chain.cmp_aln.p; return v; }
     void tick() { (void)hipEventRecord(tm.a, stream); }
     void tock(int k) {
         (void)hipEventRecord(tm.b, stream);

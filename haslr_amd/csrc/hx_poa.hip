@@ -295,7 +295,7 @@ static int poa_consensus(hx_ctx* c, const PoaInput& in, const hx_poa_params* pp,
 extern "C" int hx_poa_batch(hx_ctx* c, const hx_poa_params* pp, hx_cns_out* out) {
     memset(out, 0, sizeof(*out));
     if (!c->have_coords) return fail("hx_poa_batch: hx_edge_coords has not run");
-    const PoaInput in{c->n_sel, c->h_supp_off.data(), c->h_supp_lr.data(), c->h_spos.data(), c->h_epos.data(), c->h_rlen.data(), c->packed.p, c->roff.p, c->rlen.p};
+    const PoaInput in{c->coords.n_sel, c->coords.h_supp_off.data(), c->coords.h_supp_lr.data(), c->coords.h_spos.data(), c->coords.h_epos.data(), c->h_rlen.data(), c->packed.p, c->roff.p, c->rlen.p};
     return poa_consensus(c, in, pp, out);
 }
 
