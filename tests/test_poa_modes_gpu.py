@@ -89,6 +89,11 @@ def test_nw_through_the_new_entry_is_the_tuned_path(ctx):
     sets = SETS[:200]
     assert ctx.poa_sequences_mode(sets, "nw") == ctx.poa_sequences(sets)
     assert ctx.poa_sequences_mode(sets, "nw", 3, -5, -4) == ctx.poa_sequences(sets, 3, -5, -4)
+    # (both sides above are one tuned call: what it computes under 3 / -5 / -4 is the oracle's consensus)
+    got = ctx.poa_sequences_mode(sets, "nw", 3, -5, -4)
+    with ThreadPoolExecutor(16) as ex:
+        want = list(ex.map(lambda st: orclib.poa_consensus(st, 3, -5, -4), sets))
+    assert [k for k in range(len(sets)) if got[k] != want[k]] == []
 
 
 def test_nw_through_the_general_path_is_the_oracle(ctx):
