@@ -359,6 +359,7 @@ static int poa_general_run(hx_ctx* c, const char* tag, hxk::PoaModesArgs& a, hxk
         if (a.msa) { snprintf(rows, sizeof rows, "%zu bytes of rows, ", o.msa.size()); snprintf(part, sizeof part, " (rows %.3f ms)", o.msa_rows_ms); }
         if (a.weighted) snprintf(part, sizeof part, " (coverage %.3f ms)", o.cov_ms);
         if (a.strand) snprintf(part, sizeof part, " (%llu of %llu sequences reversed)", (unsigned long long)o.third_passes, (unsigned long long)o.n_aligned);
+        if (a.band) snprintf(part, sizeof part, " (band %u, %u reruns after a band miss)", a.band, o.band_reruns);
         if (a.graph) { snprintf(rows, sizeof rows, "%zu nodes, %zu edges, %zu pairs, ", o.node_base.size(), o.edge_w.size(), o.aln_pos.size()); snprintf(part, sizeof part, " (gather %.3f ms, %u sets rerun for their alignments)", o.gather_ms, o.aln_retried); }
         fprintf(stderr, "[hx] POA %s call%s: %u sets, %.3g cells, %skernels %.2f ms%s, %u sets rerun in a larger slot\n", tag, hxk::gap_model_label(a.gap_model), a.n_sets, (double)o.cells, rows, o.kernel_ms, part, o.retried);
     }
@@ -590,6 +591,41 @@ extern "C" int hx_poa_strand(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off
     return 0;
 }
 
+// the consensus of sets aligned inside an adaptive band: the general path's band instances (all three types) of the gap model the scores
+// name, chosen by hx_poa_graph's rules; sets that miss their band climb to twice the band and at last to the full-matrix instances
+extern "C" int hx_poa_banded(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params* cp,
+                             const hx_poa_band_params* bp, hx_band_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!cp || !bp) return fail("hx_poa_banded: no parameters");
+    if (check_convex_call("hx_poa_banded", *cp, set_off[n_sets])) return -1;
+    if (bp->band < 1 || bp->band > hxk::MAX_BAND) return fail("hx_poa_banded: the band half-width must be 1.." + std::to_string(hxk::MAX_BAND) + ", not " + std::to_string(bp->band));
+    if (check_weights("hx_poa_banded", n_sets, set_off, seq_off, weights)) return -1;
+    hxk::PoaModesArgs a = general_args("hx_poa_banded", n_sets, set_off, seq_off, bases, convex_or_affine_scores(c, *cp));
+    a.band = bp->band; a.weights = weights;
+    a.msa = bp->want_msa != 0; a.include_consensus = a.msa && bp->include_consensus != 0;
+    a.want_coverage = bp->want_coverage != 0; a.want_profile = bp->want_profile != 0;
+    a.weighted = weights || a.msa || a.want_coverage || a.want_profile;   // (the consensus alone keeps no node per base)
+    hxk::PoaModesOut o;
+    if (poa_general_run(c, "banded", a, o)) return -1;
+    out->n_set = n_sets;
+    out->cns_off = dup(o.cns_off.data(), (size_t)n_sets + 1);
+    out->cns = dup(o.cns.data(), o.cns.size());
+    out->band_used = dup(o.band_used.data(), n_sets);
+    if (a.msa) {
+        out->n_rows = dup(o.msa_rows.data(), n_sets); out->n_cols = dup(o.msa_cols.data(), n_sets);
+        out->msa_off = dup(o.msa_off.data(), (size_t)n_sets + 1); out->msa = dup(o.msa.data(), o.msa.size());
+    }
+    if (a.want_coverage || a.want_profile) out->coverage = dup(o.cov.data(), o.cov.size());
+    if (a.want_profile) out->profile = dup(o.prof.data(), o.prof.size());
+    out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned; out->workspace_bytes = o.workspace_bytes;
+    out->slot_reruns = o.retried; out->band_reruns = o.band_reruns;
+    return 0;
+}
+
+extern "C" void hx_free_band(hx_ctx*, hx_band_out* o) {
+    free(o->cns_off); free(o->cns); free(o->band_used); free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa); free(o->coverage); free(o->profile);
+    memset(o, 0, sizeof(*o));
+}
 extern "C" void hx_free_strand(hx_ctx*, hx_strand_out* o) {
     free(o->cns_off); free(o->cns); free(o->reversed); free(o->score_fwd); free(o->score_rev); free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa);
     free(o->coverage); free(o->profile);

@@ -22,6 +22,8 @@ inline uint8_t base_code(char c) { return c == 'C' || c == 'c' ? 1 : c == 'G' ||
 // what the debug lines call a gap model (PoaModesArgs::gap_model)
 inline const char* gap_model_label(int gm) { return gm == 2 ? " (convex)" : gm == 1 ? " (affine)" : ""; }
 
+constexpr uint32_t MAX_BAND = 511;   // the widest half-width of a band (PoaModesArgs::band): 2 x 511 + 1 columns are one wavefront's
+
 struct PoaModesArgs {
     const char* who = "";                // the entry point of the C-ABI that asks: the name every error text begins with
     uint32_t n_sets = 0;
@@ -45,6 +47,8 @@ struct PoaModesArgs {
     int strand = 0;                      // 1: hx_poa_strand (the strand instances: every sequence is aligned forward and reverse-complemented and the better
                                          // one is added; weights as for a weighted call, or null). msa / include_consensus and want_coverage / want_profile
                                          // say what PoaModesOut holds beside the flags and the scores
+    uint32_t band = 0;                   // hx_poa_banded: the half-width w of the adaptive band, 1..511 (0: no band). A set whose alignment misses the band is run
+                                         // again with 2 w, at last on the full matrix; not with graph or strand
     uint32_t aln_cap = 0;                // graph calls, first round only: a set's share of the alignment pool holds at most this many pairs (0: no cap); sets whose
                                          // alignments outgrow it are rerun once with exactly the room they need
 };
@@ -78,6 +82,11 @@ struct PoaModesOut {
     std::vector<uint8_t> reversed;
     std::vector<int32_t> score_fwd, score_rev;
     uint64_t third_passes = 0;           // sequences whose reverse complement won: each cost a third DP pass
+    // banded calls: per set the half-width of the attempt that gave its result (0: the full matrix), the reruns after a band miss, and the
+    // largest workspace a round of the call asked for
+    std::vector<uint32_t> band_used;
+    uint32_t band_reruns = 0;
+    uint64_t workspace_bytes = 0;
 };
 
 // 0 = ok, else -1 with the reason in err

@@ -39,7 +39,12 @@
 // forward; when the reverse complement wins, its DP runs once more so that its H is the one the traceback walks), and everything
 // downstream reads the codes and weights as they were added (codes_used / wts_used).
 //
-// Layout: the DP and traceback of the three gap models are poa_modes_dp.inl, the columns, row text, coverage and the graph output's helpers
+// Adaptive banded alignment (hx_poa_banded; DESIGN.md "Banded alignment") is a flag of its own, BAND, over the three variants that keep no
+// per-alignment pair pool: one shape per gap model, one wavefront of 64 lanes x 16 columns, whose row loop and traceback (dp_rows_band,
+// traceback_band) read and write H through per-row windows of 2 w + 1 columns. An alignment without a reachable end cell stops its set
+// with MS_BAND_MISS; the host runs the set again in twice the band, at last in the full-matrix instances above.
+//
+// Layout: the DP and traceback of the three gap models are poa_modes_dp.inl, their banded siblings poa_modes_band.inl, the columns, row text, coverage and the graph output's helpers
 // and gather poa_modes_out.inl, the pools of a set poa_modes_pools.inl; this file keeps the work of one set (run_set), the kernel, the
 // kernel table and the device half of the host driver (poa_modes_run, in named stages: buffers, uploads, launches, downloads). Every
 // integer decision of those stages - limits, instance, slot sizes, shares of the alignment pool, the retry rule, the work lists and
@@ -99,6 +104,7 @@ struct MArgs {
     int32_t q, c;         // convex instances only: gap open and gap extend of the second piece
     GraphOutArgs go;      // graph instances only (poa_modes_out.inl)
     StrandArgs sa;        // strand instances only
+    const uint32_t* band_w;   // band instances only: per set the half-width of its current attempt
 };
 
 // one row of the MSA text: its columns (rising) start at cols[src], its letters at codes[src] (a sequence) or cns[src] (the consensus row)
@@ -154,9 +160,10 @@ __device__ void order_rows(G& g, const uint32_t V, uint32_t* s_scan) {
 struct Shared { uint32_t item, V, E, fail; int best; uint32_t na /* graph instances: the pairs the traceback left */; unsigned long long key; };
 
 #include "poa_modes_dp.inl"     // DP and traceback, linear, affine and convex gaps
+#include "poa_modes_band.inl"   // the banded row loop and traceback: one wavefront per window
 #include "poa_modes_out.inl"    // MSA columns and row text, base weights, coverage, graph and alignment output
 
-template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH, bool STRAND>
+template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH, bool STRAND, bool BAND>
 __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Shared& sh, int* s_wtot, uint32_t* s_scan) {
     const uint32_t t = threadIdx.x;
     const MSet S = a.sets[set];
@@ -165,6 +172,15 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     if (pools > a.slot_bytes) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
     Cell<GM>* H = (Cell<GM>*)(slot + pools);
     const uint64_t hcap = (a.slot_bytes - pools) / sizeof(Cell<GM>);   // cells the slot holds
+    // band instances: H is rcap rows of B cells, and behind it the rows' three word arrays (lo, m, best)
+    BandRows br{};
+    uint64_t rcap = 0;
+    if constexpr (BAND) {
+        static_assert(NT == BAND_NT && CPL == BAND_CPL && !GRAPH && !STRAND, "the band instances are one wavefront of 64 lanes x 16 columns, without graph output and strands");
+        br.w = a.band_w[set]; br.B = 2 * br.w + 1;
+        rcap = (a.slot_bytes - pools) / ((uint64_t)br.B * sizeof(Cell<GM>) + 12);
+        br.lo = (uint32_t*)(slot + pools + rcap * br.B * sizeof(Cell<GM>)); br.m = br.lo + rcap; br.best = (int32_t*)(br.m + rcap);
+    }
     uint32_t V = 0, E = 0, non_empty = 0;
     unsigned long long cells = 0;
     uint64_t aln_used = 0;   // graph instances: the pairs of the set's alignments so far
@@ -176,7 +192,16 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
         const uint8_t* s = a.codes + b;
         non_empty++;
         uint32_t na = 0;
-        if (V) {
+        if constexpr (BAND) {
+            if (V) {
+                if ((uint64_t)V + 1 > rcap) { if (t == 0) { a.status[set] = MS_H_OVERFLOW; a.vseen[set] = V; } return; }
+                cells += (unsigned long long)V * min(br.B, L + 1);
+                uint32_t bi, bj;
+                // (a miss is the same value in every lane: dp_rows_band reads it behind its last barrier)
+                if (dp_rows_band<GM>(g, H, br, V, s, L, a, sh, &bi, &bj)) { if (t == 0) a.status[set] = MS_BAND_MISS; return; }
+                if (t == 0 && bi) na = traceback_band<GM>(g, H, br, s, L, bi, bj, a);
+            }
+        } else if (V) {
             if ((uint64_t)(V + 1) * (L + 1) > hcap) { if (t == 0) { a.status[set] = MS_H_OVERFLOW; a.vseen[set] = V; } return; }
             cells += (unsigned long long)V * L * (STRAND ? 2u : 1u);   // (strand instances: the algorithm's cells, both orientations)
             uint32_t bi, bj;
@@ -247,7 +272,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     __syncthreads();   // the slot is free for the next set
 }
 
-template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH = false, bool STRAND = false>
+template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH = false, bool STRAND = false, bool BAND = false>
 __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
     __shared__ Shared sh;
     __shared__ int s_wtot[(GM == GM_CONVEX ? 2 : 1) * (NT / 64)];   // per wave the total of its row scan (convex: of its two)
@@ -259,7 +284,7 @@ __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
         const uint32_t q = sh.item;
         __syncthreads();
         if (q >= a.n_items) return;
-        run_set<NT, CPL, GM, MSA, WTS, GRAPH, STRAND>(a, a.order[q], slot, sh, s_wtot, s_scan);
+        run_set<NT, CPL, GM, MSA, WTS, GRAPH, STRAND, BAND>(a, a.order[q], slot, sh, s_wtot, s_scan);
     }
 }
 
@@ -275,6 +300,13 @@ const Inst kInst[3][N_INST] = {{HX_POA_INSTANCES_LINEAR(HX_INST)}, {HX_POA_INSTA
 #undef HX_INST
 static_assert(CELL_BYTES[GM_LINEAR] == sizeof(Cell<GM_LINEAR>) && CELL_BYTES[GM_AFFINE] == sizeof(Cell<GM_AFFINE>) && CELL_BYTES[GM_CONVEX] == sizeof(Cell<GM_CONVEX>), "CELL_BYTES against the cell types of poa_modes_dp.inl");
 static_assert(GR_NODES == ROW_NODES && GR_EDGES == ROW_EDGES && GR_CNS == ROW_CNS && GR_ALN == ROW_ALN, "the plan's row kinds against k_graph_gather's");
+// the band instances (BAND_INST, poa_modes_plan.h): one shape per gap model, in the three variants that keep no per-alignment pair pool
+#define HX_BAND(GM) {{(const void*)k_poa_general<BAND_NT, BAND_CPL, GM, false, false, false, false, true>, (const void*)k_poa_general<BAND_NT, BAND_CPL, GM, true, false, false, false, true>, \
+                      (const void*)k_poa_general<BAND_NT, BAND_CPL, GM, true, true, false, false, true>, nullptr, nullptr}}
+const Inst kBand[3] = {HX_BAND(GM_LINEAR), HX_BAND(GM_AFFINE), HX_BAND(GM_CONVEX)};
+#undef HX_BAND
+static_assert(BAND_SHAPE.nt == BAND_NT && BAND_SHAPE.cpl == BAND_CPL && 2 * MAX_BAND + 1 <= BAND_NT * BAND_CPL, "the plan's band shape against the kernels'");
+static_assert(MAX_LEN[GM_LINEAR] + 1 <= (BAND_SEQ_WORDS - 1) * 16, "the staged sequence of the band instances against the longest sequence");
 inline const void* fn(const Inst& inst, bool cols, bool weighted, bool graph, bool strand) { return inst.variant[strand ? 4 : graph ? 3 : weighted ? 2 : cols ? 1 : 0]; }
 
 template <class T> struct Buf {   // device buffer of one call
@@ -311,6 +343,7 @@ struct Run {
     uint64_t budget = 0;
     Buf<MSet> d_sets; Buf<uint8_t> d_codes; Buf<uint64_t> d_soff; Buf<uint32_t> d_order, d_counter, d_status, d_vseen, d_cns_len; Buf<unsigned long long> d_cells; Buf<char> d_cns;
     Buf<uint32_t> d_base_col, d_n_cols, d_cns_col;   // MSA and weighted calls only
+    Buf<uint32_t> d_band;                            // banded calls only: per set the half-width of its current attempt
     Buf<uint8_t> d_wts;                              // weighted calls with weights only: a byte per base (graph and strand calls: always, 1 without weights)
     // strand calls only: what StrandArgs points to
     Buf<uint8_t> d_codes_rc, d_wts_rc, d_codes_used, d_wts_used, d_reversed; Buf<int32_t> d_score_fwd, d_score_rev; Buf<uint32_t> d_third;
@@ -322,7 +355,7 @@ struct Run {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~Run() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
 
-    const void* fn_of(int k) const { return fn(kInst[c.gm][k], c.cols, d_wts.p != nullptr, c.graph, c.strand); }
+    const void* fn_of(int k) const { return fn(k == BAND_INST ? kBand[c.gm] : kInst[c.gm][k], c.cols, d_wts.p != nullptr, c.graph, c.strand); }
     const uint8_t* codes_as_added() const { return c.strand ? d_codes_used.p : d_codes.p; }   // what the row, coverage and profile kernels read
 
     // runs f (0 = ok) between two events, waits for it, and adds the milliseconds it took on the device to *ms
@@ -348,13 +381,14 @@ struct Run {
         int dev = 0;
         MCHK(hipGetDevice(&dev));
         MCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        MCHK(d_sets.alloc(ns)); MCHK(d_codes.alloc(c.codes.size())); MCHK(d_soff.alloc(nseq + 1)); MCHK(d_order.alloc(ns)); MCHK(d_counter.alloc(N_INST));
+        MCHK(d_sets.alloc(ns)); MCHK(d_codes.alloc(c.codes.size())); MCHK(d_soff.alloc(nseq + 1)); MCHK(d_order.alloc(ns)); MCHK(d_counter.alloc(N_SLOTS));
         MCHK(d_status.alloc(ns)); MCHK(d_vseen.alloc(ns)); MCHK(d_cns_len.alloc(ns)); MCHK(d_cells.alloc(ns)); MCHK(d_cns.alloc(ncns));
         MCHK(hipMemcpyAsync(d_sets.p, c.sets.data(), ns * sizeof(MSet), hipMemcpyHostToDevice, s));
         MCHK(hipMemcpyAsync(d_codes.p, c.codes.data(), c.codes.size(), hipMemcpyHostToDevice, s));   // (the codes live to the end of the call)
         MCHK(hipMemcpyAsync(d_soff.p, a.seq_off, (nseq + 1) * 8, hipMemcpyHostToDevice, s));
         MCHK(d_cns_len.fill(0, ns, s));
         MCHK(d_cells.fill(0, ns, s));
+        if (c.band) MCHK(d_band.alloc(ns));
         if (c.cols) {
             MCHK(d_base_col.alloc(nb)); MCHK(d_n_cols.alloc(ns));
             MCHK(d_n_cols.fill(0, ns, s));
@@ -393,12 +427,11 @@ struct Run {
     // ---- one round over st.todo: plan (plan_round), launch, collect; the sets that outgrew their slot are todo again (after_round)
     int round(const bool first) {
         const uint32_t ns = c.ns;
-        const InstShape* const shape = INST_SHAPE[c.gm];
-        uint64_t resident[N_INST] = {};   // workgroups the device holds, asked for the instances that have sets
-        for (int k = 0; k < N_INST; k++) {
-            if (std::none_of(st.todo.begin(), st.todo.end(), [&](uint32_t i) { return inst_of(c, i) == k; })) continue;
+        uint64_t resident[N_SLOTS] = {};   // workgroups the device holds, asked for the instances that have sets
+        for (int k = 0; k < N_SLOTS; k++) {
+            if (std::none_of(st.todo.begin(), st.todo.end(), [&](uint32_t i) { return slot_of(c, st, i) == k; })) continue;
             int occ = 0;
-            MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_of(k), shape[k].nt, 0));
+            MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_of(k), shape_of(c.gm, k).nt, 0));
             resident[k] = (uint64_t)std::max(1, occ) * (uint64_t)n_cu;
         }
         RoundPlan p;
@@ -410,6 +443,8 @@ struct Run {
             if (e != hipSuccess) { ws.p = nullptr; err = c.who + ": the workspace of " + std::to_string(p.total) + " bytes could not be allocated: " + hipGetErrorString(e); return -1; }
             ws.cap = p.total;
         }
+        o.workspace_bytes = std::max(o.workspace_bytes, p.total);
+        if (c.band) MCHK(hipMemcpyAsync(d_band.p, st.band.data(), ns * 4, hipMemcpyHostToDevice, s));   // (st.band stays as it is until after_round, behind the round's last download)
         GraphOutArgs go{};
         if (c.graph) {   // this round's pool
             pools.emplace_back(new Pool);
@@ -425,21 +460,21 @@ struct Run {
                               d_edge_from.p, d_edge_to.p, d_edge_w.p, d_n_edges.p, d_cns_node.p};
         }
         MCHK(hipMemcpyAsync(d_order.p, p.order.data(), p.order.size() * 4, hipMemcpyHostToDevice, s));
-        MCHK(d_counter.fill(0, N_INST, s));
+        MCHK(d_counter.fill(0, N_SLOTS, s));
         MCHK(d_status.fill(0xff, ns, s));
         float ms = 0;
         if (timed(&ms, [&] {
-                for (int k = 0; k < N_INST; k++) {
+                for (int k = 0; k < N_SLOTS; k++) {
                     const RoundPlan::PerInst& pk = p.inst[k];
                     if (pk.sets.empty()) continue;
                     MArgs q{d_sets.p, d_order.p + pk.base, (uint32_t)pk.sets.size(), d_counter.p + k, d_codes.p, d_soff.p, (uint8_t*)ws.p, pk.slot,
                             a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p, a.gap_extend,
                             d_base_col.p, d_n_cols.p, d_cns_col.p, d_wts.p, a.gap_open2, a.gap_extend2, go,
-                            StrandArgs{d_codes_rc.p, d_wts_rc.p ? d_wts_rc.p : d_wts.p, d_codes_used.p, d_wts_used.p, d_reversed.p, d_score_fwd.p, d_score_rev.p, d_third.p}};
+                            StrandArgs{d_codes_rc.p, d_wts_rc.p ? d_wts_rc.p : d_wts.p, d_codes_used.p, d_wts_used.p, d_reversed.p, d_score_fwd.p, d_score_rev.p, d_third.p}, d_band.p};
                     void* kargs[] = {&q};
-                    MCHK(hipLaunchKernel(fn_of(k), dim3(pk.nslots), dim3((uint32_t)shape[k].nt), kargs, 0, s));
+                    MCHK(hipLaunchKernel(fn_of(k), dim3(pk.nslots), dim3((uint32_t)shape_of(c.gm, k).nt), kargs, 0, s));
                     o.launches++;
-                    if (a.debug) fprintf(stderr, "[hx] POA modes%s: %zu sets on %u workgroups of %d lanes x %d columns, slots of %.1f MB\n", gap_model_label(c.gm), pk.sets.size(), pk.nslots, shape[k].nt, shape[k].cpl, pk.slot / 1e6);
+                    if (a.debug) fprintf(stderr, "[hx] POA modes%s: %zu sets on %u workgroups of %d lanes x %d columns, slots of %.1f MB\n", gap_model_label(c.gm), pk.sets.size(), pk.nslots, shape_of(c.gm, k).nt, shape_of(c.gm, k).cpl, pk.slot / 1e6);
                 }
                 return 0;
             })) return -1;
@@ -448,8 +483,12 @@ struct Run {
         MCHK(d_status.download(status.data(), ns));
         MCHK(d_vseen.download(vseen.data(), ns));
         if (c.graph) { pairs.resize(ns); MCHK(d_aln_need.download(pairs.data(), ns)); }
+        if (c.band) {   // the half-width a set finished with, before after_round moves the others on
+            o.band_used.resize(ns, 0);
+            for (uint32_t i : st.todo) if (status[i] == MS_OK) o.band_used[i] = st.band[i];
+        }
         const int bad = after_round(c, st, first, status.data(), vseen.data(), pairs.data(), err);
-        o.retried = st.retried; o.aln_retried = st.aln_retried;
+        o.retried = st.retried; o.aln_retried = st.aln_retried; o.band_reruns = st.band_retried;
         return bad;
     }
 
@@ -463,6 +502,7 @@ struct Run {
         MCHK(d_cns_len.download(len.data(), ns));
         MCHK(d_cells.download(cells.data(), ns));
         MCHK(d_cns.download(cns.data(), c.cns_off[ns]));
+        if (c.band) o.band_used.resize(ns, 0);   // (a call without a round: no set has a base)
         o.cns_off.assign((size_t)ns + 1, 0);
         for (uint32_t i = 0; i < ns; i++) {
             o.cns.append(cns.data() + c.cns_off[i], len[i]);

@@ -11,7 +11,7 @@ namespace hxk {
 
 enum { MT_SW = 0, MT_NW = 1, MT_OV = 2 };
 enum { GM_LINEAR = 0, GM_AFFINE = 1, GM_CONVEX = 2 };   // PoaModesArgs::gap_model
-enum { MS_OK = 0, MS_H_OVERFLOW = 1, MS_GRAPH_OVERFLOW = 2, MS_ALN_OVERFLOW = 3 };   // (3: done, but its alignments outgrew their share of the pool)
+enum { MS_OK = 0, MS_H_OVERFLOW = 1, MS_GRAPH_OVERFLOW = 2, MS_ALN_OVERFLOW = 3, MS_BAND_MISS = 4 };   // (3: done, but its alignments outgrew their share of the pool; 4: an alignment had no reachable end cell in its band)
 constexpr uint32_t MAX_SET_BASES = (1u << 21) - 2;   // node ids are packed in 21 bits (+1) in the node records of poa_graph.inl
 
 struct MSet { uint64_t seq_begin, sum_len, cns_off; uint32_t nseq, lmax; };
@@ -32,6 +32,12 @@ constexpr InstShape INST_SHAPE[3][N_INST] = {{HX_POA_INSTANCES_LINEAR(HX_SHAPE)}
 #undef HX_SHAPE
 constexpr uint32_t MAX_LEN[3] = {1024 * 32 - 1, 1024 * 16 - 1, 512 * 16 - 1};
 constexpr uint64_t CELL_BYTES[3] = {4, 8, 12};   // of a cell of H by gap model: what the kernels take as sizeof(Cell<GM>)
+// The band instance (PoaModesArgs::band; DESIGN.md "Banded alignment"): one shape for the three gap models, one wavefront that holds a window of
+// 2 w + 1 <= 1023 columns. It is slot BAND_INST of a round's plan, behind the N_INST full-matrix instances: a call without a band never names it.
+constexpr int BAND_INST = N_INST, N_SLOTS = N_INST + 1;
+constexpr InstShape BAND_SHAPE = {64, 16};
+constexpr int64_t BAND_SCORE_BOUND = 1 << 28;   // (bases of a set + its longest sequence) x the largest score magnitude stays below it
+inline InstShape shape_of(int gm, int k) { return k == BAND_INST ? BAND_SHAPE : INST_SHAPE[gm][k]; }
 static_assert(MAX_LEN[GM_LINEAR] + 1 == INST_SHAPE[GM_LINEAR][N_INST - 1].nt * INST_SHAPE[GM_LINEAR][N_INST - 1].cpl && MAX_LEN[GM_AFFINE] + 1 == INST_SHAPE[GM_AFFINE][N_INST - 1].nt * INST_SHAPE[GM_AFFINE][N_INST - 1].cpl &&
               MAX_LEN[GM_CONVEX] + 1 == INST_SHAPE[GM_CONVEX][N_INST - 1].nt * INST_SHAPE[GM_CONVEX][N_INST - 1].cpl, "MAX_LEN against the widest instance of every gap model");
 
@@ -46,6 +52,7 @@ struct ModesCall {
     bool graph = false;                                      // hx_poa_graph: the node of every base stays a node, the graph and the alignments are written out
     bool strand = false;                                     // hx_poa_strand: every sequence in both orientations; MSA text, coverage and profile as asked
     bool cols = false, want_cov = false;
+    bool band = false;                                       // hx_poa_banded: sets run inside an adaptive band as long as they do not miss it
     uint64_t nseq = 0, nb = 0;
     std::vector<MSet> sets;
     std::vector<uint64_t> cns_off;                           // ns + 1
@@ -64,27 +71,36 @@ struct ModesState {
     std::vector<uint64_t> aln_at;
     uint32_t rounds = 0;             // planned so far
     uint32_t retried = 0, aln_retried = 0;   // sets rerun in a larger slot, sets rerun because their alignments outgrew their share
+    // banded calls only: per set the half-width of its current attempt (0: the full matrix), and the reruns after a band miss
+    std::vector<uint32_t> band;
+    uint32_t band_retried = 0;
 };
 
 // the graph pools of a set in bytes: carve_pools (poa_modes_pools.inl) itself, asked without a slot
 uint64_t pools_bytes(const MSet& S);
 // the first instance whose NT x CPL columns hold the set's longest sequence + 1
 int inst_of(const ModesCall& c, uint32_t set);
+// the slot of a round's plan a set runs in: BAND_INST while it has a half-width, else inst_of(c, set)
+int slot_of(const ModesCall& c, const ModesState& st, uint32_t set);
+// the half-width after a band miss at w of a set whose longest sequence is lmax: 2 w while that window holds at most 1023 columns and does
+// not hold the whole sequence, else 0, the full matrix
+uint32_t next_band(uint32_t w, uint32_t lmax);
 
 // the sets checked and described, the codes, the first estimates and the first shares of the alignment pool. 0, or -1 with the reason in err
 int describe(const PoaModesArgs& a, ModesCall& c, ModesState& st, std::string& err);
 
 struct RoundPlan {
     struct PerInst { std::vector<uint32_t> sets; uint64_t base = 0, slot = 0; uint32_t nslots = 0; };   // sets: in launch order; base: their place in order
-    PerInst inst[N_INST];
+    PerInst inst[N_SLOTS];
     std::vector<uint32_t> order;
     uint64_t total = 0;        // bytes of the shared workspace
     uint64_t aln_pairs = 0;    // graph calls: the round's alignment pool
 };
 // one round over st.todo: per instance its sets costliest first, one slot size (the largest need), as many slots as are resident
-// (resident[k]: workgroups of instance k the device holds; read for instances with sets only) and fit the budget. Graph calls: the
+// (resident[k]: workgroups of instance k the device holds; read for instances with sets only, so a call without a band may pass N_INST of
+// them and a banded one passes N_SLOTS) and fit the budget. Graph calls: the
 // shares of the round's pool side by side (st.pool_of, st.aln_at).
-int plan_round(const ModesCall& c, ModesState& st, bool first, uint64_t budget, const uint64_t resident[N_INST], RoundPlan& p, std::string& err);
+int plan_round(const ModesCall& c, ModesState& st, bool first, uint64_t budget, const uint64_t* resident, RoundPlan& p, std::string& err);
 // the statuses of a round: st.todo becomes the sets that come back, with their new estimate or share
 int after_round(const ModesCall& c, ModesState& st, bool first, const uint32_t* status, const uint32_t* vseen, const uint32_t* pairs, std::string& err);
 

@@ -21,6 +21,13 @@ int inst_of(const ModesCall& c, uint32_t set) {
     return k;
 }
 
+int slot_of(const ModesCall& c, const ModesState& st, uint32_t set) { return c.band && st.band[set] ? BAND_INST : inst_of(c, set); }
+
+uint32_t next_band(uint32_t w, uint32_t lmax) {
+    const uint32_t w2 = 2 * w;
+    return w2 <= MAX_BAND && (uint64_t)lmax + 1 > 2 * (uint64_t)w2 + 1 ? w2 : 0u;
+}
+
 int describe(const PoaModesArgs& a, ModesCall& c, ModesState& st, std::string& err) {
     c = ModesCall();
     st = ModesState();
@@ -28,6 +35,9 @@ int describe(const PoaModesArgs& a, ModesCall& c, ModesState& st, std::string& e
     c.msa = a.msa != 0; c.wtd = a.weighted != 0; c.graph = a.graph != 0; c.strand = a.strand != 0;
     c.cols = c.msa || c.wtd || c.graph || c.strand;
     c.want_cov = (c.wtd || c.strand) && (a.want_coverage || a.want_profile);
+    c.band = a.band != 0;
+    if (c.band && a.band > MAX_BAND) { err = c.who + ": the band half-width must be 1.." + std::to_string(MAX_BAND) + ", not " + std::to_string(a.band); return -1; }
+    if (c.band && (c.graph || c.strand)) { err = c.who + ": graph output and strand-ambiguous sets have no band"; return -1; }
     const uint32_t ns = c.ns;
     const int gm = c.gm;
     c.nseq = a.set_off[ns]; c.nb = a.seq_off[c.nseq];
@@ -45,6 +55,17 @@ int describe(const PoaModesArgs& a, ModesCall& c, ModesState& st, std::string& e
         }
         if (S.sum_len > MAX_SET_BASES) { err = c.who + ": set " + std::to_string(i) + " holds " + std::to_string(S.sum_len) + " bases in all, more than the " + std::to_string(MAX_SET_BASES) + " nodes a graph can have"; return -1; }
         S.cns_off = c.cns_off[i]; c.cns_off[i + 1] = c.cns_off[i] + S.sum_len;   // (a consensus has at most one base per node)
+    }
+    if (c.band) {
+        // every real value of a banded set's matrices stays above -2^28 and every value derived from minus infinity at or below it
+        int64_t mag = 0;
+        for (const int32_t v : {a.match, a.mismatch, a.gap, a.gap_extend, a.gap_open2, a.gap_extend2}) mag = std::max<int64_t>(mag, v < 0 ? -(int64_t)v : v);
+        st.band.assign(ns, 0);
+        for (uint32_t i = 0; i < ns; i++) {
+            const MSet& S = c.sets[i];
+            if ((int64_t)(S.sum_len + S.lmax) * mag >= BAND_SCORE_BOUND) { err = c.who + ": set " + std::to_string(i) + " holds " + std::to_string(S.sum_len) + " bases, its longest sequence " + std::to_string(S.lmax) + ": with scores of up to " + std::to_string(mag) + " their product " + std::to_string((int64_t)(S.sum_len + S.lmax) * mag) + " reaches 2^28 = " + std::to_string(BAND_SCORE_BOUND) + " (a banded set's scores must stay below it)"; return -1; }
+            st.band[i] = (uint64_t)S.lmax + 1 <= 2 * (uint64_t)a.band + 1 ? 0u : a.band;   // (a window that holds the longest sequence is the full matrix)
+        }
     }
     c.codes.resize(std::max<uint64_t>(1, c.nb));
     for (uint64_t k = 0; k < c.nb; k++) c.codes[k] = base_code(a.bases[k]);
@@ -84,14 +105,18 @@ int describe(const PoaModesArgs& a, ModesCall& c, ModesState& st, std::string& e
     return 0;
 }
 
-int plan_round(const ModesCall& c, ModesState& st, const bool first, const uint64_t budget, const uint64_t resident[N_INST], RoundPlan& p, std::string& err) {
+int plan_round(const ModesCall& c, ModesState& st, const bool first, const uint64_t budget, const uint64_t* resident, RoundPlan& p, std::string& err) {
     const PoaModesArgs& a = *c.a;
     const std::vector<MSet>& sets = c.sets;
     const uint64_t cell_bytes = CELL_BYTES[c.gm];
-    auto need = [&](uint32_t i) { return pools_bytes(sets[i]) + al256((st.vest[i] + 1) * (uint64_t)(sets[i].lmax + 1) * cell_bytes); };
+    // (a banded set: vest + 1 rows of B cells, and the rows' three word arrays)
+    auto need = [&](uint32_t i) {
+        if (c.band && st.band[i]) return pools_bytes(sets[i]) + al256((st.vest[i] + 1) * (2 * (uint64_t)st.band[i] + 1) * cell_bytes + 12 * (st.vest[i] + 1));
+        return pools_bytes(sets[i]) + al256((st.vest[i] + 1) * (uint64_t)(sets[i].lmax + 1) * cell_bytes);
+    };
     p = RoundPlan();
-    for (uint32_t i : st.todo) p.inst[inst_of(c, i)].sets.push_back(i);
-    for (int k = 0; k < N_INST; k++) {
+    for (uint32_t i : st.todo) p.inst[slot_of(c, st, i)].sets.push_back(i);
+    for (int k = 0; k < N_SLOTS; k++) {
         auto& v = p.inst[k].sets;
         if (v.empty()) continue;
         std::stable_sort(v.begin(), v.end(), [&](uint32_t x, uint32_t y) { return sets[x].sum_len * sets[x].lmax > sets[y].sum_len * sets[y].lmax; });
@@ -128,6 +153,12 @@ int after_round(const ModesCall& c, ModesState& st, const bool first, const uint
             st.aln_rerun[i] = 1; st.aln_room[i] = pairs[i];
             next.push_back(i);
             st.aln_retried++;
+            continue;
+        }
+        if (c.band && st.band[i] && status[i] == MS_BAND_MISS) {   // from its first sequence again, in twice the band or on the full matrix
+            st.band[i] = next_band(st.band[i], c.sets[i].lmax);
+            next.push_back(i);
+            st.band_retried++;
             continue;
         }
         const bool capped = first && a.slot_kb_cap;   // (a capped slot can be short of even the worst case)

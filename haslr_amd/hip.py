@@ -16,7 +16,7 @@ _lib = None
 SYMBOLS = ["hx_last_error", "hx_device_count", "hx_ctx_create", "hx_ctx_destroy", "hx_upload", "hx_set_read_shard", "hx_set_prefiltered",
            "hx_chain_reads", "hx_edge_support", "hx_edge_coords", "hx_poa_batch", "hx_free_chain", "hx_free_edges",
            "hx_free_coords", "hx_free_cns", "hx_edge_emit", "hx_edge_records_bytes", "hx_edge_records_export",
-           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_poa_graph", "hx_free_graph", "hx_poa_strand", "hx_free_strand", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
+           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_poa_graph", "hx_free_graph", "hx_poa_strand", "hx_free_strand", "hx_poa_banded", "hx_free_band", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
            "hx_set_option", "hx_get_option", "hx_option_names", "hx_poa_memory_stats", "hx_poa_release_workspace", "hx_poa_prune_stats", "hx_poa_retry_stats", "hx_group_set_timeout", "hx_group_inject_fault", "hx_poa_reserve", "hx_poa_host_times", "hx_poa_arena_stats", "hx_group_rccl_ranks",
            "hx_group_create", "hx_group_destroy", "hx_group_size", "hx_group_ctx", "hx_group_transport", "hx_edge_merge", "hx_group_backend_fill", "hx_group_exchange_stats"]
 
@@ -57,6 +57,8 @@ def lib():
         L.hx_free_graph.argtypes = [C.c_void_p, C.POINTER(T.GraphOut)]
         L.hx_poa_strand.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.PoaStrandWant), C.POINTER(T.StrandOut)]
         L.hx_free_strand.argtypes = [C.c_void_p, C.POINTER(T.StrandOut)]
+        L.hx_poa_banded.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.PoaBandParams), C.POINTER(T.BandOut)]
+        L.hx_free_band.argtypes = [C.c_void_p, C.POINTER(T.BandOut)]
         L.hx_free_chain.argtypes = [C.c_void_p, C.POINTER(T.ChainOut)]
         L.hx_free_edges.argtypes = [C.c_void_p, C.POINTER(T.EdgesOut)]
         L.hx_free_coords.argtypes = [C.c_void_p, C.POINTER(T.CoordsOut)]
@@ -195,6 +197,9 @@ GraphSequence = namedtuple("GraphSequence", "path alignment score")
 # One set of HipContext.poa_strand (include/haslr_types.h, hx_strand_out): the consensus; per GIVEN sequence whether its reverse complement
 # was added and the (forward, reverse-complemented) end-cell scores; the MSA rows, the coverage and the profile, each None unless asked for
 StrandRecord = namedtuple("StrandRecord", "consensus reversed scores rows coverage profile")
+# One set of HipContext.poa_banded (include/haslr_types.h, hx_band_out): the consensus; the half-width of the attempt that gave it (0: the
+# full matrix); rows, coverage and profile as StrandRecord has them, each None unless asked for.
+BandRecord = namedtuple("BandRecord", "consensus band_used rows coverage profile")
 
 
 def _out_edges_in_list_order(rec):
@@ -603,6 +608,42 @@ class HipContext:
             st = _counters(o, "third_passes", "slot_reruns")
         finally:
             lib().hx_free_strand(self._h, C.byref(o))
+        return (res, st) if stats else res
+
+    def poa_banded(self, sets, band, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=None, gap_open2=None, gap_extend2=None, weights=None, qualities=None,
+                   msa=False, include_consensus=False, coverage=False, profile=False, stats=False):
+        """the consensus of sets aligned inside an adaptive band of half-width `band` (hx_poa_banded; 1..511): every row of an alignment's
+        score matrix owns the 2 * band + 1 columns around a centre that follows the best cell of its best predecessor, so a set takes
+        (nodes + 1) x (2 * band + 1) cells of workspace and one wavefront per window. A set with an alignment that finds no end cell inside
+        its band (a band miss; global and overlap alignment) is run again with twice the band and at last on the full matrix; a set
+        whose longest sequence + 1 fits the window runs on the full matrix at once. A list with one BandRecord per set: consensus;
+        band_used (the half-width of the attempt that gave the result, 0: the full matrix); rows (msa=True: the alignment text as poa_msa
+        has it, with include_consensus the consensus last), coverage and profile (as poa_weighted has them), each None unless asked for.
+        gap_extend None (or equal to gap_open) is the linear gap model; gap_open2 and gap_extend2 (both or neither) give the convex one.
+        weights / qualities: as for poa_weighted, with its checks and errors. With stats=True returns (records, counters): dp_cells
+        (nodes x window columns per banded alignment of the final attempts), seq_bases, n_aligned, workspace_bytes (the largest workspace a
+        round asked for), slot_reruns and band_reruns (the reruns after a band miss)."""
+        import numpy as np
+        _check_type(type)
+        ge = gap_open if gap_extend is None else gap_extend
+        cp = _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
+        if cp is None:   # one piece: a second one that is the first again never wins
+            cp = T.PoaConvexParams(match, mismatch, gap_open, ge, gap_open, ge, T.POA_TYPES[type])
+        if not 0 <= int(band) <= 0xffffffff:
+            raise ValueError("band is a half-width in columns, 1..511")
+        wbytes = _weight_bytes(sets, weights, qualities)
+        bp = T.PoaBandParams(int(band), int(bool(msa)), int(bool(msa and include_consensus)), int(bool(coverage)), int(bool(profile)))
+        o = T.BandOut()
+        n_sets, set_off, seq_off, bases = _flatten_sets(sets)
+        self._chk(lib().hx_poa_banded(self._h, n_sets, set_off, seq_off, bases, wbytes, C.byref(cp), C.byref(bp), C.byref(o)))
+        try:
+            cns, cov, prof = T.wcns_to_lists(o)
+            rows = T.msa_to_lists(o)[0] if msa else None
+            used = T.arr(o.band_used, n_sets, np.uint32).tolist()
+            res = [BandRecord(cns[i], used[i], rows[i] if msa else None, cov[i] if coverage else None, prof[i] if profile else None) for i in range(n_sets)]
+            st = _counters(o, "workspace_bytes", "slot_reruns", "band_reruns")
+        finally:
+            lib().hx_free_band(self._h, C.byref(o))
         return (res, st) if stats else res
 
     def poa_phase_cycles(self):

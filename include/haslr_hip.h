@@ -173,6 +173,24 @@ void hx_free_graph(hx_ctx*, hx_graph_out*);
  *                     path: the rules are written after spoa's main.cpp as published and the tests hold them to a CPU restatement. */
 int hx_poa_strand(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params*, const hx_poa_strand_want*, hx_strand_out* out);
 void hx_free_strand(hx_ctx*, hx_strand_out*);
+/*   hx_poa_banded     the consensus of sets aligned inside an adaptive band (DESIGN.md "General POA path", "Banded alignment"; the arrays:
+ *                     haslr_types.h, hx_band_out). Row i of an alignment's score matrix owns the 2 w + 1 columns around a centre one past
+ *                     the best cell of its best predecessor's row; every other cell is minus infinity. An alignment without a reachable
+ *                     end cell (kNW, kOV) is a band miss: its set is run again from its first sequence with 2 w, and once 2 w + 1 would
+ *                     pass 1023 columns on the full matrix; a set whose longest sequence + 1 fits the window runs on the full matrix at
+ *                     once. band_used tells per set which it was. H takes (nodes + 1) x (2 w + 1) cells per workspace slot instead of
+ *                     (nodes + 1) x (length + 1), and a window is one wavefront's. One entry over the convex parameters, by hx_poa_graph's
+ *                     rules for the gap model (sequences of up to 8191, 16383 and 32767 bases: any set may end on the full matrix); weights
+ *                     as for hx_poa_weighted (1..255, 0 refused), or NULL; MSA text, coverage and profile as hx_poa_strand hands them
+ *                     over. Every type runs the general path. The errors are hx_poa_graph's with this entry's name in front, and: a band
+ *                     outside 1..511; a set for which (its bases + its longest sequence) x the largest score magnitude reaches 2^28 (the
+ *                     bound that keeps real scores and minus infinity apart). Options poa_modes_slot_kb and poa_workspace_gb act as on
+ *                     the other entries. Under kOV and kSW, whose alignments start anywhere for free, the centre can leave the true diagonal in
+ *                     a graph's first rows (DESIGN.md has the measurement): check the result against a wider band there. Graph output and
+ *                     strand-ambiguous sets have no band. Not pinned against spoa, which has no band:
+ *                     the tests hold the rules to a CPU restatement. */
+int hx_poa_banded(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params*, const hx_poa_band_params*, hx_band_out* out);
+void hx_free_band(hx_ctx*, hx_band_out*);
 void hx_free_chain(hx_ctx*, hx_chain_out*);
 void hx_free_edges(hx_ctx*, hx_edges_out*);
 void hx_free_coords(hx_ctx*, hx_coords_out*);

@@ -276,6 +276,37 @@ typedef struct {
     uint32_t slot_reruns;
 } hx_strand_out;
 
+/* hx_poa_banded: the half-width of the adaptive band, and what is wanted beside the consensus (hx_poa_strand_want's four switches). */
+typedef struct {
+    uint32_t band;             /* the half-width w, 1..511: every row of the score matrix owns 2 w + 1 columns */
+    int32_t want_msa;          /* 0 / 1: the alignment text of every set */
+    int32_t include_consensus; /* 0 / 1: with want_msa, the consensus is the last row of every set */
+    int32_t want_coverage;     /* 0 / 1: the coverage of every consensus base */
+    int32_t want_profile;      /* 0 / 1: and the four letter counts of its column (the coverage is filled in as well) */
+} hx_poa_band_params;
+
+/* hx_poa_banded: the consensus of sets aligned inside an adaptive band (DESIGN.md "General POA path", "Banded alignment"). band_used[i]
+ * is the half-width of the attempt that gave set i's result: the call's, a doubled one after band misses, or 0 for the full matrix (a
+ * set whose longest sequence + 1 fits the window, or one that missed every band). n_rows / n_cols / msa_off / msa are hx_msa_out's (NULL
+ * unless want_msa), coverage / profile hx_wcns_out's (NULL unless asked for). dp_cells counts, over the alignments of every set's final
+ * attempt, nodes x min(2 w + 1, length + 1) inside a band and nodes x length on the full matrix. slot_reruns: the sets that ran again
+ * in a larger workspace slot; band_reruns: the reruns after a band miss (a set counts once per rung it climbs); workspace_bytes: the
+ * largest workspace a round of the call asked for. */
+typedef struct {
+    uint32_t n_set;
+    uint64_t* cns_off;   /* n_set+1 */
+    char* cns;
+    uint32_t* band_used; /* n_set */
+    uint32_t* n_rows;    /* n_set, or NULL */
+    uint32_t* n_cols;    /* n_set, or NULL */
+    uint64_t* msa_off;   /* n_set+1, or NULL */
+    char* msa;           /* or NULL */
+    uint32_t* coverage;  /* cns_off[n_set], or NULL */
+    uint32_t* profile;   /* 4 * cns_off[n_set], or NULL */
+    uint64_t dp_cells, seq_bases, n_aligned, workspace_bytes;
+    uint32_t slot_reruns, band_reruns;
+} hx_band_out;
+
 #ifdef __cplusplus
 }
 #endif

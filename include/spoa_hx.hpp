@@ -452,6 +452,57 @@ inline std::vector<Stranded> strand_batch(const std::vector<std::vector<std::str
     return strand_batch(detail::pointers(sets), detail::pointers(weights), type, m, n, g, e, q, c, msa, include_consensus);
 }
 
+// banded sets in ONE device call (hx_poa_banded): every alignment runs inside an adaptive band of half-width `band` (1..511), a set that
+// misses its band is run again with twice the band and at last on the full matrix. Per set: the consensus, the half-width of the attempt
+// that gave it (0: the full matrix), and with msa the rows (with include_consensus the consensus is the last row). weights as for
+// weighted_batch, or empty: every weight is 1. (q, c) == (g, e) is one gap piece, and then e == g the linear model.
+struct Banded {
+    std::string consensus;
+    std::uint32_t band_used = 0;
+    std::vector<std::string> rows;   // empty unless asked for
+};
+inline std::vector<Banded> banded_batch(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights,
+                                        std::uint32_t band, AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, std::int8_t q = -8,
+                                        std::int8_t c = -8, bool msa = false, bool include_consensus = false) {
+    if (!weights.empty() && weights.size() != sets.size()) throw std::invalid_argument("spoa_hx: banded_batch needs one set of weights per set of sequences, or none");
+    const detail::Flat f(sets);
+    std::vector<std::uint8_t> w;
+    for (std::size_t i = 0; i < sets.size() && !weights.empty(); i++) {
+        const auto& st = *sets[i];
+        if (weights[i]->size() != st.size()) throw std::invalid_argument("spoa_hx: banded_batch: a set has another number of weight vectors than of sequences");
+        for (std::size_t k = 0; k < st.size(); k++) {
+            const auto& wk = (*weights[i])[k];
+            if (wk.size() != st[k].size()) throw std::invalid_argument("spoa_hx: banded_batch: a sequence has another number of weights than of bases");
+            w.insert(w.end(), wk.begin(), wk.end());
+        }
+    }
+    if (!weights.empty() && w.empty()) w.push_back(1);   // (no base at all: a pointer that is not null, nothing behind it is read)
+    const hx_poa_convex_params cp{m, n, g, e, q, c, static_cast<std::int32_t>(type)};
+    const hx_poa_band_params bp{band, msa ? 1 : 0, msa && include_consensus ? 1 : 0, 0, 0};
+    hx_band_out out;
+    return detail::locked_call([&](hx_ctx* ctx) { return hx_poa_banded(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), weights.empty() ? nullptr : w.data(), &cp, &bp, &out); },
+                               [&](hx_ctx* ctx) -> std::vector<Banded> {
+        std::vector<Banded> res(sets.size());
+        for (std::size_t i = 0; i < sets.size(); i++) {
+            Banded& d = res[i];
+            d.consensus.assign(out.cns + out.cns_off[i], out.cns + out.cns_off[i + 1]);
+            d.band_used = out.band_used[i];
+            if (msa)
+                for (std::uint32_t r = 0; r < out.n_rows[i]; r++) {
+                    const char* p = out.msa + out.msa_off[i] + static_cast<std::uint64_t>(r) * out.n_cols[i];
+                    d.rows.emplace_back(p, p + out.n_cols[i]);
+                }
+        }
+        hx_free_band(ctx, &out);
+        return res;
+    });
+}
+inline std::vector<Banded> banded_batch(const std::vector<std::vector<std::string>>& sets, const std::vector<std::vector<std::vector<std::uint8_t>>>& weights, std::uint32_t band,
+                                        AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, std::int8_t q = -8, std::int8_t c = -8,
+                                        bool msa = false, bool include_consensus = false) {
+    return banded_batch(detail::pointers(sets), detail::pointers(weights), band, type, m, n, g, e, q, c, msa, include_consensus);
+}
+
 // Graphviz text of a graph, after spoa's Graph::print_dot: per node `id [label = "id - LETTER"]`, filled for the nodes of the consensus;
 // per out-edge, in out-list order, `from -> to [label = "weight"]`; one dotted line without arrowhead per pair of aligned nodes (nodes that
 // share a column), from the smaller to the larger id

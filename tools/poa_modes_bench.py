@@ -27,7 +27,13 @@ linear scores, unit weights, with the rows and the consensus row; part "strand",
 every member after the first reverse-complemented with probability 1/2: kernel time against the MSA's on the sets as they are, which is
 the same call on the sets oriented beforehand ("over_msa", with the smallest and largest ratio the repeats allow), the sequences whose
 reverse complement won and with them the ratio the DP passes alone predict (2 + third_passes / aligned sequences), and a sample compared
-with the strand restatement (tests/poa_strand_ref.cpp). --rows picks the rows, --only picks the parts to run; --package-root runs the parts another
+with the strand restatement (tests/poa_strand_ref.cpp). --band W [W ...] is a mode of its own: workload (a) under kNW and kOV, linear
+scores, consensus only, through the banded entry (hx_poa_banded) at every half-width W against the full-matrix general path on the same
+sets in the same process: kernel time by the same protocol, the workspace the call left allocated on the device (free memory before and
+after, the workspace released in between; the banded call also reports the plan's own figure), the share of sets that did not finish at
+W (band_used != W: they climbed to a wider band or to the full matrix), the reruns that cost, and the share of sets whose banded consensus
+is the full-matrix one. A package without the banded entry (--package-root of a parent checkout) gives the full-matrix figures alone.
+--rows picks the rows, --only picks the parts to run; --package-root runs the parts another
 build of the package has (a checkout of the parent commit, say) in the same way, for a comparison on one machine. Prints one JSON line,
 and writes it to --out when given."""
 import argparse
@@ -113,6 +119,59 @@ def wall_stats(wall):
     return {"wall_ms_median": round(float(np.median(wall)), 2), "wall_ms_min": round(min(wall), 2), "wall_ms_max": round(max(wall), 2)}
 
 
+def device_free_bytes():
+    import ctypes
+    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    if ctypes.CDLL("libamdhip64.so").hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) != 0:
+        raise RuntimeError("hipMemGetInfo failed")
+    return free.value
+
+
+def band_mode(a, hip):
+    rng = np.random.default_rng(a.seed)
+    workload_a(rng, a.sets_a, True)   # (the kSW sets come first in the generator's sequence: the kNW / kOV sets are those of the other rows)
+    sets = workload_a(rng, a.sets_a, False)
+    ctx = hip.HipContext(0)
+    has_band = hasattr(hip.HipContext, "poa_banded")
+    res = {"tool": "poa_modes_bench", "mode": "band", "seed": a.seed, "repeats": a.repeats, "sets": len(sets), "bands": list(a.band) if has_band else [],
+           "longest_sequence": max(len(q) for st in sets for q in st), "bases": sum(len(q) for st in sets for q in st)}
+
+    def timed(fn):
+        ctx.poa_release_workspace()
+        before = device_free_bytes()
+        ms, wall = gpu_time(ctx, fn, a.repeats)
+        held = before - device_free_bytes()
+        med = float(np.median(ms))
+        out = {"kernel_ms_median": round(med, 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2), "workspace_bytes_held": int(held)}
+        out.update(wall_stats(wall))
+        return out
+    for mode in ("nw", "ov"):
+        r = {}
+        with ctx.options(poa_general=1):
+            full_cns, st = ctx.poa_sequences_mode(sets, mode, stats=True)
+            r["full"] = timed(lambda: ctx.poa_sequences_mode(sets, mode))
+        r["full"].update({"cells": int(st["dp_cells"]), "gcups": round(st["dp_cells"] / r["full"]["kernel_ms_median"] / 1e6, 2)})
+        note("band", mode, "full", r["full"]["kernel_ms_median"], "ms")
+        for w in (a.band if has_band else []):
+            recs, st = ctx.poa_banded(sets, w, type=mode, stats=True)
+            b = timed(lambda: ctx.poa_banded(sets, w, type=mode))
+            other = sum(rec.band_used != w for rec in recs)
+            b.update({"cells": int(st["dp_cells"]), "workspace_bytes_planned": int(st["workspace_bytes"]), "band_reruns": int(st["band_reruns"]), "slot_reruns": int(st["slot_reruns"]),
+                      "sets_not_at_w": int(other), "share_not_at_w": round(other / len(sets), 4), "sets_on_full_matrix": int(sum(rec.band_used == 0 for rec in recs)),
+                      "share_consensus_equal_full": round(sum(rec.consensus == c for rec, c in zip(recs, full_cns)) / len(sets), 4),
+                      "over_full": round(b["kernel_ms_median"] / r["full"]["kernel_ms_median"], 4), "over_full_min": round(b["kernel_ms_min"] / r["full"]["kernel_ms_max"], 4),
+                      "over_full_max": round(b["kernel_ms_max"] / r["full"]["kernel_ms_min"], 4),
+                      "workspace_over_full": round(b["workspace_bytes_held"] / max(1, r["full"]["workspace_bytes_held"]), 4)})
+            r["band_%d" % w] = b
+            note("band", mode, w, b["kernel_ms_median"], "ms")
+        res["a_" + mode] = r
+    ctx.close()
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sets-a", type=int, default=256)
@@ -125,10 +184,13 @@ def main():
     ap.add_argument("--only", nargs="+", default=PARTS, choices=PARTS, help="the parts of every row to run (outputs: the MSA and the weighted entry, which need general; ratios are given against the parts that ran)")
     ap.add_argument("--rows", nargs="+", default=["a_sw", "a_nw", "a_ov", "b_ov"], choices=["a_sw", "a_nw", "a_ov", "b_ov"], help="the rows to run")
     ap.add_argument("--package-root", default=ROOT, help="the tree whose built haslr_amd package runs (default: this one); parts it does not have are left out")
+    ap.add_argument("--band", type=int, nargs="+", metavar="W", help="the band mode: workload (a) under kNW and kOV through hx_poa_banded at these half-widths, against the full-matrix general path")
     ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.package_root))
     from haslr_amd import hip
+    if a.band:
+        return band_mode(a, hip)
     import cvxlib
     import msalib
     import parlib
