@@ -20,8 +20,8 @@
 //     (tagged mailboxes in LDS between waves, one tagged word per row in HBM between members, no barrier inside the DP). Rows needed
 //     later as non-adjacent predecessors live in an LDS ring, the overflow in HBM. The row loop is written against what ONE wave alone on
 //     its SIMD pays per instruction kind (tools/dev_lonebench.hip): scalar flags, one test for the rare cases, buffer-resource stores.
-//   * traceback: the first wavefront walks 32x16 tiles of direction nibbles with v_readlane; a second wavefront, where the workgroup has
-//     one, touches the lines the walk reaches next (cache warm-up only)
+//   * traceback: the first wavefront walks tiles of 64 rows x 32 columns of direction nibbles with v_readlane (4 columns per lane and fewer: off a table of next
+//     rows that all lanes build per tile); a second wavefront, where the workgroup has one, touches the lines the walk reaches next (cache warm-up only)
 //   * graph update (spoa add_alignment), order update and the rank-ordered CSR rebuild run on all lanes (prefix sums for the ids the
 //     serial walk would hand out); the reference's DFS topological sort runs only for end-node ties that a column cannot decide and
 //     for heaviest bundles that do not end in a unique sink (one wavefront in lock step, on ranks).
@@ -59,6 +59,44 @@ namespace {
         if (((Lq) + 1 + GM * NP * DL - 1) / (GM * NP * DL) <= (uint32_t)CM) {    /* the host puts an edge into a launch whose columns per lane hold its longest sequence */ \
             dp_rows<CM, DIR, PRUNE, MAXNT == 64>(g, H, Dm, Dw, W, WH, seq, Lq, Vq, ring, R, ring_w, match, mismatch, gap, wmail.box, wmail.consumed, sink_row, sink_score, SINK_LDS, nsq, cl, ph + PW_BUILD0, Tq, (prune_pct >> 16) & 1u, ph + PW_PRUNE0, ED.hrows); \
         } else sOk = ES_INTERNAL; } while (0)
+
+// The traceback's walk on a tile's table of next rows (poa_edge, the direction-nibble traceback), written out: 32 steps, one per column of the tile, each on its own
+// register and byte of the table (registers 2k / 2k + 1: the even / odd columns of nibble word k), so that a step is seven instructions -
+//     v_readlane (the table word of row RA), s_bfe (this column's byte -> RB), s_cmp + s_cbranch (a flag is set), s_or + v_writelane (the entry: row | (column + 2) << 6
+//     into lane M0 of rec), s_add (M0)
+// and the row number goes from one scalar to the other and back (RA / RB swap from step to step: no copy). M0 is saved, holds the entry's lane throughout and is
+// restored (the compiler reserves it). A vertical move (bit 6) records, takes its row and repeats its column's step while fewer than 32 entries wait; a flagged byte
+// (bit 7), or a vertical move with 32 entries waiting, ends the walk with the byte in x, its column in c and its row in dr; behind column 0, x = 0.
+// Entries: at most 31 wait at the entry, vertical moves add up to 32, the columns at most 32 more: lanes 0..63.
+// (Wait states: the lane select of a v_readlane is written by an s_bfe five instructions earlier or by an s_and / s_mov two instructions earlier - scalar writes, which
+// need none; M0 is written at least five instructions before the v_writelane that reads it, behind the first s_mov a s_nop stands.)
+#define HX_WS(C, T, OFF, RA, RB) \
+    "Ls" #C "_%=:\n\tv_readlane_b32 %[x], %[" T "], %[" RA "]\n\ts_bfe_u32 %[" RB "], %[x], " #OFF "|0x80000\n\ts_cmp_lt_u32 %[" RB "], 64\n\ts_cbranch_scc0 Lx" #C "_%=\n\t" \
+    "s_or_b32 %[w], %[" RA "], (" #C "+2)<<6\n\tv_writelane_b32 %[rec], %[w], m0\n\ts_add_u32 m0, m0, 1\n"
+#define HX_WX(C, RA, RB) \
+    "Lx" #C "_%=:\n\ts_bitcmp1_b32 %[" RB "], 7\n\ts_cbranch_scc1 Ld" #C "_%=\n\ts_cmp_lt_u32 m0, 32\n\ts_cbranch_scc0 Ld" #C "_%=\n\t" \
+    "s_or_b32 %[w], %[" RA "], (" #C "+2)<<6\n\tv_writelane_b32 %[rec], %[w], m0\n\ts_add_u32 m0, m0, 1\n\ts_and_b32 %[" RA "], %[" RB "], 63\n\ts_branch Ls" #C "_%=\n" \
+    "Ld" #C "_%=:\n\ts_mov_b32 %[x], %[" RB "]\n\ts_mov_b32 %[dr], %[" RA "]\n\ts_movk_i32 %[c], " #C "\n\ts_branch Lend_%=\n"
+// (an odd column has its row in dr and leaves the next in drb, an even column the other way round; a walk that enters at an even column moves its row over first)
+#define HX_WE(C) "Le" #C "_%=:\n\ts_mov_b32 %[drb], %[dr]\n\ts_branch Ls" #C "_%=\n"
+#define HX_WPAIR(CO, CE, TO, TE, OFF) HX_WS(CO, TO, OFF, "dr", "drb") HX_WS(CE, TE, OFF, "drb", "dr")
+#define HX_WXPAIR(CO, CE) HX_WX(CO, "dr", "drb") HX_WX(CE, "drb", "dr") HX_WE(CE)
+#define HX_WGO(C, L) "s_cmp_eq_u32 %[c], " #C "\n\ts_cbranch_scc1 " L #C "_%=\n\t"
+#define HX_WALK_ASM \
+    "s_mov_b32 %[keep], m0\n\ts_mov_b32 m0, %[el]\n\ts_nop 0\n\t" \
+    "s_cmp_lt_u32 %[c], 8\n\ts_cbranch_scc1 Lg0_%=\n\ts_cmp_lt_u32 %[c], 16\n\ts_cbranch_scc1 Lg1_%=\n\ts_cmp_lt_u32 %[c], 24\n\ts_cbranch_scc1 Lg2_%=\n\t" \
+    HX_WGO(31, "Ls") HX_WGO(30, "Le") HX_WGO(29, "Ls") HX_WGO(28, "Le") HX_WGO(27, "Ls") HX_WGO(26, "Le") HX_WGO(25, "Ls") "s_branch Le24_%=\n" \
+    "Lg2_%=:\n\t" HX_WGO(23, "Ls") HX_WGO(22, "Le") HX_WGO(21, "Ls") HX_WGO(20, "Le") HX_WGO(19, "Ls") HX_WGO(18, "Le") HX_WGO(17, "Ls") "s_branch Le16_%=\n" \
+    "Lg1_%=:\n\t" HX_WGO(15, "Ls") HX_WGO(14, "Le") HX_WGO(13, "Ls") HX_WGO(12, "Le") HX_WGO(11, "Ls") HX_WGO(10, "Le") HX_WGO(9, "Ls") "s_branch Le8_%=\n" \
+    "Lg0_%=:\n\t" HX_WGO(7, "Ls") HX_WGO(6, "Le") HX_WGO(5, "Ls") HX_WGO(4, "Le") HX_WGO(3, "Ls") HX_WGO(2, "Le") HX_WGO(1, "Ls") "s_branch Le0_%=\n" \
+    HX_WPAIR(31, 30, "t7", "t6", 24) HX_WPAIR(29, 28, "t7", "t6", 16) HX_WPAIR(27, 26, "t7", "t6", 8) HX_WPAIR(25, 24, "t7", "t6", 0) \
+    HX_WPAIR(23, 22, "t5", "t4", 24) HX_WPAIR(21, 20, "t5", "t4", 16) HX_WPAIR(19, 18, "t5", "t4", 8) HX_WPAIR(17, 16, "t5", "t4", 0) \
+    HX_WPAIR(15, 14, "t3", "t2", 24) HX_WPAIR(13, 12, "t3", "t2", 16) HX_WPAIR(11, 10, "t3", "t2", 8) HX_WPAIR(9, 8, "t3", "t2", 0) \
+    HX_WPAIR(7, 6, "t1", "t0", 24) HX_WPAIR(5, 4, "t1", "t0", 16) HX_WPAIR(3, 2, "t1", "t0", 8) HX_WPAIR(1, 0, "t1", "t0", 0) \
+    "\ts_mov_b32 %[x], 0\n\ts_branch Lend_%=\n" \
+    HX_WXPAIR(31, 30) HX_WXPAIR(29, 28) HX_WXPAIR(27, 26) HX_WXPAIR(25, 24) HX_WXPAIR(23, 22) HX_WXPAIR(21, 20) HX_WXPAIR(19, 18) HX_WXPAIR(17, 16) \
+    HX_WXPAIR(15, 14) HX_WXPAIR(13, 12) HX_WXPAIR(11, 10) HX_WXPAIR(9, 8) HX_WXPAIR(7, 6) HX_WXPAIR(5, 4) HX_WXPAIR(3, 2) HX_WXPAIR(1, 0) \
+    "Lend_%=:\n\ts_mov_b32 %[el], m0\n\ts_mov_b32 m0, %[keep]"
 
 // One kernel per (largest workgroup, columns per lane, traceback flavour): the register budget of a launch is that of ITS row loop, so the
 // many short gaps (one wavefront, 4-8 columns per lane) run with a fraction of the registers - and several times the waves per SIMD - of
@@ -404,13 +442,16 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
             if (DIR) {
                 // Direction bytes: the first wavefront walks the path together. A tile of 64 rows x 32 columns of direction nibbles (four registers)
                 // and the records of those 32 rows are fetched with one round of loads; the walk inside the tile runs on v_readlane, i.e. one
-                // memory round trip per ~12 steps instead of 3-4 dependent ones per step. Ranks are turned into node ids by all lanes afterwards.
+                // memory round trip per ~33 steps instead of 3-4 dependent ones per step. Ranks are turned into node ids by all lanes afterwards.
+                // Where a lane has at most 4 columns all lanes first decode the tile into a table of next rows, a byte per cell, and the walk's step is a lane read
+                // and a test (HX_WALK_ASM); the instances of 8 and more columns per lane decode the nibble per step.
                 if (tid < 64) {
                     const uint32_t ln = tid;
                     if (ln == 0) sCells += (unsigned long long)V * L;
                     uint32_t i = (uint32_t)__builtin_amdgcn_readfirstlane(sBestI), j = L, na = 0;
                     // The walk records the cell it stands on, (rank, column), before every move: entry n in lane n % 64 of two registers
-                    // (v_writelane), 64 entries leave with one coalesced store each. What the alignment wants - "node or nothing, position or
+                    // (v_writelane), 64 entries leave with one coalesced store each (the table walk: one word per entry, tile-relative, expanded when
+                    // it is stored - at 32 entries and at the tile's end). What the alignment wants - "node or nothing, position or
                     // nothing" - is a comparison of neighbouring entries and is made by all lanes afterwards.
                     int pn = 0, pp = 0;
                     uint32_t nwalk = 0, iend = 0, jend = 0;   // entries of the walk proper, and where it stopped
@@ -421,7 +462,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                         // arrays have 64 entries of slack for the tile that runs over: need_of)
                         if (__builtin_expect(na > V + L + 2u, 0)) { if (ln == 0) sOk = ES_INTERNAL; break; }
                         if (i == 0) {   // only horizontal moves are left in the virtual row: written in their final form
-                            if (na & 63u) { const uint32_t base = na & ~63u; if (ln < na - base) { g.aln_node[base + ln] = pn; g.aln_pos[base + ln] = pp; } }
+                            if constexpr (CM > 4) { if (na & 63u) { const uint32_t base = na & ~63u; if (ln < na - base) { g.aln_node[base + ln] = pn; g.aln_pos[base + ln] = pp; } } }   // (the table walk stores its entries tile by tile)
                             tail = true;
                             nwalk = na; iend = 0; jend = j;
                             for (uint32_t q = ln; q < j; q += 64) { g.aln_node[na + q] = -1; g.aln_pos[na + q] = (int32_t)(j - 1 - q); }
@@ -435,73 +476,183 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
                         const uint32_t ti = i, ct = j | 1u;
                         if (NT > 64 && ln == 0) { st_wg(&lds_u[WALK_AT_I], ti); st_wg(&lds_u[WALK_AT_J], ct); }   // (where the walk is: the helper wave fetches ahead of it)
                         const int32_t bs = ((int32_t)ct - 31) >> 1;   // first byte of the tile in its rows (ct < 31: negative - bytes before the row, never looked at)
-                        uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0, mt = 0, pv0 = 0, pv1 = 0, qo = 0, qw = 0;
-                        if (ti > ln) {
-                            // four unaligned dword loads per lane (bytes bs .. bs + 15 of the row; columns below 0 read the end of the previous row - row 0 exists)
-                            const uint8_t* rowp = Dm + (uint64_t)(ti - ln) * (W >> 1) + bs;
-                            __builtin_memcpy(&w0, rowp, 4); __builtin_memcpy(&w1, rowp + 4, 4); __builtin_memcpy(&w2, rowp + 8, 4); __builtin_memcpy(&w3, rowp + 12, 4);
-                            // the records of the tile's rows: where a move into the first / second predecessor leads
-                            const uint32_t rr = ti - 1 - ln;
-                            mt = g.row_meta[rr]; qo = g.row_pred_off[rr]; if (mt & 32u) qw = g.wslot[rr];
-                            pv0 = (mt >> META_NP) == 0 ? 0u : (g.row_pred0[rr] & 0x0fffffffu) + 1;   // (a source node continues in the virtual row 0)
-                            pv1 = (g.row_pred1[rr] & 0x0fffffffu) + 1;
-                        }
-                        uint32_t ilo = ti > 63u ? ti - 63u : 1u;                       // the walk goes on while i >= ilo (rows of the tile, never row 0) ...
-                        asm volatile("" : "+s"(ilo));                                // (... as ONE subtraction per step: the compiler otherwise takes the constant apart again)
-                        const int32_t jb0 = 2 * bs;                                  // ... and j >= first column of the tile
-                        // (bit dr: the tile's row dr has more than 4 predecessors - a scalar bit test per step instead of a readlane of the row's record)
-                        const unsigned long long wmask = __ballot((mt & 32u) != 0);
-                        if (mt & 32u) { w0 = 0x88888888u; w1 = 0x88888888u; w2 = 0x88888888u; w3 = 0x88888888u; }   // a row with more than 4 predecessors: every cell reads as code 8, one of the rare moves - its real move is in the wide-row pool
-                        for (;;) {
-                            const uint32_t dr = ti - i, jb = (uint32_t)((int32_t)j - jb0);   // row and column inside the tile (0..63, 0..31)
-                            const uint32_t wsa = (uint32_t)__builtin_amdgcn_readlane((int)w0, (int)dr), wsb = (uint32_t)__builtin_amdgcn_readlane((int)w1, (int)dr);
-                            const uint32_t wsc = (uint32_t)__builtin_amdgcn_readlane((int)w2, (int)dr), wsd = (uint32_t)__builtin_amdgcn_readlane((int)w3, (int)dr);
-                            const uint32_t wsh = ((jb & 16u) ? ((jb & 8u) ? wsd : wsc) : ((jb & 8u) ? wsb : wsa)) >> (4 * (jb & 7u));   // the cell's code in bits 0-3
-                            const uint32_t n4 = wsh & 15u;
-                            // move code: type (3 diagonal / 2 vertical / 1 horizontal) * 4 + 3 - predecessor slot; a row with more than 4 predecessors
-                            // keeps type * 16 + 15 - slot in the wide-row pool
-                            // (a move into the third or a later predecessor - codes 8, 9, 12, 13 of a 4-bit row - has to fetch that predecessor's rank)
-                            const uint32_t pva = (uint32_t)__builtin_amdgcn_readlane((int)pv0, (int)dr), pvb = (uint32_t)__builtin_amdgcn_readlane((int)pv1, (int)dr);
-                            // What the step waits for is its chain of DEPENDENT instructions from one (row, column) to the next, ~20 cycles each for a lone wave
-                            // (docs/poa_kernel_notes.md); the compiler spends 7 on "which row next" and 5 on "which column next". Spelled out, 4 and 3:
-                            //   row:    not slot 0 (a low bit of the code clear)? second predecessor : first; bit 3 (types 2 and 3: the move leaves the row)? that : this row
-                            //   column: type 2 (bits 3-2 = 10: vertical)? this column : one to the left
-                            uint32_t ni, nj;
-                            asm("s_andn2_b32 %0, 3, %2\n\ts_cselect_b32 %0, %4, %3\n\ts_bitcmp1_b32 %2, 3\n\ts_cselect_b32 %0, %0, %5\n\t"
-                                "s_and_b32 %1, %2, 12\n\ts_cmp_lg_u32 %1, 8\n\ts_subb_u32 %1, %6, 0"
-                                : "=&s"(ni), "=&s"(nj) : "s"(wsh), "s"(pva), "s"(pvb), "s"(i), "s"(j) : "scc");
-                            if (__builtin_expect((n4 & 10u) == 8u, 0)) {   // ONE test for the rare moves: codes 8, 9, 12, 13 = a third or later predecessor, or (code 8 by the line above the loop) a wide row
-                                uint32_t type = n4 >> 2, slot = 3u - (n4 & 3u), later = 1u, pv = slot == 0 ? pva : pvb;
-                                if ((uint32_t)(wmask >> dr) & 1u) {
-                                    const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)Dw[(uint64_t)__builtin_amdgcn_readlane((int)qw, (int)dr) * W + j]);
-                                    type = d >> 4; slot = 15u - (d & 15u); later = slot >= 2 && type > 1u;
-                                    pv = slot == 0 ? pva : pvb;
-                                }
-                                if (later != 0)
-                                    pv = ((uint32_t)__builtin_amdgcn_readfirstlane((int)g.pred_rank[(uint32_t)__builtin_amdgcn_readlane((int)qo, (int)dr) + slot]) & 0x0fffffffu) + 1;
-                                ni = type > 1u ? pv : i;          // (a horizontal move is type 1 from the int32 rows, type 0 from the packed ones)
-                                nj = j - (uint32_t)(type != 2u);  // (horizontal and diagonal moves go a column to the left, a vertical one does not)
+                        // (the table walk where a lane has at most 4 columns - the instances that run the longest chains; the instances of 8 and more columns
+                        //  per lane are capped at 128 registers and spill already: with the table two of the 256-lane ones took 16 bytes more scratch per lane, so they
+                        //  keep the walk that decodes per step)
+                        if constexpr (CM <= 4) {
+                            uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0, mt = 0, pv0 = 0, pv1 = 0;
+                            if (ti > ln) {
+                                // four unaligned dword loads per lane (bytes bs .. bs + 15 of the row; columns below 0 read the end of the previous row - row 0 exists)
+                                const uint8_t* rowp = Dm + (uint64_t)(ti - ln) * (W >> 1) + bs;
+                                __builtin_memcpy(&w0, rowp, 4); __builtin_memcpy(&w1, rowp + 4, 4); __builtin_memcpy(&w2, rowp + 8, 4); __builtin_memcpy(&w3, rowp + 12, 4);
+                                // the records of the tile's rows: where a move into the first / second predecessor leads
+                                const uint32_t rr = ti - 1 - ln;
+                                mt = g.row_meta[rr];
+                                pv0 = (mt >> META_NP) == 0 ? 0u : (g.row_pred0[rr] & 0x0fffffffu) + 1;   // (a source node continues in the virtual row 0)
+                                pv1 = (g.row_pred1[rr] & 0x0fffffffu) + 1;
                             }
+                            uint32_t ilo = ti > 63u ? ti - 63u : 1u;                       // the walk goes on while i >= ilo (rows of the tile, never row 0) ...
+                            asm volatile("" : "+s"(ilo));                                // (... as ONE subtraction per step: the compiler otherwise takes the constant apart again)
+                            const int32_t jb0 = 2 * bs;                                  // ... and j >= first column of the tile
+                            // (bit dr: the tile's row dr has more than 4 predecessors - a scalar bit test per step instead of a readlane of the row's record)
+                            const unsigned long long wmask = __ballot((mt & 32u) != 0);
+                            if (mt & 32u) { w0 = 0x88888888u; w1 = 0x88888888u; w2 = 0x88888888u; w3 = 0x88888888u; }   // a row with more than 4 predecessors: every cell reads as code 8, one of the rare moves - its real move is in the wide-row pool
+                            // The table of next rows: a byte per cell of the tile = the row inside the tile its move leads to (0..63) | 0x40 "the column stays" (a
+                            // vertical move) | 0x80 "not here": the target is outside the tile or the virtual row 0, the move goes into a third or later predecessor,
+                            // the row has more than 4 predecessors, the lane has no row. Every lane decodes its own row - per-tile, data-parallel work - so that the
+                            // walk's serial step is a lane read, a byte at a static offset and one test. A lane has eight bytes that are not "this row, a column to the
+                            // left", those of codes 8..15: laid out once (lut_lo: codes 8-11, lut_hi: 12-15) and picked with v_perm_b32 by the nibbles themselves
+                            // (bit 3 flipped, so codes 8..15 are selectors 0..7); a second v_perm_b32 puts "this row" where bit 3 was clear. Register 2k holds the even
+                            // columns of word k, 2k + 1 the odd ones.
+                            uint32_t tb0, tb1, tb2, tb3, tb4, tb5, tb6, tb7;
                             {
-                                const int el = (int)(na & 63u);
-                                // (M0 is saved and restored around the two v_writelane: the compiler reserves it - an earlier version that listed it as a
-                                //  clobber broke the one kernel instance that spills heavily, k_poa<1024, 32, true>: memory faults / wrong consensus for
-                                //  gaps above 16 383 columns in ONE workgroup, found by the round-3 fuzz)
-                                int m0_keep;
-                                asm volatile("s_mov_b32 %2, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tv_writelane_b32 %0, %4, m0\n\tv_writelane_b32 %1, %5, m0\n\ts_mov_b32 m0, %2"
-                                             : "+v"(pn), "+v"(pp), "=&s"(m0_keep) : "s"(el), "s"(i), "s"(j));
+                                const bool plain = ti > ln && !(mt & 32u);
+                                const uint32_t t0 = ti - pv0, t1 = ti - pv1;   // (rows inside the tile of the first two predecessors; a target at or above the lane's own row is no move)
+                                const uint32_t b0 = plain && pv0 != 0 && t0 > ln && t0 < 64u ? t0 : 0x80u, b1 = plain && pv1 != 0 && t1 > ln && t1 < 64u ? t1 : 0x80u;
+                                const uint32_t lut_lo = 0x40408080u | (b1 << 16) | (b0 << 24), lut_hi = 0x00008080u | (b1 << 16) | (b0 << 24);
+                                const uint32_t hrow = plain ? ln * 0x01010101u : 0x80808080u;
+                                auto cells = [&](uint32_t w, uint32_t& even, uint32_t& odd) {
+                                    const uint32_t x = w ^ 0x88888888u;
+                                    const uint32_t re = __builtin_amdgcn_perm(lut_hi, lut_lo, x & 0x0f0f0f0fu), ro = __builtin_amdgcn_perm(lut_hi, lut_lo, (x >> 4) & 0x0f0f0f0fu);
+                                    even = __builtin_amdgcn_perm(hrow, re, ((x >> 1) & 0x04040404u) | 0x03020100u);
+                                    odd = __builtin_amdgcn_perm(hrow, ro, ((x >> 5) & 0x04040404u) | 0x03020100u);
+                                };
+                                cells(w0, tb0, tb1); cells(w1, tb2, tb3); cells(w2, tb4, tb5); cells(w3, tb6, tb7);
                             }
-                            if (__builtin_expect((na & 63u) == 63u, 0)) {   // 64 entries: out they go (a store per step cost more than the step itself)
-                                asm volatile("" ::: "memory");
-                                g.aln_node[na - 63 + ln] = pn; g.aln_pos[na - 63 + ln] = pp;
+                            // The walk on the table (HX_WALK_ASM above the function): a step per column, spelled out on its register and offset; it records one word per
+                            // step - the row inside the tile | (column inside the tile + 2) << 6 - in lane `el` of `rec` and comes back with the byte it cannot
+                            // take: a flagged cell (the full step below), a vertical move with 32 entries waiting (they leave, and the walk goes on), or 0 behind the
+                            // tile's first column. The entries leave as (rank, column) at 32 and at the tile's end: `ti` and `jb0` are the tile's.
+                            uint32_t rec = 0, el = 0, dr = 0, c = (uint32_t)((int32_t)j - jb0);   // (c: the column inside the tile, 30 or 31 at the tile's entry)
+                            auto flush = [&]() {
+                                if (ln < el) { g.aln_node[na - el + ln] = (int32_t)(ti - (rec & 63u)); g.aln_pos[na - el + ln] = jb0 + (int32_t)(rec >> 6) - 2; }
+                                el = 0;
+                            };
+                            for (;;) {
+                                if (el >= 32u) flush();
+                                uint32_t x, drb, wrd, m0_keep;
+                                const uint32_t e0 = el;
+                                asm volatile(HX_WALK_ASM
+                                             : [rec] "+v"(rec), [dr] "+s"(dr), [c] "+s"(c), [el] "+s"(el), [x] "=&s"(x), [drb] "=&s"(drb), [w] "=&s"(wrd), [keep] "=&s"(m0_keep)
+                                             : [t0] "v"(tb0), [t1] "v"(tb1), [t2] "v"(tb2), [t3] "v"(tb3), [t4] "v"(tb4), [t5] "v"(tb5), [t6] "v"(tb6), [t7] "v"(tb7)
+                                             : "scc");
+                                na += el - e0;
+                                i = ti - dr;
+                                if (x == 0) { j = (uint32_t)(jb0 - 1); break; }   // left the tile through its first column
+                                j = (uint32_t)(jb0 + (int32_t)c);
+                                if (!(x & 0x80u)) continue;                      // (a vertical move, and 32 entries wait)
+                                // the full step: a cell the table does not answer (rare)
+                                const uint32_t wsa = (uint32_t)__builtin_amdgcn_readlane((int)w0, (int)dr), wsb = (uint32_t)__builtin_amdgcn_readlane((int)w1, (int)dr);
+                                const uint32_t wsc = (uint32_t)__builtin_amdgcn_readlane((int)w2, (int)dr), wsd = (uint32_t)__builtin_amdgcn_readlane((int)w3, (int)dr);
+                                const uint32_t wsh = ((c & 16u) ? ((c & 8u) ? wsd : wsc) : ((c & 8u) ? wsb : wsa)) >> (4 * (c & 7u));   // the cell's code in bits 0-3
+                                const uint32_t n4 = wsh & 15u;
+                                // move code: type (3 diagonal / 2 vertical / 1 horizontal) * 4 + 3 - predecessor slot; a row with more than 4 predecessors
+                                // keeps type * 16 + 15 - slot in the wide-row pool
+                                // (a move into the third or a later predecessor - codes 8, 9, 12, 13 of a 4-bit row - has to fetch that predecessor's rank)
+                                const uint32_t pva = (uint32_t)__builtin_amdgcn_readlane((int)pv0, (int)dr), pvb = (uint32_t)__builtin_amdgcn_readlane((int)pv1, (int)dr);
+                                //   row:    not slot 0 (a low bit of the code clear)? second predecessor : first; bit 3 (types 2 and 3: the move leaves the row)? that : this row
+                                //   column: type 2 (bits 3-2 = 10: vertical)? this column : one to the left
+                                uint32_t ni, nj;
+                                asm("s_andn2_b32 %0, 3, %2\n\ts_cselect_b32 %0, %4, %3\n\ts_bitcmp1_b32 %2, 3\n\ts_cselect_b32 %0, %0, %5\n\t"
+                                    "s_and_b32 %1, %2, 12\n\ts_cmp_lg_u32 %1, 8\n\ts_subb_u32 %1, %6, 0"
+                                    : "=&s"(ni), "=&s"(nj) : "s"(wsh), "s"(pva), "s"(pvb), "s"(i), "s"(j) : "scc");
+                                if (__builtin_expect((n4 & 10u) == 8u, 0)) {   // ONE test for the rare moves: codes 8, 9, 12, 13 = a third or later predecessor, or (code 8 by the line above the table) a wide row
+                                    uint32_t type = n4 >> 2, slot = 3u - (n4 & 3u), later = 1u, pv = slot == 0 ? pva : pvb;
+                                    if ((uint32_t)(wmask >> dr) & 1u) {
+                                        const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)Dw[(uint64_t)g.wslot[i - 1] * W + j]);
+                                        type = d >> 4; slot = 15u - (d & 15u); later = slot >= 2 && type > 1u;
+                                        pv = slot == 0 ? pva : pvb;
+                                    }
+                                    if (later != 0)
+                                        pv = ((uint32_t)__builtin_amdgcn_readfirstlane((int)g.pred_rank[g.row_pred_off[i - 1] + slot]) & 0x0fffffffu) + 1;
+                                    ni = type > 1u ? pv : i;          // (a horizontal move is type 1 from the int32 rows, type 0 from the packed ones)
+                                    nj = j - (uint32_t)(type != 2u);  // (horizontal and diagonal moves go a column to the left, a vertical one does not)
+                                }
+                                {
+                                    if (el >= 32u) flush();
+                                    // (M0 is saved and restored around the v_writelane: the compiler reserves it - an earlier version that listed it as a
+                                    //  clobber broke the one kernel instance that spills heavily, k_poa<1024, 32, true>: memory faults / wrong consensus for
+                                    //  gaps above 16 383 columns in ONE workgroup, found by the round-3 fuzz)
+                                    uint32_t keep;
+                                    const uint32_t word = dr | ((c + 2u) << 6);
+                                    asm volatile("s_mov_b32 %1, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %3, m0\n\ts_mov_b32 m0, %1"
+                                                 : "+v"(rec), "=&s"(keep) : "s"(el), "s"(word));
+                                    el++; na++;
+                                }
+                                i = ni; j = nj;
+                                if ((int32_t)((i - ilo) | (uint32_t)((int32_t)j - jb0)) < 0) break;   // left the tile's rows or columns
+                                dr = ti - i; c = (uint32_t)((int32_t)j - jb0);                        // still inside: back to the table, at this column
                             }
-                            na++;
-                            i = ni; j = nj;
-                            if ((int32_t)((i - ilo) | (uint32_t)((int32_t)j - jb0)) < 0) break;   // left the tile's rows or columns
+                            flush();
+                        } else {
+                            uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0, mt = 0, pv0 = 0, pv1 = 0, qo = 0, qw = 0;
+                            if (ti > ln) {
+                                // four unaligned dword loads per lane (bytes bs .. bs + 15 of the row; columns below 0 read the end of the previous row - row 0 exists)
+                                const uint8_t* rowp = Dm + (uint64_t)(ti - ln) * (W >> 1) + bs;
+                                __builtin_memcpy(&w0, rowp, 4); __builtin_memcpy(&w1, rowp + 4, 4); __builtin_memcpy(&w2, rowp + 8, 4); __builtin_memcpy(&w3, rowp + 12, 4);
+                                // the records of the tile's rows: where a move into the first / second predecessor leads
+                                const uint32_t rr = ti - 1 - ln;
+                                mt = g.row_meta[rr]; qo = g.row_pred_off[rr]; if (mt & 32u) qw = g.wslot[rr];
+                                pv0 = (mt >> META_NP) == 0 ? 0u : (g.row_pred0[rr] & 0x0fffffffu) + 1;   // (a source node continues in the virtual row 0)
+                                pv1 = (g.row_pred1[rr] & 0x0fffffffu) + 1;
+                            }
+                            uint32_t ilo = ti > 63u ? ti - 63u : 1u;                       // the walk goes on while i >= ilo (rows of the tile, never row 0) ...
+                            asm volatile("" : "+s"(ilo));                                // (... as ONE subtraction per step: the compiler otherwise takes the constant apart again)
+                            const int32_t jb0 = 2 * bs;                                  // ... and j >= first column of the tile
+                            // (bit dr: the tile's row dr has more than 4 predecessors - a scalar bit test per step instead of a readlane of the row's record)
+                            const unsigned long long wmask = __ballot((mt & 32u) != 0);
+                            if (mt & 32u) { w0 = 0x88888888u; w1 = 0x88888888u; w2 = 0x88888888u; w3 = 0x88888888u; }   // a row with more than 4 predecessors: every cell reads as code 8, one of the rare moves - its real move is in the wide-row pool
+                            for (;;) {
+                                const uint32_t dr = ti - i, jb = (uint32_t)((int32_t)j - jb0);   // row and column inside the tile (0..63, 0..31)
+                                const uint32_t wsa = (uint32_t)__builtin_amdgcn_readlane((int)w0, (int)dr), wsb = (uint32_t)__builtin_amdgcn_readlane((int)w1, (int)dr);
+                                const uint32_t wsc = (uint32_t)__builtin_amdgcn_readlane((int)w2, (int)dr), wsd = (uint32_t)__builtin_amdgcn_readlane((int)w3, (int)dr);
+                                const uint32_t wsh = ((jb & 16u) ? ((jb & 8u) ? wsd : wsc) : ((jb & 8u) ? wsb : wsa)) >> (4 * (jb & 7u));   // the cell's code in bits 0-3
+                                const uint32_t n4 = wsh & 15u;
+                                // move code: type (3 diagonal / 2 vertical / 1 horizontal) * 4 + 3 - predecessor slot; a row with more than 4 predecessors
+                                // keeps type * 16 + 15 - slot in the wide-row pool
+                                // (a move into the third or a later predecessor - codes 8, 9, 12, 13 of a 4-bit row - has to fetch that predecessor's rank)
+                                const uint32_t pva = (uint32_t)__builtin_amdgcn_readlane((int)pv0, (int)dr), pvb = (uint32_t)__builtin_amdgcn_readlane((int)pv1, (int)dr);
+                                // What the step waits for is its chain of DEPENDENT instructions from one (row, column) to the next, ~20 cycles each for a lone wave
+                                // (docs/poa_kernel_notes.md); the compiler spends 7 on "which row next" and 5 on "which column next". Spelled out, 4 and 3:
+                                //   row:    not slot 0 (a low bit of the code clear)? second predecessor : first; bit 3 (types 2 and 3: the move leaves the row)? that : this row
+                                //   column: type 2 (bits 3-2 = 10: vertical)? this column : one to the left
+                                uint32_t ni, nj;
+                                asm("s_andn2_b32 %0, 3, %2\n\ts_cselect_b32 %0, %4, %3\n\ts_bitcmp1_b32 %2, 3\n\ts_cselect_b32 %0, %0, %5\n\t"
+                                    "s_and_b32 %1, %2, 12\n\ts_cmp_lg_u32 %1, 8\n\ts_subb_u32 %1, %6, 0"
+                                    : "=&s"(ni), "=&s"(nj) : "s"(wsh), "s"(pva), "s"(pvb), "s"(i), "s"(j) : "scc");
+                                if (__builtin_expect((n4 & 10u) == 8u, 0)) {   // ONE test for the rare moves: codes 8, 9, 12, 13 = a third or later predecessor, or (code 8 by the line above the loop) a wide row
+                                    uint32_t type = n4 >> 2, slot = 3u - (n4 & 3u), later = 1u, pv = slot == 0 ? pva : pvb;
+                                    if ((uint32_t)(wmask >> dr) & 1u) {
+                                        const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)Dw[(uint64_t)__builtin_amdgcn_readlane((int)qw, (int)dr) * W + j]);
+                                        type = d >> 4; slot = 15u - (d & 15u); later = slot >= 2 && type > 1u;
+                                        pv = slot == 0 ? pva : pvb;
+                                    }
+                                    if (later != 0)
+                                        pv = ((uint32_t)__builtin_amdgcn_readfirstlane((int)g.pred_rank[(uint32_t)__builtin_amdgcn_readlane((int)qo, (int)dr) + slot]) & 0x0fffffffu) + 1;
+                                    ni = type > 1u ? pv : i;          // (a horizontal move is type 1 from the int32 rows, type 0 from the packed ones)
+                                    nj = j - (uint32_t)(type != 2u);  // (horizontal and diagonal moves go a column to the left, a vertical one does not)
+                                }
+                                {
+                                    const int el = (int)(na & 63u);
+                                    // (M0 is saved and restored around the two v_writelane: the compiler reserves it - an earlier version that listed it as a
+                                    //  clobber broke the one kernel instance that spills heavily, k_poa<1024, 32, true>: memory faults / wrong consensus for
+                                    //  gaps above 16 383 columns in ONE workgroup, found by the round-3 fuzz)
+                                    int m0_keep;
+                                    asm volatile("s_mov_b32 %2, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tv_writelane_b32 %0, %4, m0\n\tv_writelane_b32 %1, %5, m0\n\ts_mov_b32 m0, %2"
+                                                 : "+v"(pn), "+v"(pp), "=&s"(m0_keep) : "s"(el), "s"(i), "s"(j));
+                                }
+                                if (__builtin_expect((na & 63u) == 63u, 0)) {   // 64 entries: out they go (a store per step cost more than the step itself)
+                                    asm volatile("" ::: "memory");
+                                    g.aln_node[na - 63 + ln] = pn; g.aln_pos[na - 63 + ln] = pp;
+                                }
+                                na++;
+                                i = ni; j = nj;
+                                if ((int32_t)((i - ilo) | (uint32_t)((int32_t)j - jb0)) < 0) break;   // left the tile's rows or columns
+                            }
                         }
                     }
                     if (!tail) {
-                        if (na & 63u) { const uint32_t base = na & ~63u; if (ln < na - base) { g.aln_node[base + ln] = pn; g.aln_pos[base + ln] = pp; } }
+                        if constexpr (CM > 4) { if (na & 63u) { const uint32_t base = na & ~63u; if (ln < na - base) { g.aln_node[base + ln] = pn; g.aln_pos[base + ln] = pp; } } }
                         nwalk = na; iend = 0; jend = 0;
                     }
                     if (ln == 0) { sNaln = na; lds_u[WALK_N] = nwalk; lds_u[WALK_I] = iend; lds_u[WALK_J] = jend; st_wg(&lds_u[WALK_DONE], 1u); }
