@@ -622,6 +622,45 @@ extern "C" int hx_poa_banded(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off
     return 0;
 }
 
+// one consensus per caller-given label over the one graph of every set: the general path's label instances (all three types) of the gap
+// model the scores name, chosen by hx_poa_graph's rules
+extern "C" int hx_poa_labelled(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const uint8_t* labels,
+                               const hx_poa_convex_params* cp, const hx_poa_label_params* lp, hx_label_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!cp || !lp) return fail("hx_poa_labelled: no parameters");
+    if (check_convex_call("hx_poa_labelled", *cp, set_off[n_sets])) return -1;
+    if (lp->n_labels < 1 || lp->n_labels > 16) return fail("hx_poa_labelled: n_labels must be 1..16, not " + std::to_string(lp->n_labels));
+    if (!labels) return fail("hx_poa_labelled: no labels");
+    for (uint32_t i = 0; i < n_sets; i++)
+        for (uint64_t k = set_off[i]; k < set_off[i + 1]; k++)
+            if (labels[k] >= lp->n_labels && labels[k] != 255)
+                return fail("hx_poa_labelled: set " + std::to_string(i) + ", sequence " + std::to_string(k - set_off[i]) + ": label " + std::to_string(labels[k]) + " is not below n_labels = " + std::to_string(lp->n_labels) + " and not 255 (no label)");
+    if (check_weights("hx_poa_labelled", n_sets, set_off, seq_off, weights)) return -1;
+    hxk::PoaModesArgs a = general_args("hx_poa_labelled", n_sets, set_off, seq_off, bases, convex_or_affine_scores(c, *cp));
+    a.labels = labels; a.n_labels = lp->n_labels; a.weights = weights;
+    a.msa = lp->want_msa != 0; a.include_consensus = a.msa && lp->include_consensus != 0;
+    a.want_coverage = lp->want_coverage != 0; a.want_profile = lp->want_profile != 0;
+    hxk::PoaModesOut o;
+    if (poa_general_run(c, "labelled", a, o)) return -1;
+    out->n_set = n_sets; out->n_labels = lp->n_labels;
+    out->cns_off = dup(o.cns_off.data(), o.cns_off.size());
+    out->cns = dup(o.cns.data(), o.cns.size());
+    out->cns_col = dup(o.cns_col.data(), o.cns_col.size());
+    if (a.msa) {
+        out->n_rows = dup(o.msa_rows.data(), n_sets); out->n_cols = dup(o.msa_cols.data(), n_sets);
+        out->msa_off = dup(o.msa_off.data(), (size_t)n_sets + 1); out->msa = dup(o.msa.data(), o.msa.size());
+    }
+    if (a.want_coverage || a.want_profile) out->coverage = dup(o.cov.data(), o.cov.size());
+    if (a.want_profile) out->profile = dup(o.prof.data(), o.prof.size());
+    out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
+    out->slot_reruns = o.retried;
+    return 0;
+}
+
+extern "C" void hx_free_label(hx_ctx*, hx_label_out* o) {
+    free(o->cns_off); free(o->cns); free(o->cns_col); free(o->coverage); free(o->profile); free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa);
+    memset(o, 0, sizeof(*o));
+}
 extern "C" void hx_free_band(hx_ctx*, hx_band_out* o) {
     free(o->cns_off); free(o->cns); free(o->band_used); free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa); free(o->coverage); free(o->profile);
     memset(o, 0, sizeof(*o));

@@ -49,13 +49,19 @@ struct PoaModesArgs {
                                          // say what PoaModesOut holds beside the flags and the scores
     uint32_t band = 0;                   // hx_poa_banded: the half-width w of the adaptive band, 1..511 (0: no band). A set whose alignment misses the band is run
                                          // again with 2 w, at last on the full matrix; not with graph or strand
+    const uint8_t* labels = nullptr;     // hx_poa_labelled (the label instances; weights as for a weighted call, or null): a label per sequence of the call,
+    uint32_t n_labels = 0;               // 0 .. n_labels - 1 or 255 for none (the caller has checked; n_labels 1..16). PoaModesOut then holds n_labels consensus
+                                         // strings per set, label after label (cns_off: n_sets x n_labels + 1), their columns, and with include_consensus one row
+                                         // per label behind the sequences' rows; msa / include_consensus and want_coverage / want_profile as for a strand call.
+                                         // Not with graph, strand or band
     uint32_t aln_cap = 0;                // graph calls, first round only: a set's share of the alignment pool holds at most this many pairs (0: no cap); sets whose
                                          // alignments outgrow it are rerun once with exactly the room they need
 };
 
 struct PoaModesOut {
-    std::vector<uint64_t> cns_off;       // n_sets + 1
+    std::vector<uint64_t> cns_off;       // n_sets + 1 (labelled calls: n_sets x n_labels + 1)
     std::string cns;
+    std::vector<uint32_t> cns_col;       // labelled calls: the MSA column of every consensus base (cns's layout)
     uint64_t cells = 0, seq_bases = 0, n_aligned = 0;
     double kernel_ms = 0;                // hipEvents around the launches
     uint32_t launches = 0, retried = 0;  // kernel launches, sets rerun in a larger slot

@@ -2,7 +2,7 @@
 // caller-given sequence sets (hx_poa_sequences_mode; DESIGN.md "General POA path" has the semantics and the mapping), and the affine-gap
 // engine in the same modes (hx_poa_sequences_affine: same mapping, a cell is the pair (H, F), its own row of the instance table), and the
 // two-piece affine ("convex") gap model (hx_poa_sequences_convex: a cell is (H, F, O), 12 bytes, a third row of the table). All of it is
-// one kernel template, k_poa_general<NT, CPL, GM, MSA, WTS, GRAPH, STRAND>, GM the gap model.
+// one kernel template, k_poa_general<NT, CPL, GM, MSA, WTS, GRAPH, STRAND, BAND, LABELS>, GM the gap model.
 //
 // It is a kernel family of its own beside the tuned global-only k_poa (kernels/poa.hip), which depends on kNW throughout (de-ramped keys
 // with tie bits, score-bound pruning, sink lists, end-node ties decided on closures, multi-member pipelines). What the modes share with
@@ -44,8 +44,13 @@
 // traceback_band) read and write H through per-row windows of 2 w + 1 columns. An alignment without a reachable end cell stops its set
 // with MS_BAND_MISS; the host runs the set again in twice the band, at last in the full-matrix instances above.
 //
+// Per-label consensus (hx_poa_labelled; DESIGN.md "Per-label consensus") is one more flag, LABELS, over the weighted variant of every
+// shape: the graph is built as ever, and behind the last sort the workgroup runs once per label over the view of that label - the edges
+// its own sequences walk, weighed by them alone (label_views: a per-edge weight array, the rank-ordered rows without the absent edges, the
+// heaviest bundle with a branch completion that stays inside the view) - and writes one consensus and its columns per label.
+//
 // Layout: the DP and traceback of the three gap models are poa_modes_dp.inl, their banded siblings poa_modes_band.inl, the columns, row text, coverage and the graph output's helpers
-// and gather poa_modes_out.inl, the pools of a set poa_modes_pools.inl; this file keeps the work of one set (run_set), the kernel, the
+// and gather and the per-label views poa_modes_out.inl, the pools of a set poa_modes_pools.inl; this file keeps the work of one set (run_set), the kernel, the
 // kernel table and the device half of the host driver (poa_modes_run, in named stages: buffers, uploads, launches, downloads). Every
 // integer decision of those stages - limits, instance, slot sizes, shares of the alignment pool, the retry rule, the work lists and
 // offsets of the outputs - is poa_modes_plan.h / .hip, which makes no HIP call and is tested without a GPU.
@@ -105,6 +110,9 @@ struct MArgs {
     GraphOutArgs go;      // graph instances only (poa_modes_out.inl)
     StrandArgs sa;        // strand instances only
     const uint32_t* band_w;   // band instances only: per set the half-width of its current attempt
+    // label instances only: the label of every sequence of the call (0 .. n_labels - 1, or 255: none). A set has n_labels consensus
+    // places of sum_len bases each from its cns_off on, and cns_len holds n_labels lengths per set
+    const uint8_t* labels; uint32_t n_labels;
 };
 
 // one row of the MSA text: its columns (rising) start at cols[src], its letters at codes[src] (a sequence) or cns[src] (the consensus row)
@@ -157,13 +165,13 @@ __device__ void order_rows(G& g, const uint32_t V, uint32_t* s_scan) {
     __syncthreads();
 }
 
-struct Shared { uint32_t item, V, E, fail; int best; uint32_t na /* graph instances: the pairs the traceback left */; unsigned long long key; };
+struct Shared { uint32_t item, V, E, fail; int best; uint32_t na /* graph instances: the pairs the traceback left; label instances: the smallest node id of a view */; unsigned long long key; };
 
 #include "poa_modes_dp.inl"     // DP and traceback, linear, affine and convex gaps
 #include "poa_modes_band.inl"   // the banded row loop and traceback: one wavefront per window
 #include "poa_modes_out.inl"    // MSA columns and row text, base weights, coverage, graph and alignment output
 
-template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH, bool STRAND, bool BAND>
+template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH, bool STRAND, bool BAND, bool LABELS>
 __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Shared& sh, int* s_wtot, uint32_t* s_scan) {
     const uint32_t t = threadIdx.x;
     const MSet S = a.sets[set];
@@ -249,10 +257,16 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
         uint32_t* colr = g.stack;
         const uint32_t ncols = msa_columns<NT>(g, V, colr, s_scan);
         const uint64_t b0 = a.soff[S.seq_begin];
+        if constexpr (LABELS) {
+            static_assert(WTS && !GRAPH && !STRAND && !BAND, "the label instances are weighted ones, without graph output, strands and band");
+            label_views<NT>(g, a, S, set, V, E, colr, sh, s_scan);   // (reads base_col as node ids)
+        }
         // (a graph instance keeps base_col as node ids: there the column travels with the node)
         if (GRAPH) keep_graph<NT>(g, V, E, colr, a.go, set, b0, b0 + S.seq_begin);
         else for (uint64_t i = t; i < S.sum_len; i += NT) a.base_col[b0 + i] = colr[g.node2rank[a.base_col[b0 + i]]];
-        if (t < 64) {
+        if (LABELS) {   // (label_views has written the consensus places)
+            if (t == 0) { a.n_cols[set] = ncols; a.cells[set] = cells; a.status[set] = MS_OK; }
+        } else if (t < 64) {
             uint32_t len = 0, end_rank = 0;
             if (non_empty) {
                 len = consensus_wave_end(g, V, a.cns + S.cns_off, &end_rank);
@@ -272,7 +286,7 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
     __syncthreads();   // the slot is free for the next set
 }
 
-template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH = false, bool STRAND = false, bool BAND = false>
+template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH = false, bool STRAND = false, bool BAND = false, bool LABELS = false>
 __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
     __shared__ Shared sh;
     __shared__ int s_wtot[(GM == GM_CONVEX ? 2 : 1) * (NT / 64)];   // per wave the total of its row scan (convex: of its two)
@@ -284,7 +298,7 @@ __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
         const uint32_t q = sh.item;
         __syncthreads();
         if (q >= a.n_items) return;
-        run_set<NT, CPL, GM, MSA, WTS, GRAPH, STRAND, BAND>(a, a.order[q], slot, sh, s_wtot, s_scan);
+        run_set<NT, CPL, GM, MSA, WTS, GRAPH, STRAND, BAND, LABELS>(a, a.order[q], slot, sh, s_wtot, s_scan);
     }
 }
 
@@ -307,6 +321,10 @@ const Inst kBand[3] = {HX_BAND(GM_LINEAR), HX_BAND(GM_AFFINE), HX_BAND(GM_CONVEX
 #undef HX_BAND
 static_assert(BAND_SHAPE.nt == BAND_NT && BAND_SHAPE.cpl == BAND_CPL && 2 * MAX_BAND + 1 <= BAND_NT * BAND_CPL, "the plan's band shape against the kernels'");
 static_assert(MAX_LEN[GM_LINEAR] + 1 <= (BAND_SEQ_WORDS - 1) * 16, "the staged sequence of the band instances against the longest sequence");
+// the label instances (hx_poa_labelled; DESIGN.md "Per-label consensus"): the weighted variant of every shape with the per-label views behind its last sort
+#define HX_LABEL(GM, NT, CPL) (const void*)k_poa_general<NT, CPL, GM, true, true, false, false, false, true>
+const void* const kLabel[3][N_INST] = {{HX_POA_INSTANCES_LINEAR(HX_LABEL)}, {HX_POA_INSTANCES_AFFINE(HX_LABEL)}, {HX_POA_INSTANCES_CONVEX(HX_LABEL)}};
+#undef HX_LABEL
 inline const void* fn(const Inst& inst, bool cols, bool weighted, bool graph, bool strand) { return inst.variant[strand ? 4 : graph ? 3 : weighted ? 2 : cols ? 1 : 0]; }
 
 template <class T> struct Buf {   // device buffer of one call
@@ -343,6 +361,7 @@ struct Run {
     uint64_t budget = 0;
     Buf<MSet> d_sets; Buf<uint8_t> d_codes; Buf<uint64_t> d_soff; Buf<uint32_t> d_order, d_counter, d_status, d_vseen, d_cns_len; Buf<unsigned long long> d_cells; Buf<char> d_cns;
     Buf<uint32_t> d_base_col, d_n_cols, d_cns_col;   // MSA and weighted calls only
+    Buf<uint8_t> d_labels;                           // labelled calls only: a label per sequence
     Buf<uint32_t> d_band;                            // banded calls only: per set the half-width of its current attempt
     Buf<uint8_t> d_wts;                              // weighted calls with weights only: a byte per base (graph and strand calls: always, 1 without weights)
     // strand calls only: what StrandArgs points to
@@ -355,7 +374,7 @@ struct Run {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~Run() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
 
-    const void* fn_of(int k) const { return fn(k == BAND_INST ? kBand[c.gm] : kInst[c.gm][k], c.cols, d_wts.p != nullptr, c.graph, c.strand); }
+    const void* fn_of(int k) const { return c.labels ? kLabel[c.gm][k] : fn(k == BAND_INST ? kBand[c.gm] : kInst[c.gm][k], c.cols, d_wts.p != nullptr, c.graph, c.strand); }
     const uint8_t* codes_as_added() const { return c.strand ? d_codes_used.p : d_codes.p; }   // what the row, coverage and profile kernels read
 
     // runs f (0 = ok) between two events, waits for it, and adds the milliseconds it took on the device to *ms
@@ -377,28 +396,29 @@ struct Run {
         o.seq_bases = c.seq_bases; o.n_aligned = c.n_aligned;
         if (bad) return -1;
         const uint32_t ns = c.ns;
-        const uint64_t nseq = c.nseq, nb = c.nb, ncns = c.cns_off[ns];
+        const uint64_t nseq = c.nseq, nb = c.nb, ncns = c.cns_off.back(), nlen = (uint64_t)ns * c.nl;
         int dev = 0;
         MCHK(hipGetDevice(&dev));
         MCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
         MCHK(d_sets.alloc(ns)); MCHK(d_codes.alloc(c.codes.size())); MCHK(d_soff.alloc(nseq + 1)); MCHK(d_order.alloc(ns)); MCHK(d_counter.alloc(N_SLOTS));
-        MCHK(d_status.alloc(ns)); MCHK(d_vseen.alloc(ns)); MCHK(d_cns_len.alloc(ns)); MCHK(d_cells.alloc(ns)); MCHK(d_cns.alloc(ncns));
+        MCHK(d_status.alloc(ns)); MCHK(d_vseen.alloc(ns)); MCHK(d_cns_len.alloc(nlen)); MCHK(d_cells.alloc(ns)); MCHK(d_cns.alloc(ncns));
         MCHK(hipMemcpyAsync(d_sets.p, c.sets.data(), ns * sizeof(MSet), hipMemcpyHostToDevice, s));
         MCHK(hipMemcpyAsync(d_codes.p, c.codes.data(), c.codes.size(), hipMemcpyHostToDevice, s));   // (the codes live to the end of the call)
         MCHK(hipMemcpyAsync(d_soff.p, a.seq_off, (nseq + 1) * 8, hipMemcpyHostToDevice, s));
-        MCHK(d_cns_len.fill(0, ns, s));
+        MCHK(d_cns_len.fill(0, nlen, s));
         MCHK(d_cells.fill(0, ns, s));
         if (c.band) MCHK(d_band.alloc(ns));
         if (c.cols) {
             MCHK(d_base_col.alloc(nb)); MCHK(d_n_cols.alloc(ns));
             MCHK(d_n_cols.fill(0, ns, s));
-            if ((c.msa && a.include_consensus) || c.want_cov) MCHK(d_cns_col.alloc(ncns));
+            if ((c.msa && a.include_consensus) || c.want_cov || c.labels) MCHK(d_cns_col.alloc(ncns));
         }
-        if ((c.wtd || c.graph || c.strand) && a.weights) {
+        if ((c.wtd || c.graph || c.strand || c.labels) && a.weights) {
             MCHK(d_wts.alloc(nb));
             MCHK(hipMemcpyAsync(d_wts.p, a.weights, nb, hipMemcpyHostToDevice, s));
         }
-        if ((c.graph || c.strand) && !a.weights) { MCHK(d_wts.alloc(nb)); MCHK(d_wts.fill(1, nb, s)); }
+        if ((c.graph || c.strand || c.labels) && !a.weights) { MCHK(d_wts.alloc(nb)); MCHK(d_wts.fill(1, nb, s)); }
+        if (c.labels) { MCHK(d_labels.alloc(nseq)); MCHK(hipMemcpyAsync(d_labels.p, a.labels, nseq, hipMemcpyHostToDevice, s)); }
         if (c.strand) {
             MCHK(d_codes_rc.alloc(nb)); MCHK(d_codes_used.alloc(nb)); MCHK(d_wts_used.alloc(nb));
             MCHK(d_reversed.alloc(nseq)); MCHK(d_score_fwd.alloc(nseq)); MCHK(d_score_rev.alloc(nseq)); MCHK(d_third.alloc(ns));
@@ -470,7 +490,7 @@ struct Run {
                     MArgs q{d_sets.p, d_order.p + pk.base, (uint32_t)pk.sets.size(), d_counter.p + k, d_codes.p, d_soff.p, (uint8_t*)ws.p, pk.slot,
                             a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p, a.gap_extend,
                             d_base_col.p, d_n_cols.p, d_cns_col.p, d_wts.p, a.gap_open2, a.gap_extend2, go,
-                            StrandArgs{d_codes_rc.p, d_wts_rc.p ? d_wts_rc.p : d_wts.p, d_codes_used.p, d_wts_used.p, d_reversed.p, d_score_fwd.p, d_score_rev.p, d_third.p}, d_band.p};
+                            StrandArgs{d_codes_rc.p, d_wts_rc.p ? d_wts_rc.p : d_wts.p, d_codes_used.p, d_wts_used.p, d_reversed.p, d_score_fwd.p, d_score_rev.p, d_third.p}, d_band.p, d_labels.p, c.nl};
                     void* kargs[] = {&q};
                     MCHK(hipLaunchKernel(fn_of(k), dim3(pk.nslots), dim3((uint32_t)shape_of(c.gm, k).nt), kargs, 0, s));
                     o.launches++;
@@ -495,19 +515,24 @@ struct Run {
     // ---- the consensus strings and the cell counts, after the last round
     int consensus() {
         const uint32_t ns = c.ns;
-        const uint64_t nseq = c.nseq;
-        len.resize(ns);
+        const uint64_t nseq = c.nseq, nlen = (uint64_t)ns * c.nl, ncns = c.cns_off.back();
+        len.resize(nlen);
         std::vector<unsigned long long> cells(ns);
-        std::vector<char> cns(std::max<uint64_t>(1, c.cns_off[ns]));
-        MCHK(d_cns_len.download(len.data(), ns));
+        std::vector<char> cns(std::max<uint64_t>(1, ncns));
+        MCHK(d_cns_len.download(len.data(), nlen));
         MCHK(d_cells.download(cells.data(), ns));
-        MCHK(d_cns.download(cns.data(), c.cns_off[ns]));
+        MCHK(d_cns.download(cns.data(), ncns));
         if (c.band) o.band_used.resize(ns, 0);   // (a call without a round: no set has a base)
-        o.cns_off.assign((size_t)ns + 1, 0);
-        for (uint32_t i = 0; i < ns; i++) {
-            o.cns.append(cns.data() + c.cns_off[i], len[i]);
-            o.cns_off[i + 1] = o.cns.size();
-            o.cells += cells[i];
+        o.cns_off.assign((size_t)nlen + 1, 0);
+        for (uint64_t j = 0; j < nlen; j++) {
+            o.cns.append(cns.data() + c.cns_off[j], len[j]);
+            o.cns_off[j + 1] = o.cns.size();
+        }
+        for (uint32_t i = 0; i < ns; i++) o.cells += cells[i];
+        if (c.labels) {   // the columns of the consensus bases, dense like the strings
+            std::vector<uint32_t> col(std::max<uint64_t>(1, ncns));
+            MCHK(d_cns_col.download(col.data(), ncns));
+            for (uint64_t j = 0; j < nlen; j++) o.cns_col.insert(o.cns_col.end(), col.begin() + c.cns_off[j], col.begin() + c.cns_off[j] + len[j]);
         }
         if (c.strand) {   // (a set that was rerun rewrote its own part)
             std::vector<uint32_t> third(ns);

@@ -1,6 +1,6 @@
 // poa_modes_out.inl - what the general POA path (kernels/poa_modes.hip) writes beside the consensus text: the columns of the multiple sequence
-// alignment and its row text, the base weights on the graph's edges, the coverage of the consensus bases, and the graph and the alignments
-// themselves. Included inside that file's anonymous namespace, after MRow, GraphOutArgs and block_excl_sum.
+// alignment and its row text, the base weights on the graph's edges, the coverage of the consensus bases, the graph and the alignments
+// themselves, and the per-label views of a set's graph with their consensus. Included inside that file's anonymous namespace, after MRow, GraphOutArgs and block_excl_sum.
 
 // ---- MSA output (DESIGN.md "General POA path", "MSA output") ----
 // The columns of spoa's generate_multiple_sequence_alignment on the final rank order (order_rows leaves aligned nodes contiguous): rank r
@@ -233,4 +233,106 @@ __global__ __launch_bounds__(256) void k_graph_gather(const GRow* rows, const ui
     else if (R.kind == GR_EDGES) { a.o_from[d] = a.edge_from[s]; a.o_to[d] = a.edge_to[s]; a.o_w[d] = a.edge_w[s]; }
     else if (R.kind == GR_CNS) a.o_cns_node[d] = a.cns_node[s];
     else { const uint64_t b = R.src + (R.len - 1u - i); a.o_aln_node[d] = R.pa[b]; a.o_aln_pos[d] = R.pb[b]; }
+}
+
+// ---- per-label consensus (DESIGN.md "General POA path", "Per-label consensus") ----
+// The rank-ordered rows of a label's view: the second half of order_rows with the edges no sequence of the label walks (weight 0 in vw)
+// left out, the weights the view's, and the sink bit set where the node has no out-edge in the view. All lanes.
+template <int NT>
+__device__ void view_rows(G& g, const uint32_t V, const int32_t* vw, uint32_t* s_scan) {
+    const uint32_t t = threadIdx.x;
+    uint32_t carry = 0;
+    for (uint32_t b = 0; b < V; b += NT) {
+        const uint32_t r = b + t;
+        uint32_t np = 0;
+        if (r < V) {
+            const uint32_t n = g.rank2node[r];
+            for (uint32_t e = g.in_head[n]; e != NONE; e = g.e_next_in[e]) np += vw[e] != 0;
+            bool sink = true;
+            for (uint32_t e = g.out_head[n]; e != NONE && sink; e = g.e_next_out[e]) sink = vw[e] == 0;
+            g.row_meta[r] = (uint32_t)g.code[n] | (sink ? 4u : 0u) | (np << META_NP);
+        }
+        uint32_t tot;
+        const uint32_t pre = block_excl_sum<NT>(np, s_scan, &tot);
+        if (r < V) {
+            uint32_t o = carry + pre;
+            g.row_pred_off[r] = o;
+            for (uint32_t e = g.in_head[g.rank2node[r]]; e != NONE; e = g.e_next_in[e])
+                if (vw[e] != 0) { g.pred_rank[o] = g.node2rank[g.e_from[e]]; g.pred_w[o] = vw[e]; o++; }
+        }
+        carry += tot;
+    }
+    if (t == 0) g.row_pred_off[V] = carry;
+    __syncthreads();
+}
+
+// consensus_wave_end on a view: the rows are view_rows', the branch completion kills through the view's edges only, and where spoa falls
+// back to node 0 the view falls back to its own node of smallest id (low_rank: its rank). The first wavefront.
+__device__ uint32_t consensus_wave_view(G& g, const uint32_t V, const int32_t* vw, const uint32_t low_rank, char* out, uint32_t* end_rank) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t best, nbest;
+    bundle_pass(g, V, 0, false, -1, best, nbest);
+    if (best == NONE) best = low_rank;
+    for (uint32_t round = 0; !(g.row_meta[best] & 4u) && round <= V; round++) {
+        const uint32_t n0 = g.rank2node[best];
+        if (lane == 0)
+            for (uint32_t e = g.out_head[n0]; e != NONE; e = g.e_next_out[e]) {
+                if (vw[e] == 0) continue;
+                for (uint32_t oe = g.in_head[g.e_to[e]]; oe != NONE; oe = g.e_next_in[oe])
+                    if (vw[oe] != 0 && g.e_from[oe] != n0) g.score[g.node2rank[g.e_from[oe]]] = -1;
+            }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        uint32_t nb;
+        bundle_pass(g, V, best + 1, true, 0, nb, nbest);
+        best = nb == NONE ? low_rank : nb;
+    }
+    *end_rank = best;
+    return bundle_backtrack(g, best, out);
+}
+
+// All lanes, after the last sort and msa_columns, while base_col still holds the node of every base: one consensus per label over the
+// set's graph. Per label with members: the weight of every edge in its view (vw; cleared, then every base pair of the label's sequences
+// adds w[i-1] + w[i] to the edge between its two nodes - looked up in the out-list of the first, as weigh_path does; two sequences of a
+// label may share an edge, hence the atomic), the view's rows, the heaviest bundle on them and the columns of its bases. vw lies in the
+// node records' pool, which nothing reads after the last add and which holds four words per node (a set has no more edges than bases);
+// e_w itself stays as it is. A label without a non-empty sequence in the set keeps the length 0 its place was cleared to.
+template <int NT>
+__device__ void label_views(G& g, const MArgs& a, const MSet& S, const uint32_t set, const uint32_t V, const uint32_t E, const uint32_t* colr, Shared& sh, uint32_t* s_scan) {
+    const uint32_t t = threadIdx.x;
+    int32_t* vw = (int32_t*)g.nrec;
+    for (uint32_t lb = 0; lb < a.n_labels; lb++) {
+        for (uint32_t e = t; e < E; e += NT) vw[e] = 0;
+        if (t == 0) sh.na = NONE;
+        __syncthreads();
+        uint32_t low = NONE;
+        for (uint32_t k = 0; k < S.nseq; k++) {
+            if (a.labels[S.seq_begin + k] != lb) continue;
+            const uint64_t b = a.soff[S.seq_begin + k];
+            const uint32_t L = (uint32_t)(a.soff[S.seq_begin + k + 1] - b);
+            const uint32_t* path = a.base_col + b;
+            const uint8_t* w = a.wts + b;
+            for (uint32_t i = t; i < L; i += NT) {
+                const uint32_t to = path[i];
+                low = min(low, to);
+                if (i == 0) continue;
+                for (uint32_t e = g.out_head[path[i - 1]]; e != NONE; e = g.e_next_out[e])
+                    if (g.e_to[e] == to) { if (e < E) atomicAdd(&vw[e], (int32_t)w[i - 1] + (int32_t)w[i]); break; }   // (e < E always: the guard keeps the add inside the array)
+            }
+        }
+        if (low != NONE) atomicMin(&sh.na, low);
+        __syncthreads();
+        const uint32_t lowest = sh.na;   // (the same value in every lane)
+        if (lowest < V) {
+            view_rows<NT>(g, V, vw, s_scan);
+            if (t < 64) {
+                const uint64_t at = S.cns_off + (uint64_t)lb * S.sum_len;
+                uint32_t end_rank = 0;
+                const uint32_t len = consensus_wave_view(g, V, vw, g.node2rank[lowest], a.cns + at, &end_rank);
+                consensus_columns(g, end_rank, len, colr, (uint32_t*)g.aln_pos, a.cns_col + at);
+                if (t == 0) a.cns_len[(uint64_t)set * a.n_labels + lb] = len;
+            }
+        }
+        __syncthreads();   // the next label rewrites vw, the rows and the smallest id
+    }
 }

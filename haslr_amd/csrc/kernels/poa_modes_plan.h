@@ -53,9 +53,11 @@ struct ModesCall {
     bool strand = false;                                     // hx_poa_strand: every sequence in both orientations; MSA text, coverage and profile as asked
     bool cols = false, want_cov = false;
     bool band = false;                                       // hx_poa_banded: sets run inside an adaptive band as long as they do not miss it
+    bool labels = false;                                     // hx_poa_labelled: one consensus per label and set over the set's one graph
+    uint32_t nl = 1;                                         // consensus places per set: the call's n_labels, 1 without labels
     uint64_t nseq = 0, nb = 0;
     std::vector<MSet> sets;
-    std::vector<uint64_t> cns_off;                           // ns + 1
+    std::vector<uint64_t> cns_off;                           // ns x nl + 1: place g of set i is entry i x nl + g
     std::vector<uint8_t> codes;                              // the bases as 0..3
     std::vector<uint8_t> codes_rc, wts_rc;                   // strand calls: every sequence reverse-complemented at its own offset, its weights reversed with it
     uint64_t seq_bases = 0, n_aligned = 0;                   // (PoaModesOut's)
@@ -123,7 +125,9 @@ struct CovRow { uint64_t src, dst, hoff; uint32_t len, ncols; };
 enum { ROW_NODES = 0, ROW_EDGES = 1, ROW_CNS = 2, ROW_ALN = 3 };
 struct GraphRow { uint64_t src, dst; uint32_t len, kind; uint32_t round; };   // ROW_ALN: src is a place in the alignment pool of that round
 
-// ncols, len: per set the columns and the length of the consensus; out_cns_off: PoaModesOut::cns_off
+// ncols: per set its columns; len: the length of every consensus (per set, labelled calls: per set and label, as cns_off);
+// out_cns_off: PoaModesOut::cns_off. A labelled call counts per set and label (one counter block each, the blocks of a set side by
+// side; a sequence without a label counts nowhere) and has one consensus row per label, in label order, behind a set's sequences
 struct MsaPlan { RowPlan<MsaRow> rows; std::vector<uint32_t> msa_rows; std::vector<uint64_t> msa_off; uint64_t out_bytes = 0, moved_bytes = 0; };
 int plan_msa(const ModesCall& c, const std::vector<uint32_t>& ncols, const std::vector<uint32_t>& len, const std::vector<uint64_t>& out_cns_off, MsaPlan& p, std::string& err);
 

@@ -33,16 +33,20 @@ int describe(const PoaModesArgs& a, ModesCall& c, ModesState& st, std::string& e
     st = ModesState();
     c.a = &a; c.who = a.who; c.ns = a.n_sets; c.gm = a.gap_model;
     c.msa = a.msa != 0; c.wtd = a.weighted != 0; c.graph = a.graph != 0; c.strand = a.strand != 0;
-    c.cols = c.msa || c.wtd || c.graph || c.strand;
-    c.want_cov = (c.wtd || c.strand) && (a.want_coverage || a.want_profile);
+    c.labels = a.labels != nullptr; c.nl = c.labels ? a.n_labels : 1u;
+    c.cols = c.msa || c.wtd || c.graph || c.strand || c.labels;
+    c.want_cov = (c.wtd || c.strand || c.labels) && (a.want_coverage || a.want_profile);
     c.band = a.band != 0;
+    if (c.labels && (c.nl < 1 || c.nl > 16)) { err = c.who + ": n_labels must be 1..16, not " + std::to_string(c.nl); return -1; }
+    if (c.labels && (c.graph || c.strand || c.band)) { err = c.who + ": graph output, strand-ambiguous sets and banded alignment have no labels"; return -1; }
     if (c.band && a.band > MAX_BAND) { err = c.who + ": the band half-width must be 1.." + std::to_string(MAX_BAND) + ", not " + std::to_string(a.band); return -1; }
     if (c.band && (c.graph || c.strand)) { err = c.who + ": graph output and strand-ambiguous sets have no band"; return -1; }
     const uint32_t ns = c.ns;
     const int gm = c.gm;
     c.nseq = a.set_off[ns]; c.nb = a.seq_off[c.nseq];
     c.sets.resize(ns);
-    c.cns_off.assign((size_t)ns + 1, 0);
+    const uint32_t nl = c.nl;
+    c.cns_off.assign((size_t)ns * nl + 1, 0);
     const uint32_t max_len = MAX_LEN[gm];
     for (uint32_t i = 0; i < ns; i++) {
         MSet& S = c.sets[i];
@@ -54,7 +58,8 @@ int describe(const PoaModesArgs& a, ModesCall& c, ModesState& st, std::string& e
             c.seq_bases += L; c.n_aligned += L != 0;
         }
         if (S.sum_len > MAX_SET_BASES) { err = c.who + ": set " + std::to_string(i) + " holds " + std::to_string(S.sum_len) + " bases in all, more than the " + std::to_string(MAX_SET_BASES) + " nodes a graph can have"; return -1; }
-        S.cns_off = c.cns_off[i]; c.cns_off[i + 1] = c.cns_off[i] + S.sum_len;   // (a consensus has at most one base per node)
+        S.cns_off = c.cns_off[(size_t)i * nl];   // (a consensus has at most one base per node; a labelled set has nl places of that size)
+        for (uint32_t g = 0; g < nl; g++) c.cns_off[(size_t)i * nl + g + 1] = c.cns_off[(size_t)i * nl + g] + S.sum_len;
     }
     if (c.band) {
         // every real value of a banded set's matrices stays above -2^28 and every value derived from minus infinity at or below it
@@ -174,7 +179,7 @@ int after_round(const ModesCall& c, ModesState& st, const bool first, const uint
 // the MSA text: the rows' places (set i = rows x n_cols bytes, row-major) and the work list of k_msa_rows
 int plan_msa(const ModesCall& c, const std::vector<uint32_t>& ncols, const std::vector<uint32_t>& len, const std::vector<uint64_t>& out_cns_off, MsaPlan& p, std::string& err) {
     const PoaModesArgs& a = *c.a;
-    const uint32_t ns = c.ns;
+    const uint32_t ns = c.ns, nl = c.nl;
     p = MsaPlan();
     p.msa_rows.assign(ns, 0);
     p.msa_off.assign((size_t)ns + 1, 0);
@@ -183,14 +188,15 @@ int plan_msa(const ModesCall& c, const std::vector<uint32_t>& ncols, const std::
         uint64_t dst = p.msa_off[i];
         if (nc) {   // (no column: no non-empty sequence, nothing to write)
             for (uint64_t k = a.set_off[i]; k < a.set_off[i + 1]; k++, dst += nc) { const uint32_t L = (uint32_t)(a.seq_off[k + 1] - a.seq_off[k]); p.rows.add(MsaRow{a.seq_off[k], dst, L, nc, 0}, L); }
-            if (a.include_consensus) p.rows.add(MsaRow{c.cns_off[i], dst, len[i], nc, 1}, len[i]);
+            if (a.include_consensus)
+                for (size_t j = (size_t)i * nl; j < (size_t)(i + 1) * nl; j++, dst += nc) p.rows.add(MsaRow{c.cns_off[j], dst, len[j], nc, 1}, len[j]);   // (a label without a consensus: a row of gaps)
         }
-        p.msa_rows[i] = c.sets[i].nseq + (a.include_consensus ? 1u : 0u);
+        p.msa_rows[i] = c.sets[i].nseq + (a.include_consensus ? nl : 0u);
         p.msa_off[i + 1] = p.msa_off[i] + (uint64_t)p.msa_rows[i] * nc;
     }
     if (p.rows.too_many()) { err = c.who + ": too many rows"; return -1; }
     p.out_bytes = p.msa_off[ns];
-    p.moved_bytes = p.out_bytes + 4 * (c.nb + (a.include_consensus ? out_cns_off[ns] : 0));
+    p.moved_bytes = p.out_bytes + 4 * (c.nb + (a.include_consensus ? out_cns_off.back() : 0));
     return 0;
 }
 
@@ -201,18 +207,24 @@ int plan_coverage(const ModesCall& c, const std::vector<uint32_t>& ncols, const 
     p = CovPlan();
     p.stride = a.want_profile ? 4u : 1u;
     uint64_t hoff = 0, hist_bases = 0;
+    const uint32_t nl = c.nl;
     for (uint32_t i = 0; i < c.ns; i++) {
         for (uint64_t k = a.set_off[i]; k < a.set_off[i + 1]; k++) {
             const uint32_t L = (uint32_t)(a.seq_off[k + 1] - a.seq_off[k]);
             if (L < 2) continue;   // (spoa counts the sequence labels of a node's edges: a sequence of one base has none)
-            p.seqs.add(CovRow{a.seq_off[k], 0, hoff, L, ncols[i]}, L);
+            const uint32_t g = c.labels ? a.labels[k] : 0u;
+            if (g >= nl) continue;   // (a labelled call: the sequence has no label)
+            p.seqs.add(CovRow{a.seq_off[k], 0, hoff + (uint64_t)g * ncols[i], L, ncols[i]}, L);
             hist_bases += L;
         }
-        if (len[i]) p.cnss.add(CovRow{c.cns_off[i], out_cns_off[i], hoff, len[i], ncols[i]}, len[i]);
-        hoff += ncols[i];
+        for (uint32_t g = 0; g < nl; g++) {
+            const size_t j = (size_t)i * nl + g;
+            if (len[j]) p.cnss.add(CovRow{c.cns_off[j], out_cns_off[j], hoff + (uint64_t)g * ncols[i], len[j], ncols[i]}, len[j]);
+        }
+        hoff += (uint64_t)nl * ncols[i];
     }
     if (p.seqs.too_many() || p.cnss.too_many()) { err = c.who + ": too many sequences"; return -1; }
-    const uint64_t nc = out_cns_off[c.ns], stride = p.stride;
+    const uint64_t nc = out_cns_off.back(), stride = p.stride;
     p.nc = nc; p.hist_words = hoff * stride;
     // what the two kernels and the clearing of the counters must move: a column (and a letter) read per counted base, the
     // counters written twice and read once where a consensus base stands, a column read and the counts written per consensus base

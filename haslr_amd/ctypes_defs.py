@@ -210,6 +210,16 @@ class BandOut(C.Structure):
                 ("dp_cells", C.c_uint64), ("seq_bases", C.c_uint64), ("n_aligned", C.c_uint64), ("workspace_bytes", C.c_uint64), ("slot_reruns", C.c_uint32), ("band_reruns", C.c_uint32)]
 
 
+class PoaLabelParams(C.Structure):
+    _fields_ = [("n_labels", C.c_uint32), ("want_msa", C.c_int32), ("include_consensus", C.c_int32), ("want_coverage", C.c_int32), ("want_profile", C.c_int32)]
+
+
+class LabelOut(C.Structure):
+    _fields_ = [("n_set", C.c_uint32), ("n_labels", C.c_uint32), ("cns_off", u64p), ("cns", C.POINTER(C.c_char)), ("cns_col", u32p), ("coverage", u32p), ("profile", u32p),
+                ("n_rows", u32p), ("n_cols", u32p), ("msa_off", u64p), ("msa", C.POINTER(C.c_char)),
+                ("dp_cells", C.c_uint64), ("seq_bases", C.c_uint64), ("n_aligned", C.c_uint64), ("slot_reruns", C.c_uint32)]
+
+
 def msa_to_lists(o):
     """(rows per set, consensus per set) of an MsaOut"""
     n = o.n_set

@@ -16,7 +16,7 @@ _lib = None
 SYMBOLS = ["hx_last_error", "hx_device_count", "hx_ctx_create", "hx_ctx_destroy", "hx_upload", "hx_set_read_shard", "hx_set_prefiltered",
            "hx_chain_reads", "hx_edge_support", "hx_edge_coords", "hx_poa_batch", "hx_free_chain", "hx_free_edges",
            "hx_free_coords", "hx_free_cns", "hx_edge_emit", "hx_edge_records_bytes", "hx_edge_records_export",
-           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_poa_graph", "hx_free_graph", "hx_poa_strand", "hx_free_strand", "hx_poa_banded", "hx_free_band", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
+           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_poa_graph", "hx_free_graph", "hx_poa_strand", "hx_free_strand", "hx_poa_banded", "hx_free_band", "hx_poa_labelled", "hx_free_label", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
            "hx_set_option", "hx_get_option", "hx_option_names", "hx_poa_memory_stats", "hx_poa_release_workspace", "hx_poa_prune_stats", "hx_poa_retry_stats", "hx_group_set_timeout", "hx_group_inject_fault", "hx_poa_reserve", "hx_poa_host_times", "hx_poa_arena_stats", "hx_group_rccl_ranks",
            "hx_group_create", "hx_group_destroy", "hx_group_size", "hx_group_ctx", "hx_group_transport", "hx_edge_merge", "hx_group_backend_fill", "hx_group_exchange_stats"]
 
@@ -59,6 +59,8 @@ def lib():
         L.hx_free_strand.argtypes = [C.c_void_p, C.POINTER(T.StrandOut)]
         L.hx_poa_banded.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.PoaBandParams), C.POINTER(T.BandOut)]
         L.hx_free_band.argtypes = [C.c_void_p, C.POINTER(T.BandOut)]
+        L.hx_poa_labelled.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.PoaLabelParams), C.POINTER(T.LabelOut)]
+        L.hx_free_label.argtypes = [C.c_void_p, C.POINTER(T.LabelOut)]
         L.hx_free_chain.argtypes = [C.c_void_p, C.POINTER(T.ChainOut)]
         L.hx_free_edges.argtypes = [C.c_void_p, C.POINTER(T.EdgesOut)]
         L.hx_free_coords.argtypes = [C.c_void_p, C.POINTER(T.CoordsOut)]
@@ -200,6 +202,12 @@ StrandRecord = namedtuple("StrandRecord", "consensus reversed scores rows covera
 # One set of HipContext.poa_banded (include/haslr_types.h, hx_band_out): the consensus; the half-width of the attempt that gave it (0: the
 # full matrix); rows, coverage and profile as StrandRecord has them, each None unless asked for.
 BandRecord = namedtuple("BandRecord", "consensus band_used rows coverage profile")
+# One set of HipContext.poa_labelled (include/haslr_types.h, hx_label_out). consensus, columns, coverage and profile are lists with one
+# entry per label: the label's consensus string, the MSA column of every one of its bases, and (None unless asked for) per base the number
+# of the label's sequences of two or more bases in that column and their [A, C, G, T] counts. rows (None unless asked for): the alignment
+# text, one row per given sequence and, with include_consensus, one more per label.
+LabelRecord = namedtuple("LabelRecord", "consensus columns coverage profile rows")
+NO_LABEL = 255
 
 
 def _out_edges_in_list_order(rec):
@@ -644,6 +652,52 @@ class HipContext:
             st = _counters(o, "workspace_bytes", "slot_reruns", "band_reruns")
         finally:
             lib().hx_free_band(self._h, C.byref(o))
+        return (res, st) if stats else res
+
+    def poa_labelled(self, sets, labels, n_labels, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=None, gap_open2=None, gap_extend2=None, weights=None, qualities=None,
+                     msa=False, include_consensus=False, coverage=False, profile=False, stats=False):
+        """one consensus per label over the one graph of every set (hx_poa_labelled). labels: nested like sets, one integer per sequence,
+        0 .. n_labels - 1 or NO_LABEL (255) for a sequence that builds the graph but belongs to no label; n_labels is 1..16. The graph, the
+        MSA columns and the weights are poa_weighted's for the same sets; the consensus of a label is the heaviest bundle over the edges its
+        own sequences walk, weighed by those sequences alone. A list with one LabelRecord per set: consensus, columns, coverage, profile
+        (each a list with one entry per label; coverage and profile None unless asked for, counting the label's own sequences) and rows
+        (msa=True: the alignment text as poa_msa has it, with include_consensus one consensus row per label behind the sequences'). A
+        label without a non-empty sequence in a set has an empty consensus. gap_extend None (or equal to gap_open) is the linear gap
+        model; gap_open2 and gap_extend2 (both or neither) give the convex one. weights / qualities: as for poa_weighted, with its checks
+        and errors. With stats=True returns (records, counters): dp_cells, seq_bases, n_aligned and slot_reruns."""
+        import numpy as np
+        _check_type(type)
+        ge = gap_open if gap_extend is None else gap_extend
+        cp = _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
+        if cp is None:   # one piece: a second one that is the first again never wins
+            cp = T.PoaConvexParams(match, mismatch, gap_open, ge, gap_open, ge, T.POA_TYPES[type])
+        if len(labels) != len(sets) or any(len(lb) != len(st) for lb, st in zip(labels, sets)):
+            raise ValueError("labels must be nested like sets: one per sequence")
+        flat = [int(v) for lb in labels for v in lb]
+        if any(not 0 <= v <= 255 for v in flat) or not 0 <= int(n_labels) <= 0xffffffff:
+            raise ValueError("a label is 0 .. n_labels - 1 or 255 (no label), n_labels 1..16")
+        wbytes = _weight_bytes(sets, weights, qualities)
+        lp = T.PoaLabelParams(int(n_labels), int(bool(msa)), int(bool(msa and include_consensus)), int(bool(coverage)), int(bool(profile)))
+        o = T.LabelOut()
+        n_sets, set_off, seq_off, bases = _flatten_sets(sets)
+        self._chk(lib().hx_poa_labelled(self._h, n_sets, set_off, seq_off, bases, wbytes, bytes(flat) + b"\0", C.byref(cp), C.byref(lp), C.byref(o)))
+        try:
+            nl = int(o.n_labels)
+            off = T.arr(o.cns_off, n_sets * nl + 1, np.uint64).astype(np.int64)
+            tot = int(off[-1])
+            raw = C.string_at(o.cns, tot).decode() if tot else ""
+            col = T.arr(o.cns_col, tot, np.uint32).tolist()
+            cov = T.arr(o.coverage, tot, np.uint32).tolist() if o.coverage else None
+            prof = T.arr(o.profile, 4 * tot, np.uint32).reshape(-1, 4).tolist() if o.profile else None
+            rows = T.msa_to_lists(o)[0] if msa else None
+            res = []
+            for i in range(n_sets):
+                cut = [(int(off[i * nl + g]), int(off[i * nl + g + 1])) for g in range(nl)]
+                res.append(LabelRecord([raw[a:b] for a, b in cut], [col[a:b] for a, b in cut], [cov[a:b] for a, b in cut] if coverage else None,
+                                       [prof[a:b] for a, b in cut] if profile else None, rows[i] if msa else None))
+            st = _counters(o, "slot_reruns")
+        finally:
+            lib().hx_free_label(self._h, C.byref(o))
         return (res, st) if stats else res
 
     def poa_phase_cycles(self):

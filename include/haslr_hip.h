@@ -191,6 +191,22 @@ void hx_free_strand(hx_ctx*, hx_strand_out*);
  *                     the tests hold the rules to a CPU restatement. */
 int hx_poa_banded(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params*, const hx_poa_band_params*, hx_band_out* out);
 void hx_free_band(hx_ctx*, hx_band_out*);
+/*   hx_poa_labelled   one consensus per caller-given label over the one graph of every set (DESIGN.md "General POA path", "Per-label
+ *                     consensus"; the arrays: haslr_types.h, hx_label_out). labels holds a byte per sequence of the call: 0 .. n_labels - 1,
+ *                     or 255 for a sequence without a label; n_labels is 1..16. Alignment, graph, rank order, columns and weights are
+ *                     hx_poa_weighted's for the same sets: labels enter none of them. The consensus of label g is spoa's heaviest bundle with
+ *                     branch completion on the view of g: the edges its non-empty sequences walk, each weighing the sum of w[i-1] + w[i]
+ *                     over those sequences alone; where spoa falls back to node 0 the view falls back to its own node of smallest id; a
+ *                     label without a non-empty sequence in a set has an empty consensus. All labels of a set share its MSA columns;
+ *                     coverage and profile count a label's own sequences of two or more bases; with include_consensus the MSA text has
+ *                     one consensus row per label, in label order (a row of gaps for an empty consensus). One entry over the convex
+ *                     parameters, by hx_poa_graph's rules for the gap model; weights as for hx_poa_weighted (1..255, 0 refused), or NULL.
+ *                     The errors are hx_poa_graph's with this entry's name in front, and: n_labels outside 1..16; a label >= n_labels
+ *                     other than 255 (names set and sequence). Options poa_modes_slot_kb and poa_workspace_gb act as on the other
+ *                     entries. No band, no strands, no graph output. Not pinned against spoa, which has no such entry: the tests hold the
+ *                     rules to a CPU restatement. */
+int hx_poa_labelled(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const uint8_t* labels, const hx_poa_convex_params*, const hx_poa_label_params*, hx_label_out* out);
+void hx_free_label(hx_ctx*, hx_label_out*);
 void hx_free_chain(hx_ctx*, hx_chain_out*);
 void hx_free_edges(hx_ctx*, hx_edges_out*);
 void hx_free_coords(hx_ctx*, hx_coords_out*);

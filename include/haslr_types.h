@@ -307,6 +307,37 @@ typedef struct {
     uint32_t slot_reruns, band_reruns;
 } hx_band_out;
 
+/* hx_poa_labelled: the number of labels, and what is wanted beside the consensus strings and their columns (hx_poa_strand_want's four
+ * switches). */
+typedef struct {
+    uint32_t n_labels;         /* 1..16: a sequence's label is 0 .. n_labels - 1, or 255 for none */
+    int32_t want_msa;          /* 0 / 1: the alignment text of every set */
+    int32_t include_consensus; /* 0 / 1: with want_msa, one consensus row per label behind the rows of every set */
+    int32_t want_coverage;     /* 0 / 1: the coverage of every consensus base within its label */
+    int32_t want_profile;      /* 0 / 1: and the four letter counts of its column within its label (the coverage is filled in as well) */
+} hx_poa_label_params;
+
+/* hx_poa_labelled: one consensus per label over the one graph of every set (DESIGN.md "General POA path", "Per-label consensus"). The
+ * consensus of label g of set i is entry i * n_labels + g: cns[cns_off[i * n_labels + g] .. cns_off[i * n_labels + g + 1]). cns_col holds
+ * the MSA column of every consensus base; the columns are the set's and shared by its labels. coverage / profile (NULL unless asked for)
+ * count, per consensus base, the label's own sequences of two or more bases with a base in that column. n_rows / n_cols / msa_off / msa
+ * are hx_msa_out's (NULL unless want_msa): with include_consensus a set has n_labels more rows, label after label. dp_cells, seq_bases
+ * and n_aligned are hx_poa_weighted's on the same sets; slot_reruns the sets that ran again in a larger workspace slot. */
+typedef struct {
+    uint32_t n_set, n_labels;
+    uint64_t* cns_off;  /* n_set * n_labels + 1 */
+    char* cns;
+    uint32_t* cns_col;  /* cns_off[n_set * n_labels] */
+    uint32_t* coverage; /* cns_off[n_set * n_labels], or NULL */
+    uint32_t* profile;  /* 4 * cns_off[n_set * n_labels], or NULL */
+    uint32_t* n_rows;   /* n_set, or NULL */
+    uint32_t* n_cols;   /* n_set, or NULL */
+    uint64_t* msa_off;  /* n_set+1, or NULL */
+    char* msa;          /* or NULL */
+    uint64_t dp_cells, seq_bases, n_aligned;
+    uint32_t slot_reruns;
+} hx_label_out;
+
 #ifdef __cplusplus
 }
 #endif

@@ -503,6 +503,66 @@ inline std::vector<Banded> banded_batch(const std::vector<std::vector<std::strin
     return banded_batch(detail::pointers(sets), detail::pointers(weights), band, type, m, n, g, e, q, c, msa, include_consensus);
 }
 
+// labelled sets in ONE device call (hx_poa_labelled): every sequence carries a label 0 .. n_labels - 1 (or 255: none), the graph of a set
+// is built from all of its sequences as weighted_batch builds it, and every label gets the consensus of the edges its own sequences walk,
+// weighed by those sequences alone. Per set and label: the consensus and the MSA column of every one of its bases (the columns are the
+// set's, shared by its labels); with msa the rows (with include_consensus one consensus row per label behind the sequences' rows).
+// weights as for weighted_batch, or empty: every weight is 1. (q, c) == (g, e) is one gap piece, and then e == g the linear model.
+struct Labelled {
+    std::vector<std::string> consensus;                 // one per label
+    std::vector<std::vector<std::uint32_t>> columns;    // one per label: the column of every consensus base
+    std::vector<std::string> rows;                      // empty unless asked for
+};
+inline std::vector<Labelled> labelled_batch(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights,
+                                            const std::vector<std::vector<std::uint8_t>>& labels, std::uint32_t n_labels, AlignmentType type, std::int8_t m = 5, std::int8_t n = -4,
+                                            std::int8_t g = -8, std::int8_t e = -8, std::int8_t q = -8, std::int8_t c = -8, bool msa = false, bool include_consensus = false) {
+    if (!weights.empty() && weights.size() != sets.size()) throw std::invalid_argument("spoa_hx: labelled_batch needs one set of weights per set of sequences, or none");
+    if (labels.size() != sets.size()) throw std::invalid_argument("spoa_hx: labelled_batch needs one set of labels per set of sequences");
+    const detail::Flat f(sets);
+    std::vector<std::uint8_t> w, lb;
+    for (std::size_t i = 0; i < sets.size(); i++) {
+        const auto& st = *sets[i];
+        if (labels[i].size() != st.size()) throw std::invalid_argument("spoa_hx: labelled_batch: a set has another number of labels than of sequences");
+        lb.insert(lb.end(), labels[i].begin(), labels[i].end());
+        if (weights.empty()) continue;
+        if (weights[i]->size() != st.size()) throw std::invalid_argument("spoa_hx: labelled_batch: a set has another number of weight vectors than of sequences");
+        for (std::size_t k = 0; k < st.size(); k++) {
+            const auto& wk = (*weights[i])[k];
+            if (wk.size() != st[k].size()) throw std::invalid_argument("spoa_hx: labelled_batch: a sequence has another number of weights than of bases");
+            w.insert(w.end(), wk.begin(), wk.end());
+        }
+    }
+    if (!weights.empty() && w.empty()) w.push_back(1);   // (no base at all: a pointer that is not null, nothing behind it is read)
+    if (lb.empty()) lb.push_back(255);                   // (no sequence at all: the same)
+    const hx_poa_convex_params cp{m, n, g, e, q, c, static_cast<std::int32_t>(type)};
+    const hx_poa_label_params lp{n_labels, msa ? 1 : 0, msa && include_consensus ? 1 : 0, 0, 0};
+    hx_label_out out;
+    return detail::locked_call([&](hx_ctx* ctx) { return hx_poa_labelled(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), weights.empty() ? nullptr : w.data(), lb.data(), &cp, &lp, &out); },
+                               [&](hx_ctx* ctx) -> std::vector<Labelled> {
+        std::vector<Labelled> res(sets.size());
+        for (std::size_t i = 0; i < sets.size(); i++) {
+            Labelled& d = res[i];
+            for (std::uint32_t l = 0; l < n_labels; l++) {
+                const std::uint64_t a = out.cns_off[i * n_labels + l], b = out.cns_off[i * n_labels + l + 1];
+                d.consensus.emplace_back(out.cns + a, out.cns + b);
+                d.columns.emplace_back(out.cns_col + a, out.cns_col + b);
+            }
+            if (msa)
+                for (std::uint32_t r = 0; r < out.n_rows[i]; r++) {
+                    const char* p = out.msa + out.msa_off[i] + static_cast<std::uint64_t>(r) * out.n_cols[i];
+                    d.rows.emplace_back(p, p + out.n_cols[i]);
+                }
+        }
+        hx_free_label(ctx, &out);
+        return res;
+    });
+}
+inline std::vector<Labelled> labelled_batch(const std::vector<std::vector<std::string>>& sets, const std::vector<std::vector<std::vector<std::uint8_t>>>& weights,
+                                            const std::vector<std::vector<std::uint8_t>>& labels, std::uint32_t n_labels, AlignmentType type, std::int8_t m = 5, std::int8_t n = -4,
+                                            std::int8_t g = -8, std::int8_t e = -8, std::int8_t q = -8, std::int8_t c = -8, bool msa = false, bool include_consensus = false) {
+    return labelled_batch(detail::pointers(sets), detail::pointers(weights), labels, n_labels, type, m, n, g, e, q, c, msa, include_consensus);
+}
+
 // Graphviz text of a graph, after spoa's Graph::print_dot: per node `id [label = "id - LETTER"]`, filled for the nodes of the consensus;
 // per out-edge, in out-list order, `from -> to [label = "weight"]`; one dotted line without arrowhead per pair of aligned nodes (nodes that
 // share a column), from the smaller to the larger id

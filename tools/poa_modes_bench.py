@@ -33,6 +33,9 @@ sets in the same process: kernel time by the same protocol, the workspace the ca
 after, the workspace released in between; the banded call also reports the plan's own figure), the share of sets that did not finish at
 W (band_used != W: they climbed to a wider band or to the full matrix), the reruns that cost, and the share of sets whose banded consensus
 is the full-matrix one. A package without the banded entry (--package-root of a parent checkout) gives the full-matrix figures alone.
+--labels is another mode of its own: a two-haplotype workload (per set a template and a copy of it with SNPs and one indel, noisy reads of
+each) under kNW, affine scores, through hx_poa_labelled at n_labels = 1, 2 and 16 beside hx_poa_weighted on the same sets in the same
+build: kernel time of each and the ratio over the weighted call, which is what the label passes cost on top of the DP.
 --rows picks the rows, --only picks the parts to run; --package-root runs the parts another
 build of the package has (a checkout of the parent commit, say) in the same way, for a comparison on one machine. Prints one JSON line,
 and writes it to --out when given."""
@@ -172,6 +175,64 @@ def band_mode(a, hip):
             f.write(json.dumps(res) + "\n")
 
 
+def workload_haplotypes(rng, n_sets):
+    """per set: a template of 200..4000 bases, a second haplotype of it (one SNP per 200 bases, at least three, and one indel of 1..8
+    bases), and 4..20 noisy reads of each, the haplotypes interleaved. Returns (sets, per set the haplotype of every read)"""
+    sets, haps = [], []
+    for _ in range(n_sets):
+        t = rng.integers(0, 4, int(rng.integers(200, 4001)))
+        h = t.copy()
+        for p in rng.choice(len(t), max(3, len(t) // 200), replace=False):
+            h[p] = (h[p] + int(rng.integers(1, 4))) % 4
+        p, k = int(rng.integers(10, len(t) - 10)), int(rng.integers(1, 9))
+        h = np.concatenate([h[:p], h[p + k:]]) if rng.random() < 0.5 else np.concatenate([h[:p], rng.integers(0, 4, k), h[p:]])
+        n = int(rng.integers(4, 21))
+        sets.append([text(noisy(rng, (t, h)[i % 2])) for i in range(2 * n)])
+        haps.append([i % 2 for i in range(2 * n)])
+    return sets, haps
+
+
+def labels_mode(a, hip):
+    rng = np.random.default_rng(a.seed)
+    sets, haps = workload_haplotypes(rng, a.sets_a)
+    m, n, g, e = a.affine_scores
+    kw = dict(type="nw", match=m, mismatch=n, gap_open=g, gap_extend=e)
+    ctx = hip.HipContext(0)
+    res = {"tool": "poa_modes_bench", "mode": "labels", "seed": a.seed, "repeats": a.repeats, "sets": len(sets), "scores": [m, n, g, e],
+           "longest_sequence": max(len(q) for st in sets for q in st), "bases": sum(len(q) for st in sets for q in st)}
+
+    def timed(fn):
+        ms, wall = gpu_time(ctx, fn, a.repeats)
+        out = {"kernel_ms_median": round(float(np.median(ms)), 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2)}
+        out.update(wall_stats(wall))
+        return out
+    with ctx.options(poa_weighted=1):   # (the weighted kernels, as the label instances are: weights of 1)
+        wcns, st = ctx.poa_weighted(sets, stats=True, **kw)
+        res["weighted"] = timed(lambda: ctx.poa_weighted(sets, **kw))
+    res["weighted"]["cells"] = int(st["dp_cells"])
+    note("labels", "weighted", res["weighted"]["kernel_ms_median"], "ms")
+    if hasattr(hip.HipContext, "poa_labelled"):
+        for nl in (1, 2, 16):
+            labels = [[0 if nl == 1 else hp if nl == 2 else hp * 8 + (i // 2) % 8 for i, hp in enumerate(hs)] for hs in haps]
+            recs, st = ctx.poa_labelled(sets, labels, nl, stats=True, **kw)
+            r = timed(lambda: ctx.poa_labelled(sets, labels, nl, **kw))
+            w = res["weighted"]
+            r.update({"cells": int(st["dp_cells"]), "slot_reruns": int(st["slot_reruns"]), "over_weighted": round(r["kernel_ms_median"] / w["kernel_ms_median"], 4),
+                      "over_weighted_min": round(r["kernel_ms_min"] / w["kernel_ms_max"], 4), "over_weighted_max": round(r["kernel_ms_max"] / w["kernel_ms_min"], 4),
+                      "consensus_bases": int(sum(len(c) for rec in recs for c in rec.consensus))})
+            if nl == 1:
+                r["share_consensus_equal_weighted"] = round(sum(rec.consensus[0] == c for rec, c in zip(recs, wcns)) / len(sets), 4)
+            if nl == 2:
+                r["share_sets_with_two_consensuses"] = round(sum(rec.consensus[0] != rec.consensus[1] for rec in recs) / len(sets), 4)
+            res["labels_%d" % nl] = r
+            note("labels", nl, r["kernel_ms_median"], "ms")
+    ctx.close()
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sets-a", type=int, default=256)
@@ -185,12 +246,15 @@ def main():
     ap.add_argument("--rows", nargs="+", default=["a_sw", "a_nw", "a_ov", "b_ov"], choices=["a_sw", "a_nw", "a_ov", "b_ov"], help="the rows to run")
     ap.add_argument("--package-root", default=ROOT, help="the tree whose built haslr_amd package runs (default: this one); parts it does not have are left out")
     ap.add_argument("--band", type=int, nargs="+", metavar="W", help="the band mode: workload (a) under kNW and kOV through hx_poa_banded at these half-widths, against the full-matrix general path")
+    ap.add_argument("--labels", action="store_true", help="the label mode: the two-haplotype workload through hx_poa_labelled at n_labels = 1, 2 and 16, against hx_poa_weighted on the same sets")
     ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.package_root))
     from haslr_amd import hip
     if a.band:
         return band_mode(a, hip)
+    if a.labels:
+        return labels_mode(a, hip)
     import cvxlib
     import msalib
     import parlib
