@@ -175,7 +175,7 @@ int main(int argc, char* argv[]) {
             if (poa_block) hx_set_poa_block(ctx, poa_block);
         }
         // The library reads no environment: this APPLICATION hands the HX_* variables that name library options (hx_option_names) to its contexts, once
-        const std::string names = std::string(",") + hx_option_names() + ",prof1,prof2,prof3,";
+        const std::string names = std::string(",") + hx_option_names() + ",prof1,prof2,prof3,prof4,";
         for (char** ev = environ; ev && *ev; ev++) {
             if (strncmp(*ev, "HX_", 3) != 0) continue;
             const char* eq = strchr(*ev, '=');

@@ -141,7 +141,7 @@ extern "C" int hx_set_option(hx_ctx* c, const char* name, const char* value) {
     const std::string k = opt_key(name);
     const HxOptions dflt;
     const bool reset = !value || !*value;
-    if (k == "prof1" || k == "prof2" || k == "prof3") { c->opt.prof = reset ? 0 : k[4] - '0'; return 0; }   // (HX_PROF1 / 2 / 3 of the development builds)
+    if (k == "prof1" || k == "prof2" || k == "prof3" || k == "prof4") { c->opt.prof = reset ? 0 : k[4] - '0'; return 0; }   // (HX_PROF1 / 2 / 3 / 4 of the development builds)
     for (const OptDesc& d : kOptions)
         if (k == d.name) {
             char* end = nullptr;

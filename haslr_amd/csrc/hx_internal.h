@@ -130,7 +130,7 @@ struct PoaArena {
 // variables of their environment in, once, when they create a context) and by the tests. Defaults in the table below; -1 = automatic.
 struct HxOptions {
     int debug = 0;                 // progress and statistics of every consensus call on stderr
-    int prof = 0;                  // 1 / 2 / 3: how hx_poa_phase_cycles reads words 6-11 of a build with -DHX_DP_PROF / PROF2 / PROF3 (development: POA_PHASE_FLAVOUR, kernels/poa_phase_words.h)
+    int prof = 0;                  // 1 / 2 / 3 / 4: how hx_poa_phase_cycles reads words 6-11 of a build with -DHX_DP_PROF / PROF2 / PROF3 / PROF4 (development: POA_PHASE_FLAVOUR, kernels/poa_phase_words.h)
     double poa_workspace_gb = 0;   // cap of the POA workspace in GB (0: 90 % of the memory that was free at the context's first consensus call)
     int poa_poll_limit = 1 << 24;  // polls before a wave gives up waiting for another member (testing: forces the unshared retry)
     int poa_max_indeg = 16;        // in-degree the direction bytes hold (testing: forces the score-matrix retry earlier)

@@ -48,6 +48,15 @@ void report_members(const PoaReportView& v) {   // (a build with -DHX_DP_PROF3: 
         fprintf(v.out, "\n");
     }
 }
+void report_batchhead(const PoaReportView& v) {   // (a build with -DHX_DP_PROF4: what a carry batch costs the waves with a left neighbour in their workgroup besides its rows, for the five longest edges)
+    for (const auto& t : longest(v)) {
+        const W* q = v.edge(t.second);
+        const W n = pw_hi(q[PW_BH_CLOCK], PW_SPLIT_HALF), ready = q[PW_BH_READY], polled = q[PW_BH_POLLED];
+        fprintf(v.out, "[hx] prof4 edge %u lmax=%u nseq=%u dp %llu: waves x DPs %llu, batches %llu of %.2f rows (%.1f per wave and DP); carries there %llu batches, %.0f cycles each; polled %llu batches, %.0f cycles each; two clock reads %.0f cycles\n",
+                t.second, v.lmax[t.second], v.nseq[t.second], q[PW_DP], n, ready + polled, ready + polled ? (double)q[PW_BH_ROWS] / (double)(ready + polled) : 0.0, n ? (double)(ready + polled) / (double)n : 0.0,
+                ready, ready ? (double)q[PW_BH_READY_CYCLES] / (double)ready : 0.0, polled, polled ? (double)q[PW_BH_POLLED_CYCLES] / (double)polled : 0.0, n ? (double)pw_lo(q[PW_BH_CLOCK], PW_SPLIT_HALF) / (double)n : 0.0);
+    }
+}
 void report_edges(const PoaReportView& v) {   // every edge: shape of its launch, begin and end on the 100 MHz wall clock (relative to the call's first edge), phase cycles, DP rows
     W t0 = ~0ull;
     for (size_t e = 0; e < v.n_edges; e++) if (v.edge(e)[PW_BEGIN]) t0 = std::min(t0, pw_lo(v.edge(e)[PW_BEGIN], PW_SPLIT_CLOCK));
@@ -119,6 +128,7 @@ PoaReport poa_phase_report(const PoaReportView& v, uint64_t* sum6, uint64_t* max
     if (v.prof == 1) report_rowseg(v);
     else if (v.prof == 2) report_dpsub(v);
     else if (v.prof == 3) report_members(v);
+    else if (v.prof == 4) report_batchhead(v);
     else { if (v.debug >= 2) report_edges(v); report_rowstats(v, res.slowest); }
     return res;
 }

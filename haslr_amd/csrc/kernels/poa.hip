@@ -296,6 +296,11 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
 #if POA_PHASE_FLAVOUR == POA_PHASE_MEMBERS
             if (tid == 0 && phase) atomicAdd(&phase[(uint64_t)eidx * POA_PHASE_WORDS + PW_P3_MEMBER0 + min(mem, (uint32_t)(PW_N_BUILD - 1))], pw_pack(0, ph[PW_P3_WAIT] >> 10, PW_SPLIT_HALF) | pw_pack((unsigned long long)(clock64() - td0) >> 10, 0, PW_SPLIT_HALF));   // (the wait half first: it is read before the clock)
 #endif
+#if POA_PHASE_FLAVOUR == POA_PHASE_BATCHHEAD   // (every member adds what its waves collected in this DP to the edge's words in place)
+            __syncthreads();
+            if (tid == 0 && phase) for (int k = 0; k < PW_N_BUILD; k++) { atomicAdd(&phase[(uint64_t)eidx * POA_PHASE_WORDS + PW_BUILD0 + k], ph[PW_BUILD0 + k]); ph[PW_BUILD0 + k] = 0; }
+            __syncthreads();
+#endif
             if (ns != 0xffffffffu) sNsink = ns;   // written by the lane that owns column L
             cl.tag0 += V;
         }
@@ -787,6 +792,8 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
         ph[PW_END] = pw_lo(wall_clock64(), PW_SPLIT_CLOCK);
 #if POA_PHASE_FLAVOUR == POA_PHASE_MEMBERS
         if (phase) for (int k = 0; k < PW_N_PHASES; k++) phase[(uint64_t)eidx * POA_PHASE_WORDS + k] = ph[k];   // (the members have added to the others in place)
+#elif POA_PHASE_FLAVOUR == POA_PHASE_BATCHHEAD
+        if (phase) for (int k = 0; k < POA_PHASE_WORDS; k++) if (k < PW_BUILD0 || k >= PW_BUILD0 + PW_N_BUILD) phase[(uint64_t)eidx * POA_PHASE_WORDS + k] = ph[k];   // (the same)
 #else
         if (phase) for (int k = 0; k < POA_PHASE_WORDS; k++) phase[(uint64_t)eidx * POA_PHASE_WORDS + k] = ph[k];
 #endif

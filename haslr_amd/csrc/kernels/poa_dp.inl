@@ -100,7 +100,8 @@ template <int CM> __device__ __forceinline__ void store_chunk_u8(uint8_t* p, con
 // own carries from the wave on its left, 32 rows at a time (one coalesced read, lane r = row r of the batch, broadcast per row with
 // v_readlane like the row records). A wave therefore runs one batch behind its left neighbour, polls once per 32 rows and never meets
 // a barrier inside the DP. Tags (a row counter that runs through all DPs of the edge) make every entry self-validating; the consumer
-// reports how far it has read so that the producer never laps it.
+// reports how far it has read so that the producer never laps it (in the unpruned instances every 16 rows and whenever it has to wait, and the
+// producer reads the report again only when the value it holds does not cover its batch: docs/poa_kernel_notes.md, "What a carry batch costs").
 // Nothing else is shared: the LDS ring of kept rows and the rows kept in HBM are private to the wave (each with a copy of the value
 // left of its first column), so a wave that is ahead can never pull a row from under one that is behind.
 //
@@ -130,9 +131,17 @@ constexpr int KD = 63, KV = 47;           // low 6 bits of a key of a wide row =
 constexpr int KHC = 4;                    // ... and the horizontal move's code in EVERY row format (4-bit rows: type 1 * 4 + 3 - 3; wide rows: below every other code, the
                                           // traceback takes type 0 and 1 alike): a finished key (score x 64 + KHC) is the horizontal candidate of the next column as it is
 
-constexpr uint32_t CARRY_BATCH = 32;       // rows whose carries a wave takes at a time at most
-constexpr uint32_t CARRY_MIN = 4;          // ... and at least (int32 rows; = how far a wave that keeps up runs behind its left neighbour)
+#ifndef HX_CARRY_BATCH                     // (development: -DHX_CARRY_BATCH=16 -DHX_CARRY_MIN=2 for an A/B of the batch limits)
+#define HX_CARRY_BATCH 32
+#endif
+#ifndef HX_CARRY_MIN
+#define HX_CARRY_MIN 4
+#endif
+constexpr uint32_t CARRY_BATCH = HX_CARRY_BATCH;   // rows whose carries a wave takes at a time at most
+constexpr uint32_t CARRY_MIN = HX_CARRY_MIN;       // ... and at least (int32 rows; = how far a wave that keeps up runs behind its left neighbour)
 constexpr uint32_t WAVE_MBOX = 64;         // entries of the LDS mailbox between two waves of a workgroup (a power of two >= 2 * CARRY_BATCH)
+constexpr uint32_t CARRY_PUBLISH = 16;     // rows a wave takes before it tells its left neighbour again how far it has read - while it finds carries; a wave that has to wait tells at once
+static_assert(CARRY_PUBLISH + CARRY_BATCH <= WAVE_MBOX, "a neighbour that is a batch ahead still finds room behind a count that is CARRY_PUBLISH rows old");
 constexpr uint32_t MAX_WAVES = 16;         // waves per workgroup at most
 constexpr uint32_t WG_POLL_LIMIT = 1u << 24;   // polls of a wave for another wave of its own workgroup (resident by construction) before it flags an internal error
 
@@ -308,6 +317,19 @@ template <int CM> __device__ __forceinline__ void store_nibbles_buf(__amdgpu_buf
 #else
 #define DP_T(k) do { } while (0)
 #endif
+// POA_PHASE_BATCHHEAD - of a wave with a left neighbour in its workgroup, the cycles of everything a carry batch costs besides its rows (PW_BH_*): BH_T0 .. BH_T1 around
+// the head, again around what follows the rows, BH_POLLED where a wait did not end at its first look, BH_BATCH at the batch's end
+#if POA_PHASE_FLAVOUR == POA_PHASE_BATCHHEAD
+#define BH_T0() do { if (bh_on) bh_t0 = clock64(); } while (0)
+#define BH_T1() do { if (bh_on) { const unsigned long long _d = (unsigned long long)(clock64() - bh_t0); if (bh_polled) bh_c1 += _d; else bh_c0 += _d; } } while (0)
+#define BH_POLLED() do { bh_polled = 1u; } while (0)
+#define BH_BATCH(n) do { if (bh_on) { if (bh_polled) bh_n1++; else bh_n0++; bh_rows += (n); bh_polled = 0u; } } while (0)
+#else
+#define BH_T0() do { } while (0)
+#define BH_T1() do { } while (0)
+#define BH_POLLED() do { } while (0)
+#define BH_BATCH(n) do { } while (0)
+#endif
 // The row loop is written for a lone wavefront's latency: on this hardware a VALU instruction costs ~5 cycles whether or not it depends
 // on its predecessor, a taken scalar branch ~35, an LDS round trip ~75, the DPP scan ~90. So a row is ONE dispatch on where its
 // predecessor lives (registers / LDS ring / anything else), then straight-line code: rare events (row spilled to HBM, sink row) share
@@ -376,6 +398,13 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
     const bool in_lds = !ONEW && (wv > 0 || relay_mode);                                 // ... through the workgroup's LDS mailbox, or (first wave of a member without a relay wave) through HBM
     const bool has_out = (uint64_t)(gw + 1) * 64u * CM < ncol;                // a wave on the right owns real columns (the host sized the pipeline for the longest sequence)
     const bool out_lds = !ONEW && wv + 1 < NW;
+#if POA_PHASE_FLAVOUR == POA_PHASE_BATCHHEAD
+    const bool bh_on = !ONEW && has_in && wv > 0;
+    unsigned long long bh_c0 = 0, bh_c1 = 0;
+    uint32_t bh_n0 = 0, bh_n1 = 0, bh_rows = 0, bh_polled = 0;
+    long long bh_t0 = 0;
+    const long long bh_k0 = clock64(), bh_k1 = clock64();
+#endif
     // (wave-uniform tests of the row loop as 32-bit scalars: a test of a lane-mask boolean is `s_andn2 vcc` + a vcc branch, ~32 cycles for a lone
     // wave against ~15 for `s_cmp` + an scc branch: tools/dev_lonebench.hip)
     const uint32_t out_l = (uint32_t)__builtin_amdgcn_readfirstlane((int)(has_out && out_lds)), out_h = (uint32_t)__builtin_amdgcn_readfirstlane((int)(has_out && !out_lds));
@@ -541,6 +570,12 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
     // (a one-wave workgroup has no LDS mailbox on either side - its carries come from and go to HBM, window by window - and takes the 64 rows of a record batch
     // at once: half as many round trips for the carries, which is what a dead batch costs now that its rows leave in runs)
     const uint32_t cbatch = (uint32_t)__builtin_amdgcn_readfirstlane((int)(NW == 1u ? 64u : CARRY_BATCH));
+    // the hand-over's two counts as this wave last saw / said them, in scalar registers: the tag up to which the wave on the right has taken this wave's carries
+    // (cons_out, read again only when it does not cover a batch) and the row up to which this wave has told the wave on its left (cons_in). Both begin every
+    // DP at "everything of earlier DPs", which is what the store at the DP's start leaves in cons_in.
+    constexpr bool LEAN = !ONEW && !PRUNE;   // (the pruned instances keep the hand-over they had: their waves may wait for whole batches, and their registers are the many-edge regime's occupancy)
+    const uint32_t in_l = (uint32_t)__builtin_amdgcn_readfirstlane((int)(LEAN && has_in && in_lds));
+    uint32_t taken_r = tag0_s, told_l = 0;
     for (uint32_t ib = 0; ib < V; ib += 64) {
         // the batches move up (the only waits for these loads: everything was requested at least 64 rows ago), another one goes in flight
         mC = mN; aC = aN; bC = bN; oC = oN; cC = cN; dC = dN; fC = fN;
@@ -551,7 +586,11 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
         uint32_t nb = 0;
         for (uint32_t rb = 0; rb < ie; rb += nb) {
             // rows i0 .. i0 + nb - 1: up to CARRY_BATCH rows of the record batch - as many as have their carries in the mailbox, at least CARRY_MIN (a
-            // wave follows its left neighbour at that distance when it keeps up, and the mailbox's 64 entries still absorb a neighbour's hiccup)
+            // wave follows its left neighbour at that distance when it keeps up, and the mailbox's 64 entries still absorb a neighbour's hiccup).
+            // What stands between here and the first row is paid once per batch by every wave but the edge's first, and a wave that keeps up takes small
+            // batches. LEAN (the unpruned instances with an LDS mailbox - the ones the longest chains run in): on the usual path ONE mailbox read and one
+            // test; the polls, the look at the right neighbour's count and the word about this wave's own all sit behind branches that are not taken.
+            BH_T0();
             const uint32_t want = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(cbatch, ie - rb)), i0 = ib + rb + 1;
             nb = want;
             int cinV = NEGK;     // lane r: carry into this wave for row i0 + r
@@ -559,33 +598,75 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
 #if POA_PHASE_FLAVOUR == POA_PHASE_MEMBERS
                 const long long tw0 = clock64();
 #endif
-                for (uint32_t spin = 0;; spin++) {
-                    unsigned long long v = 0;
-                    bool ok = true;
-                    if (lane < want) {
-                        v = in_lds ? ld_wg64(mb_in_l + ((i0 + lane) & (WAVE_MBOX - 1))) : ld_dev64(mb_in_h + i0 + lane);
-                        ok = (uint32_t)v == cl.tag0 + i0 + lane;
+                if (LEAN && in_lds) {
+                    const uint32_t least = min(want, CARRY_MIN);
+                    // every lane reads its entry of the ring, whatever `want` is: a lane beyond the rows that have arrived finds an older tag
+                    unsigned long long v = ld_wg64(mb_in_l + ((i0 + lane) & (WAVE_MBOX - 1)));
+                    unsigned long long late = ~__ballot((uint32_t)v == tag0_s + i0 + lane);
+                    uint32_t run = min(want, late ? (uint32_t)__builtin_ctzll(late) : 64u);   // leading rows whose carries have arrived
+                    if (__builtin_expect(run < least, 0)) {
+                        // a wave that waits has told its neighbour everything it has taken: the neighbour checks the room for a whole batch of its own before it writes the
+                        // first row of it, and must never wait for a count that is only held back
+                        if (told_l != i0 - 1) { told_l = i0 - 1; if (lane == 0) st_wg(cons_in, tag0_s + told_l); }
+                        for (uint32_t spin = 0;; spin++) {
+                            if (spin > WG_POLL_LIMIT) { if (lane == 0) st_dev(cl.err, 2u); run = want; v = (unsigned long long)(uint32_t)NEGK << 32; break; }
+                            BH_POLLED();
+                            __builtin_amdgcn_s_sleep(2);
+                            v = ld_wg64(mb_in_l + ((i0 + lane) & (WAVE_MBOX - 1)));
+                            late = ~__ballot((uint32_t)v == tag0_s + i0 + lane);
+                            run = min(want, late ? (uint32_t)__builtin_ctzll(late) : 64u);
+                            if (run >= least) break;
+                        }
                     }
-                    const unsigned long long okm = __ballot(ok);
-                    const uint32_t run = okm == ~0ull ? want : (uint32_t)__builtin_ctzll(~okm);   // leading rows whose carries have arrived
-                    // (PRUNE: a wave whose last batch was skipped whole is AHEAD of the band - it is not what its edge waits for, but a poll every ~130 cycles
-                    // takes issue slots from the waves that are: it waits for whole batches and sleeps 16 times as long between polls)
-                    if (run >= min(want, PRUNE && lazy ? want : CARRY_MIN)) { nb = run; cinV = (int)(uint32_t)(v >> 32); break; }
-                    if (spin > (in_lds ? WG_POLL_LIMIT : cl.poll_limit)) { if (lane == 0) st_dev(cl.err, in_lds ? 2u : 1u); break; }
-                    if (PRUNE && lazy) __builtin_amdgcn_s_sleep(32);
-                    else if (in_lds) __builtin_amdgcn_s_sleep(2); else __builtin_amdgcn_s_sleep(8);
+                    nb = run; cinV = (int)(uint32_t)(v >> 32);
+                } else {   // carries through HBM (the first wave of a member without a relay wave, a one-wave workgroup), and the pruned instances
+                    for (uint32_t spin = 0;; spin++) {
+                        unsigned long long v = 0;
+                        bool ok = true;
+                        if (lane < want) {
+                            v = in_lds ? ld_wg64(mb_in_l + ((i0 + lane) & (WAVE_MBOX - 1))) : ld_dev64(mb_in_h + i0 + lane);
+                            ok = (uint32_t)v == cl.tag0 + i0 + lane;
+                        }
+                        const unsigned long long okm = __ballot(ok);
+                        const uint32_t run = okm == ~0ull ? want : (uint32_t)__builtin_ctzll(~okm);   // leading rows whose carries have arrived
+                        // (PRUNE: a wave whose last batch was skipped whole is AHEAD of the band - it is not what its edge waits for, but a poll every ~130 cycles
+                        // takes issue slots from the waves that are: it waits for whole batches and sleeps 16 times as long between polls)
+                        if (run >= min(want, PRUNE && lazy ? want : CARRY_MIN)) { nb = run; cinV = (int)(uint32_t)(v >> 32); break; }
+                        if (spin > (in_lds ? WG_POLL_LIMIT : cl.poll_limit)) { if (lane == 0) st_dev(cl.err, in_lds ? 2u : 1u); break; }
+                        BH_POLLED();
+                        if (PRUNE && lazy) __builtin_amdgcn_s_sleep(32);
+                        else if (in_lds) __builtin_amdgcn_s_sleep(2); else __builtin_amdgcn_s_sleep(8);
+                    }
+                    if (in_lds && lane == 0) st_wg(cons_in, cl.tag0 + i0 + nb - 1);   // the entries of these rows may be written again
                 }
-                if (in_lds && lane == 0) st_wg(cons_in, cl.tag0 + i0 + nb - 1);   // the entries of these rows may be written again
 #if POA_PHASE_FLAVOUR == POA_PHASE_MEMBERS
                 if (tid == 0) prof[PW_P3_WAIT - PW_BUILD0] += (unsigned long long)(clock64() - tw0);
 #endif
             }
-            if (has_out && out_lds) {   // the rows of this batch overwrite the entries of the rows WAVE_MBOX earlier: the wave on the right must have taken those
+            // the rows of this batch overwrite the entries of the rows WAVE_MBOX earlier: the wave on the right must have taken those
+            if constexpr (LEAN) {
+                if (out_l != 0u) {
+                    // (its count is read again only when the value last read does not cover the batch - a count never falls, so an old one errs on the safe
+                    // side; with the neighbour a few rows behind and 64 entries one read serves several batches. Tags below tag0 - earlier DPs' - are
+                    // covered from the start.)
+                    const uint32_t need = tag0_s + i0 + nb - 1 - WAVE_MBOX;
+                    if (__builtin_expect((int32_t)(taken_r - need) < 0, 0)) {
+                        for (uint32_t spin = 0;; spin++) {
+                            taken_r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ld_wg(cons_out));
+                            if ((int32_t)(taken_r - need) >= 0) break;
+                            if (spin > WG_POLL_LIMIT) { if (lane == 0) st_dev(cl.err, 2u); break; }
+                            BH_POLLED();
+                            __builtin_amdgcn_s_sleep(2);
+                        }
+                    }
+                }
+            } else if (has_out && out_lds) {
                 const uint32_t need = i0 + nb - 1 > WAVE_MBOX ? cl.tag0 + i0 + nb - 1 - WAVE_MBOX : 0;
                 for (uint32_t spin = 0; need; spin++) {
                     const uint32_t got = (uint32_t)__builtin_amdgcn_readfirstlane((int)ld_wg(cons_out));
                     if ((int32_t)(got - need) >= 0) break;
                     if (spin > WG_POLL_LIMIT) { if (lane == 0) st_dev(cl.err, 2u); break; }
+                    BH_POLLED();
                     __builtin_amdgcn_s_sleep(2);
                 }
             }
@@ -869,13 +950,27 @@ __device__ __forceinline__ void dp_rows(const G& g, int32_t* __restrict__ H, uin
             // are 42 % rows with several predecessors, 30 % rows whose one predecessor sits in the ring (bubbles interleave in rank order), and only 28 % fast rows, in
             // runs of 1.3: what a run costs to set up (mask shift, count, the first predecessor's entry read again: ~100 cycles) and what every other row pays for the
             // test is more than the ~25 instructions a fast row saves. The code is in git history.
+            BH_T1();
             while (rj < nb) {
                 row();
                 rj++;
             }
+            // the entries of these rows may be written again: said once CARRY_PUBLISH rows have been taken since it was last said, behind the batch's rows
+            BH_T0();
+            if (LEAN && in_l != 0u && i0 + nb - 1 - told_l >= CARRY_PUBLISH) { told_l = i0 + nb - 1; if (lane == 0) st_wg(cons_in, tag0_s + told_l); }
+            BH_T1();
+            BH_BATCH(nb);
             if constexpr (PRUNE) lazy = (uint32_t)(n_dead - dead_before == nb) & lazy_on;
         }
     }
+#if POA_PHASE_FLAVOUR == POA_PHASE_BATCHHEAD
+    if (bh_on && lane == 0) {
+        atomicAdd(&prof[PW_BH_READY_CYCLES - PW_BUILD0], bh_c0); atomicAdd(&prof[PW_BH_READY - PW_BUILD0], (unsigned long long)bh_n0);
+        atomicAdd(&prof[PW_BH_POLLED_CYCLES - PW_BUILD0], bh_c1); atomicAdd(&prof[PW_BH_POLLED - PW_BUILD0], (unsigned long long)bh_n1);
+        atomicAdd(&prof[PW_BH_ROWS - PW_BUILD0], (unsigned long long)bh_rows);
+        atomicAdd(&prof[PW_BH_CLOCK - PW_BUILD0], pw_pack((unsigned long long)(bh_k1 - bh_k0) & 0xffffffull, 1ull, PW_SPLIT_HALF));
+    }
+#endif
     if (owns_last) nSinkOut = nsink;
     if constexpr (PRUNE) { if (lane == 0 && pstat) { atomicAdd(&pstat[PW_PRUNE_ROWS - PW_PRUNE0], (unsigned long long)V); atomicAdd(&pstat[PW_PRUNE_SKIPPED - PW_PRUNE0], (unsigned long long)n_dead); atomicAdd(&pstat[PW_PRUNE_BULK - PW_PRUNE0], (unsigned long long)n_bulk); } }
 }

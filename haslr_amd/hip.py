@@ -119,7 +119,7 @@ def env_options(environ=None):
     """the HX_* variables of the environment that name library options ({option: text}): what an APPLICATION hands to hx_set_option when it
     creates a context - the library itself reads no environment (include/haslr_hip.h)"""
     environ = os.environ if environ is None else environ
-    names = set(option_names()) | {"prof1", "prof2", "prof3"}
+    names = set(option_names()) | {"prof1", "prof2", "prof3", "prof4"}
     return {k[3:].lower(): v for k, v in environ.items() if k.startswith("HX_") and k[3:].lower() in names}
 
 
