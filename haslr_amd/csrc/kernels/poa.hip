@@ -769,7 +769,7 @@ __device__ __forceinline__ void poa_edge(const uint32_t eidx, const uint32_t mem
             csr_rebuild<MAXNT, DIR>(g, sV, R, 0xffffffffu, 0xffffffffu, 0xffffffffu, lds_u, &sOk, ph, false, eidx, false, false);
             __threadfence_block();
             __syncthreads();
-            if (tid < 64) { const uint32_t cl_ = consensus_wave(g, sV, cns + ED.cns_off); if (tid == 0) sCtl = cl_; }
+            if (tid < 64) { const uint32_t cl_ = consensus_wave<true>(g, sV, cns + ED.cns_off); if (tid == 0) sCtl = cl_; }
             __syncthreads();
         }
     }

@@ -290,6 +290,92 @@ __device__ void bundle_pass(G& g, const uint32_t V, const uint32_t r_begin, cons
     }
 }
 
+// The unrestricted pass over all ranks [0, V): the same score / pred of every rank and the same best / nbest as bundle_pass(g, V, 0, false, floor_score, ...),
+// without the walk through the chunk rank by rank (~70 issued instructions and one or two LDS round trips per rank, by a lone wave: ~1 000 cycles a node).
+// The fold takes the in-edge that maximises (weight, score of its source, position): a rank whose heaviest in-edge is the only one of that weight chooses
+// without a score, and its score is that weight plus the score of a known rank. So, per chunk of 64 ranks (lane = rank, all lanes throughout):
+//  - every lane takes its row's maximal weight and how many in-edges carry it. One, from before the chunk: the score is final (one load). One, from inside:
+//    the lane hangs off that lane (`link`) with its weight as offset (`val`). Several - a TIED rank, 3-5 % of the ranks of a read graph, most of them two
+//    weight-2 edges meeting -: the lane waits, as the root of whatever hangs off it;
+//  - pointer jumping along the links, at most log2(64) = 6 rounds of two ds_bpermute: a lane whose link is not a tied lane adds that lane's offset and takes
+//    over its link. Afterwards every lane has its score or hangs off a tied lane directly;
+//  - the tied lanes in rising order (a wave-uniform loop over the ballot's bits): the scores of its maximal in-edges' sources - from memory before the chunk,
+//    from the lanes inside it, which are earlier ones and final by then - choose by (score, position), spoa's <= : the later in-edge wins a full tie; the lanes
+//    that hang off it take its score into theirs;
+//  - the chunk's maximum by a wave reduction: strictly above the running one, its first rank is the new best and the lanes that hold it are counted; equal to
+//    it, they are added - what the rank-by-rank rule comes to.
+// No cross-lane read stands in a divergent block; every loop is bounded by 64, 6 or a row's in-degree.
+__device__ void bundle_pass_free(G& g, const uint32_t V, const int32_t floor_score, uint32_t& best, uint32_t& nbest) {
+    const uint32_t lane = threadIdx.x & 63u;
+    int32_t* sc_r = g.score;          // by rank
+    int32_t* pr_r = g.pred;           // by rank: rank of the chosen predecessor, -1 = none
+    best = NONE; nbest = 0;
+    int32_t bscore = floor_score;
+    for (uint32_t r0 = 0; r0 < V; r0 += 64) {
+        const uint32_t r = r0 + lane;
+        const bool valid = r < V;
+        const uint32_t np = valid ? g.row_meta[r] >> META_NP : 0u, off = valid ? g.row_pred_off[r] : 0u;
+        uint32_t ep[4]; int32_t ew[4];                          // the first four in-edges in registers (rank, weight)
+#pragma unroll
+        for (int k = 0; k < 4; k++) { ep[k] = (uint32_t)k < np ? g.pred_rank[off + k] & 0x0fffffffu : NONE; ew[k] = (uint32_t)k < np ? g.pred_w[off + k] : 0; }
+        int32_t wmax = -1; uint32_t cnt = 0, pm = NONE;         // the maximal weight, the in-edges that carry it, the source of the last of them
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (ep[k] != NONE) { if (ew[k] > wmax) { wmax = ew[k]; cnt = 1; pm = ep[k]; } else if (ew[k] == wmax) { cnt++; pm = ep[k]; } }
+        for (uint32_t k = 4; k < np; k++) {                     // more than four (rare): the rest of the list, a lane on its own
+            const uint32_t p = g.pred_rank[off + k] & 0x0fffffffu; const int32_t w = g.pred_w[off + k];
+            if (w > wmax) { wmax = w; cnt = 1; pm = p; } else if (w == wmax) { cnt++; pm = p; }
+        }
+        const bool tied = cnt > 1;
+        const unsigned long long tmask = __ballot(tied);
+        // scores from before the chunk: of the one maximal in-edge's source, or (tied) of those of the first four that carry the maximal weight
+        int32_t sb[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) sb[k] = tied && ep[k] < r0 && ew[k] == wmax ? sc_r[ep[k]] : 0;   // (NONE is not below r0)
+        int32_t val = -1, link = -1, bp = -1;                   // score, or the offset to the score of lane `link`; the chosen predecessor
+        if (cnt == 1) { bp = (int32_t)pm; if (pm < r0) val = wmax + sc_r[pm]; else { val = wmax; link = (int32_t)(pm - r0); } }
+        else if (tied) val = 0;
+        for (int it = 0; it < 6; it++) {                        // pointer jumping
+            const int src = link >= 0 ? link : (int)lane;
+            const bool act = link >= 0 && !((tmask >> src) & 1ull);
+            if (!__ballot(act)) break;
+            const int32_t v2 = __shfl(val, src), l2 = __shfl(link, src);
+            if (act) { val += v2; link = l2; }
+        }
+        for (unsigned long long m = tmask; m; m &= m - 1) {     // the tied lanes, in rising order (wave-uniform)
+            const int l = __builtin_ctzll(m);
+            int32_t bs = NEG, cp = -1;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const bool in = ep[k] != NONE && ep[k] >= r0;
+                const int32_t si = __shfl(val, in ? (int)(ep[k] - r0) : (int)lane);   // (every lane takes part in the exchange)
+                const int32_t s = in ? si : sb[k];
+                if (ep[k] != NONE && ew[k] == wmax && s >= bs) { bs = s; cp = (int32_t)ep[k]; }
+            }
+            const uint32_t npl = (uint32_t)__builtin_amdgcn_readlane((int)np, l);
+            for (uint32_t k = 4; k < npl; k++) {                // its in-edges beyond the fourth (rare)
+                uint32_t p = NONE; int32_t w = 0;
+                if ((int)lane == l) { p = g.pred_rank[off + k] & 0x0fffffffu; w = g.pred_w[off + k]; }
+                const bool in = p != NONE && p >= r0;
+                const int32_t si = __shfl(val, in ? (int)(p - r0) : (int)lane);
+                if (p != NONE && w == wmax) { const int32_t s = in ? si : sc_r[p]; if (s >= bs) { bs = s; cp = (int32_t)p; } }
+            }
+            const int32_t t = wmax + bs;
+            const int32_t tl = __builtin_amdgcn_readlane(t, l);
+            if ((int)lane == l) { val = t; bp = cp; }
+            else if (link == l) { val += tl; link = -1; }      // what hangs off it
+        }
+        const int32_t sc = valid ? val : NEG;
+        const int32_t cmax = __builtin_amdgcn_readlane(wave_scan_max(sc), 63);
+        const unsigned long long eq = __ballot(sc == cmax);
+        if (cmax > bscore) { best = r0 + (uint32_t)__builtin_ctzll(eq); bscore = cmax; nbest = (uint32_t)__popcll(eq); }
+        else if (cmax == bscore) nbest += (uint32_t)__popcll(eq);
+        if (valid) { sc_r[r] = val; pr_r[r] = bp; }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+}
+
 // The walk back from rank `best` along the chosen predecessors, by the whole wavefront: every lane gets the length. A lane on its own pays a dependent
 // round trip per node, twice (length first, then the bases back to front): 4-5 M cycles of the 14 M the consensus of the longest 12 Mb edge took. Here the
 // predecessors and bases of the 64 ranks around the walk are fetched at once, the walk inside them runs on v_readlane, the bases are kept back to front
@@ -322,18 +408,20 @@ __device__ uint32_t bundle_backtrack(G& g, const uint32_t best, char* out) {
 
 __device__ uint32_t consensus_fast_wave(G& g, const uint32_t V, char* out) {
     uint32_t best, nbest;
-    bundle_pass(g, V, 0, false, -2, best, nbest);               // (every score is >= -1: the first rank opens the maximum)
+    bundle_pass_free(g, V, -2, best, nbest);                    // (every score is >= -1: the first rank opens the maximum)
     if (best == NONE || nbest != 1 || !(g.row_meta[best] & 4u)) return NONE;    // (bit 2 of a row record: the node has no out-edge)
     return bundle_backtrack(g, best, out);
 }
 
 // spoa Graph::traverse_heaviest_bundle + branch_completion on the REFERENCE's topological order (rank2node / node2rank hold it, the rank-ordered
 // rows have been rebuilt for it: k_poa's bundle_rows), by one wavefront. The reference starts with best = node 0 and moves it to every node that
-// scores strictly more, in rank order; its branch completion does the same from (0, node 0).
-__device__ uint32_t consensus_wave(G& g, const uint32_t V, char* out) {
+// scores strictly more, in rank order; its branch completion does the same from (0, node 0). FREE: the first pass by bundle_pass_free (k_poa; the general
+// path's call stays on bundle_pass, like its own copies of this function in poa_modes_out.inl: its instances come out as they were).
+template <bool FREE = false> __device__ uint32_t consensus_wave(G& g, const uint32_t V, char* out) {
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t best, nbest;
-    bundle_pass(g, V, 0, false, -1, best, nbest);
+    if constexpr (FREE) bundle_pass_free(g, V, -1, best, nbest);
+    else bundle_pass(g, V, 0, false, -1, best, nbest);
     if (best == NONE) best = g.node2rank[0];
     for (uint32_t round = 0; !(g.row_meta[best] & 4u) && round <= V; round++) {   // branch completion (the bound only guards against a cycle the reference would hang in)
         const uint32_t n0 = g.rank2node[best];
