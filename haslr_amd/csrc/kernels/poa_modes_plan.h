@@ -37,6 +37,9 @@ constexpr uint64_t CELL_BYTES[3] = {4, 8, 12};   // of a cell of H by gap model:
 constexpr int BAND_INST = N_INST, N_SLOTS = N_INST + 1;
 constexpr InstShape BAND_SHAPE = {64, 16};
 constexpr int64_t BAND_SCORE_BOUND = 1 << 28;   // (bases of a set + its longest sequence) x the largest score magnitude stays below it
+// Every set of the path: (its bases + the NT x CPL columns of its full-matrix instance) x the largest score magnitude stays below it, which keeps every
+// cell, every scan term and every sum with minus infinity of dp_rows inside int32 and on its side of -2^29 (DESIGN.md "Score range of the full matrix")
+constexpr int64_t SCORE_BOUND = 1 << 29;
 inline InstShape shape_of(int gm, int k) { return k == BAND_INST ? BAND_SHAPE : INST_SHAPE[gm][k]; }
 static_assert(MAX_LEN[GM_LINEAR] + 1 == INST_SHAPE[GM_LINEAR][N_INST - 1].nt * INST_SHAPE[GM_LINEAR][N_INST - 1].cpl && MAX_LEN[GM_AFFINE] + 1 == INST_SHAPE[GM_AFFINE][N_INST - 1].nt * INST_SHAPE[GM_AFFINE][N_INST - 1].cpl &&
               MAX_LEN[GM_CONVEX] + 1 == INST_SHAPE[GM_CONVEX][N_INST - 1].nt * INST_SHAPE[GM_CONVEX][N_INST - 1].cpl, "MAX_LEN against the widest instance of every gap model");

@@ -61,16 +61,26 @@ int describe(const PoaModesArgs& a, ModesCall& c, ModesState& st, std::string& e
         S.cns_off = c.cns_off[(size_t)i * nl];   // (a consensus has at most one base per node; a labelled set has nl places of that size)
         for (uint32_t g = 0; g < nl; g++) c.cns_off[(size_t)i * nl + g + 1] = c.cns_off[(size_t)i * nl + g] + S.sum_len;
     }
+    int64_t mag = 0;   // the largest score magnitude
+    for (const int32_t v : {a.match, a.mismatch, a.gap, a.gap_extend, a.gap_open2, a.gap_extend2}) mag = std::max<int64_t>(mag, v < 0 ? -(int64_t)v : v);
     if (c.band) {
         // every real value of a banded set's matrices stays above -2^28 and every value derived from minus infinity at or below it
-        int64_t mag = 0;
-        for (const int32_t v : {a.match, a.mismatch, a.gap, a.gap_extend, a.gap_open2, a.gap_extend2}) mag = std::max<int64_t>(mag, v < 0 ? -(int64_t)v : v);
         st.band.assign(ns, 0);
         for (uint32_t i = 0; i < ns; i++) {
             const MSet& S = c.sets[i];
             if ((int64_t)(S.sum_len + S.lmax) * mag >= BAND_SCORE_BOUND) { err = c.who + ": set " + std::to_string(i) + " holds " + std::to_string(S.sum_len) + " bases, its longest sequence " + std::to_string(S.lmax) + ": with scores of up to " + std::to_string(mag) + " their product " + std::to_string((int64_t)(S.sum_len + S.lmax) * mag) + " reaches 2^28 = " + std::to_string(BAND_SCORE_BOUND) + " (a banded set's scores must stay below it)"; return -1; }
             st.band[i] = (uint64_t)S.lmax + 1 <= 2 * (uint64_t)a.band + 1 ? 0u : a.band;   // (a window that holds the longest sequence is the full matrix)
         }
+    }
+    // The full matrix (a banded set may end there): a real value is a sum of at most nodes + columns scores, dp_rows computes every column of the set's
+    // instance, those past the sequence on minus infinity, and its scans shift column j by j gap scores. Below the bound none of that leaves int32,
+    // and a real value stays above -2^29, a value derived from it at or below (DESIGN.md "Score range of the full matrix")
+    for (uint32_t i = 0; i < ns; i++) {
+        const MSet& S = c.sets[i];
+        if (!S.sum_len) continue;
+        const InstShape sh = INST_SHAPE[gm][inst_of(c, i)];
+        const int64_t cols = (int64_t)sh.nt * sh.cpl, prod = ((int64_t)S.sum_len + cols) * mag;
+        if (prod >= SCORE_BOUND) { err = c.who + ": set " + std::to_string(i) + " holds " + std::to_string(S.sum_len) + " bases, its instance " + std::to_string(cols) + " columns: with scores of up to " + std::to_string(mag) + " their product " + std::to_string(prod) + " reaches 2^29 = " + std::to_string(SCORE_BOUND) + " (a set's scores must stay below it)"; return -1; }
     }
     c.codes.resize(std::max<uint64_t>(1, c.nb));
     for (uint64_t k = 0; k < c.nb; k++) c.codes[k] = base_code(a.bases[k]);

@@ -141,9 +141,13 @@ int hx_poa_weighted(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uin
  *                     H, F and O (12 bytes), sequences of up to 8191 bases; a longer one is an error that names its set. Errors, each naming the
  *                     score and its value: those of hx_poa_sequences_affine for the first piece, the same three for the second piece
  *                     (gap_open2 >= 0, gap_extend2 > 0, gap_extend2 < gap_open2), gap_open2 > gap_open, an unknown type. Refused, not
- *                     reinterpreted. Scores are int32 in this ABI and the matrices are int32 too, with -2^29 as "minus infinity": (nodes of a
- *                     set + columns) x the largest score magnitude must stay below 2^29, which every int8 score does for every set the path
- *                     accepts (2^21 nodes, 8 192 columns); larger scores are not checked and can wrap. Not pinned against spoa, like the rest of the general path: the tests hold it to a CPU restatement. */
+ *                     reinterpreted. Scores are int32 in this ABI and the matrices are int32 too, with -2^29 as "minus infinity": for every
+ *                     set (its bases + the columns of the kernel instance it runs in, the first of 1 024, 4 096, 8 192, 32 768 (linear), 1 024,
+ *                     4 096, 8 192, 16 384 (affine), 1 024, 2 048, 4 096, 8 192 (convex) that holds its longest sequence + 1) x the largest
+ *                     score magnitude must stay below 2^29, which every int8 score does for every set the path accepts (2^21 nodes, 32 768
+ *                     columns). A set that reaches it is refused by every entry of the general path, hx_poa_sequences_mode to
+ *                     hx_poa_labelled, with an error that names the set, its bases, the columns, the magnitude and the product (DESIGN.md
+ *                     "Score range of the full matrix" has the derivation; hx_poa_banded has a tighter bound of its own beside it). Not pinned against spoa, like the rest of the general path: the tests hold it to a CPU restatement. */
 int hx_poa_sequences_convex(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_convex_params*, hx_cns_out* out);
 int hx_poa_msa_convex(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const hx_poa_convex_params*, int include_consensus, hx_msa_out* out);
 int hx_poa_weighted_convex(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params*, int want_coverage, int want_profile, hx_wcns_out* out);

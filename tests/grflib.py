@@ -34,7 +34,7 @@ def gap_score(scores, k):
 
 
 def _ints(line, dtype):
-    return np.array([int(v) for v in line.split()], dtype=dtype)
+    return np.fromstring(line, dtype=np.int64, sep=" ").astype(dtype)
 
 
 class GraphRef:
@@ -68,7 +68,8 @@ class GraphRef:
         for k in range(len(seqs)):
             path, aln, tail = ln[9 + 3 * k:12 + 3 * k]
             score, vb, eb = (int(v) for v in tail.split())
-            sq.append(GraphSequence(_ints(path, np.uint32), [tuple(int(v) for v in p.split(":")) for p in aln.split()], score))
+            flat = np.fromstring(aln.replace(":", " "), dtype=np.int64, sep=" ").tolist()   # (node:pos pairs; parsed in one go: the corpus tests read millions)
+            sq.append(GraphSequence(_ints(path, np.uint32), list(zip(flat[0::2], flat[1::2])), score))
             before.append((vb, eb))
         rec = GraphRecord(ln[0], _ints(ln[1], np.uint32), _ints(ln[2], np.uint32), _ints(ln[3], np.uint32), _ints(ln[4], np.uint32), _ints(ln[5], np.int32), n_cols, sq,
                           ln[6], _ints(ln[7], np.uint32))

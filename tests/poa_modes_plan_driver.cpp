@@ -25,6 +25,10 @@ int main(int argc, char** argv) {
     std::string err;
     PoaModesOut o;
     if (describe(a, c, st, err)) { T.error(err); return 0; }
+    if (!strncmp(argv[1], "bound_", 6)) {   // the score bound: describe's verdict is the case (no golden text: the check is younger than the harness that printed it)
+        for (uint32_t i = 0; i < c.ns; i++) printf("accepted set %u sum_len %llu lmax %u columns %d\n", i, (unsigned long long)c.sets[i].sum_len, c.sets[i].lmax, INST_SHAPE[c.gm][inst_of(c, i)].nt * INST_SHAPE[c.gm][inst_of(c, i)].cpl);
+        return 0;
+    }
     o.seq_bases = c.seq_bases; o.n_aligned = c.n_aligned;
     const uint32_t ns = c.ns;
     const InstShape* shape = INST_SHAPE[c.gm];

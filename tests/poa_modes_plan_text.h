@@ -147,6 +147,22 @@ inline bool make_case(const std::string& name, Case& cs) {
         a.strand = 1; wts = stem == "strand_w";
         a.msa = 1; a.include_consensus = 1; a.want_coverage = wts;
         cs.add_set({12, 9, 0, 5}); cs.add_set({7});
+    } else if (stem == "bound_under" || stem == "bound_at") {
+        // the score bound of the full matrix (kernels/poa_modes_plan.h, SCORE_BOUND): set 1 has 1 024 bases and runs in the instance of 1 024 columns,
+        // so a magnitude of 2^18 makes the product exactly 2^29 and one less stays under it; the magnitude stands in a positive and in a negative score
+        cs.add_set({30, 40}); cs.add_set({600, 424});
+        if (stem == "bound_under") a.match = (1 << 18) - 1; else a.mismatch = -(1 << 18);
+    } else if (stem == "bound_wide") {
+        // the columns are the instance's, not the sequence's: 1 024 bases + 1 take the second instance (4 096, 4 096, 2 048 columns by gap model)
+        cs.add_set({1024, 1024});
+        a.gap = a.gap_open2 = gm == 2 ? -(1 << 17) : -87382;
+    } else if (stem == "bound_int8") {
+        // the largest set the path takes with the longest sequence of its gap model, every score at an end of int8
+        a.match = 127; a.mismatch = a.gap = a.gap_extend = a.gap_open2 = a.gap_extend2 = -128;
+        const uint32_t most = (1u << 21) - 2;
+        std::vector<uint32_t> lens(most / max_len[gm], max_len[gm]);
+        lens.push_back(most % max_len[gm]);
+        cs.add_set(lens);
     } else return false;
     cs.view(wts);
     return true;

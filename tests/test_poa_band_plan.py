@@ -117,4 +117,4 @@ def test_the_plans_refusals(driver):
                                                                                   "reaches 2^28 = 268435456 (a banded set's scores must stay below it)")
     assert plan(driver, 0, 8, 0, 0, [[10], [30000, 30000]], score=2982)["error"] is None   # (90 000 x 2 982 = 268 380 000, just below)
     assert plan(driver, 2, 8, 0, 0, [[8192]])["error"].startswith("hx_poa_banded: set 0 holds a sequence of 8192 bases, longer than 8191")
-    assert plan(driver, 0, 0, 0, 0, [[10], [30000, 30000]], score=3000)["error"] is None   # (without a band there is no bound)
+    assert plan(driver, 0, 0, 0, 0, [[10], [30000, 30000]], score=3000)["error"] is None   # (without a band only the full matrix's bound holds: (60 000 + 32 768 columns) x 3 000 stays below 2^29)

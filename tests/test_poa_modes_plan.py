@@ -190,6 +190,36 @@ def test_cases_reach_every_branch():
     assert all(" variant 4 " in ln for c in ("strand", "strand_w") for ln in text[c].splitlines() if ln.startswith("launch variant"))
 
 
+SCORE_BOUND = 1 << 29   # kernels/poa_modes_plan.h; DESIGN.md section 11, "Score range of the full matrix"
+MAX_SET_BASES = (1 << 21) - 2
+MAX_LEN = {"lin": 32767, "aff": 16383, "cvx": 8191}
+
+
+def refusal(set_, bases, columns, mag):
+    """the text of describe()'s refusal of a set whose (bases + columns of its instance) x the largest score magnitude reaches 2^29"""
+    return (f"error hx_test: set {set_} holds {bases} bases, its instance {columns} columns: with scores of up to {mag} their product {(bases + columns) * mag} "
+            f"reaches 2^29 = {SCORE_BOUND} (a set's scores must stay below it)\n")
+
+
+@pytest.mark.parametrize("gm", ["lin", "aff", "cvx"])
+def test_scores_just_under_the_bound_are_accepted_and_at_the_bound_refused(driver, gm):
+    # set 1: 1 024 bases in the instance of 1 024 columns; 2 048 x (2^18 - 1) = 2^29 - 2 048, 2 048 x 2^18 = 2^29
+    assert COLUMNS[gm][0] == 1024 and (1024 + 1024) * (1 << 18) == SCORE_BOUND
+    assert plan(driver, "bound_under_" + gm) == "accepted set 0 sum_len 70 lmax 40 columns 1024\naccepted set 1 sum_len 1024 lmax 600 columns 1024\n"
+    assert plan(driver, "bound_at_" + gm) == refusal(1, 1024, 1024, 1 << 18)
+    # the columns are those of the instance the set runs in, which computes every one of them: a longest sequence of 1 024 bases takes the second
+    cols = COLUMNS[gm][1]
+    mag = {4096: 87382, 2048: 1 << 17}[cols]
+    assert (2048 + cols) * (mag - 1) < SCORE_BOUND <= (2048 + cols) * mag
+    assert plan(driver, "bound_wide_" + gm) == refusal(0, 2048, cols, mag)
+
+
+@pytest.mark.parametrize("gm", ["lin", "aff", "cvx"])
+def test_every_int8_score_is_accepted_on_the_largest_set_with_the_longest_sequence(driver, gm):
+    assert plan(driver, "bound_int8_" + gm) == f"accepted set 0 sum_len {MAX_SET_BASES} lmax {MAX_LEN[gm]} columns {MAX_LEN[gm] + 1}\n"
+    assert (MAX_SET_BASES + MAX_LEN[gm] + 1) * 128 < SCORE_BOUND
+
+
 @pytest.mark.parametrize("case", CASES)
 def test_plan_invariants(driver, case):
     text = plan(driver, case)
