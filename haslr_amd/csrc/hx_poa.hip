@@ -661,6 +661,47 @@ extern "C" void hx_free_label(hx_ctx*, hx_label_out* o) {
     free(o->cns_off); free(o->cns); free(o->cns_col); free(o->coverage); free(o->profile); free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa);
     memset(o, 0, sizeof(*o));
 }
+
+// two consensus strings per set from reads the call phases itself: the general path's phase instances (the label instances with the phasing
+// of the set's reads in front of the per-label views), chosen by hx_poa_graph's rules
+extern "C" int hx_poa_phased(hx_ctx* c, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights,
+                             const hx_poa_convex_params* cp, const hx_poa_phase_params* pp, hx_phase_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!cp || !pp) return fail("hx_poa_phased: no parameters");
+    if (check_convex_call("hx_poa_phased", *cp, set_off[n_sets])) return -1;
+    if (pp->min_count < 1 || pp->min_count > 255) return fail("hx_poa_phased: min_count must be 1..255, not " + std::to_string(pp->min_count));
+    if (pp->min_pct < 1 || pp->min_pct > 50) return fail("hx_poa_phased: min_pct must be 1..50, not " + std::to_string(pp->min_pct));
+    if (check_weights("hx_poa_phased", n_sets, set_off, seq_off, weights)) return -1;
+    hxk::PoaModesArgs a = general_args("hx_poa_phased", n_sets, set_off, seq_off, bases, convex_or_affine_scores(c, *cp));
+    a.phase = 1; a.phase_min_count = pp->min_count; a.phase_min_pct = pp->min_pct; a.weights = weights;
+    a.msa = pp->want_msa != 0; a.include_consensus = a.msa && pp->include_consensus != 0;
+    a.want_coverage = pp->want_coverage != 0; a.want_profile = pp->want_profile != 0;
+    hxk::PoaModesOut o;
+    if (poa_general_run(c, "phased", a, o)) return -1;
+    out->n_set = n_sets; out->n_labels = 2;
+    out->cns_off = dup(o.cns_off.data(), o.cns_off.size());
+    out->cns = dup(o.cns.data(), o.cns.size());
+    out->cns_col = dup(o.cns_col.data(), o.cns_col.size());
+    if (a.msa) {
+        out->n_rows = dup(o.msa_rows.data(), n_sets); out->n_cols = dup(o.msa_cols.data(), n_sets);
+        out->msa_off = dup(o.msa_off.data(), (size_t)n_sets + 1); out->msa = dup(o.msa.data(), o.msa.size());
+    }
+    if (a.want_coverage || a.want_profile) out->coverage = dup(o.cov.data(), o.cov.size());
+    if (a.want_profile) out->profile = dup(o.prof.data(), o.prof.size());
+    out->dp_cells = o.cells; out->seq_bases = o.seq_bases; out->n_aligned = o.n_aligned;
+    out->slot_reruns = o.retried;
+    out->hap = dup(o.hap.data(), o.hap.size());
+    out->n_haps = dup(o.n_haps.data(), n_sets); out->rounds = dup(o.phase_rounds.data(), n_sets); out->site_off = dup(o.site_off.data(), (size_t)n_sets + 1);
+    out->site_col = dup(o.site_col.data(), o.site_col.size()); out->site_a1 = dup(o.site_a1.data(), o.site_a1.size());
+    out->site_a2 = dup(o.site_a2.data(), o.site_a2.size()); out->site_phase = dup(o.site_phase.data(), o.site_phase.size());
+    return 0;
+}
+
+extern "C" void hx_free_phase(hx_ctx*, hx_phase_out* o) {
+    free(o->cns_off); free(o->cns); free(o->cns_col); free(o->coverage); free(o->profile); free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa);
+    free(o->hap); free(o->n_haps); free(o->rounds); free(o->site_off); free(o->site_col); free(o->site_a1); free(o->site_a2); free(o->site_phase);
+    memset(o, 0, sizeof(*o));
+}
 extern "C" void hx_free_band(hx_ctx*, hx_band_out* o) {
     free(o->cns_off); free(o->cns); free(o->band_used); free(o->n_rows); free(o->n_cols); free(o->msa_off); free(o->msa); free(o->coverage); free(o->profile);
     memset(o, 0, sizeof(*o));

@@ -54,6 +54,10 @@ struct PoaModesArgs {
                                          // strings per set, label after label (cns_off: n_sets x n_labels + 1), their columns, and with include_consensus one row
                                          // per label behind the sequences' rows; msa / include_consensus and want_coverage / want_profile as for a strand call.
                                          // Not with graph, strand or band
+    int phase = 0;                       // 1: hx_poa_phased (the phase instances: the label instances with the phasing of the set's reads in front of the views).
+    uint32_t phase_min_count = 0;        // The call derives the label of every sequence itself (0, 1, or 255), on the device, and is in everything else a labelled
+    uint32_t phase_min_pct = 0;          // call with n_labels = 2: labels stays null. A site's second allele is seen phase_min_count times (1..255) and in
+                                         // phase_min_pct per cent (1..50) of the column's depth (the caller has checked). PoaModesOut holds the labels and the sites
     uint32_t aln_cap = 0;                // graph calls, first round only: a set's share of the alignment pool holds at most this many pairs (0: no cap); sets whose
                                          // alignments outgrow it are rerun once with exactly the room they need
 };
@@ -93,6 +97,14 @@ struct PoaModesOut {
     std::vector<uint32_t> band_used;
     uint32_t band_reruns = 0;
     uint64_t workspace_bytes = 0;
+    // phased calls: per given sequence its haplotype (0, 1, 255: none); per set its haplotypes (1: unphased, or 2) and the voting rounds run;
+    // the sites of set i are entries site_off[i] .. site_off[i + 1]: column, the two alleles (0..3 a letter, 4 a gap) and the phase (-1, 0, +1)
+    std::vector<uint8_t> hap;
+    std::vector<uint32_t> n_haps, phase_rounds;
+    std::vector<uint64_t> site_off;      // n_sets + 1
+    std::vector<uint32_t> site_col;
+    std::vector<uint8_t> site_a1, site_a2;
+    std::vector<int8_t> site_phase;
 };
 
 // 0 = ok, else -1 with the reason in err

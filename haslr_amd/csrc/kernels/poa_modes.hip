@@ -2,7 +2,8 @@
 // caller-given sequence sets (hx_poa_sequences_mode; DESIGN.md "General POA path" has the semantics and the mapping), and the affine-gap
 // engine in the same modes (hx_poa_sequences_affine: same mapping, a cell is the pair (H, F), its own row of the instance table), and the
 // two-piece affine ("convex") gap model (hx_poa_sequences_convex: a cell is (H, F, O), 12 bytes, a third row of the table). All of it is
-// one kernel template, k_poa_general<NT, CPL, GM, MSA, WTS, GRAPH, STRAND, BAND, LABELS>, GM the gap model.
+// one kernel template, k_poa_general<NT, CPL, GM, MSA, WTS, GRAPH, STRAND, BAND, LABELS>, GM the gap model (and k_poa_phase, the same loop
+// over run_set with its PHASE flag set).
 //
 // It is a kernel family of its own beside the tuned global-only k_poa (kernels/poa.hip), which depends on kNW throughout (de-ramped keys
 // with tie bits, score-bound pruning, sink lists, end-node ties decided on closures, multi-member pipelines). What the modes share with
@@ -48,6 +49,10 @@
 // shape: the graph is built as ever, and behind the last sort the workgroup runs once per label over the view of that label - the edges
 // its own sequences walk, weighed by them alone (label_views: a per-edge weight array, the rank-ordered rows without the absent edges, the
 // heaviest bundle with a branch completion that stays inside the view) - and writes one consensus and its columns per label.
+//
+// Two-haplotype consensus (hx_poa_phased; DESIGN.md "Two-haplotype consensus") is one more flag of run_set, PHASE, over LABELS (kernel k_poa_phase): between msa_columns and
+// label_views the workgroup derives the label of every sequence of its set itself (phase_reads: the heterozygous columns, a seed site,
+// at most eight voting rounds, a verdict) and label_views reads those labels as it reads a caller's, with two labels.
 //
 // Layout: the DP and traceback of the three gap models are poa_modes_dp.inl, their banded siblings poa_modes_band.inl, the columns, row text, coverage and the graph output's helpers
 // and gather and the per-label views poa_modes_out.inl, the pools of a set poa_modes_pools.inl; this file keeps the work of one set (run_set), the kernel, the
@@ -95,6 +100,11 @@ struct StrandArgs {
     uint8_t* reversed; int32_t *score_fwd, *score_rev; uint32_t* third;
 };
 
+// What the phase instances (hx_poa_phased) read and write beside the rest: the haplotype of every sequence of the call (the array the
+// label code then reads as labels), per set its haplotypes, rounds and sites, and the sites themselves from the set's first base's
+// global offset on (site_inf: a1 | a2 << 4 | (phase + 1) << 8); the two thresholds of the site rule.
+struct PhaseArgs { uint8_t* hap; uint32_t *n_haps, *rounds, *n_sites, *site_col, *site_inf; uint32_t min_count, min_pct; };
+
 struct MArgs {
     const MSet* sets; const uint32_t* order; uint32_t n_items; uint32_t* counter;
     const uint8_t* codes; const uint64_t* soff;
@@ -113,6 +123,7 @@ struct MArgs {
     // label instances only: the label of every sequence of the call (0 .. n_labels - 1, or 255: none). A set has n_labels consensus
     // places of sum_len bases each from its cns_off on, and cns_len holds n_labels lengths per set
     const uint8_t* labels; uint32_t n_labels;
+    PhaseArgs ph;         // phase instances only (labels is ph.hap, n_labels 2)
 };
 
 // one row of the MSA text: its columns (rising) start at cols[src], its letters at codes[src] (a sequence) or cns[src] (the consensus row)
@@ -171,12 +182,14 @@ struct Shared { uint32_t item, V, E, fail; int best; uint32_t na /* graph instan
 #include "poa_modes_band.inl"   // the banded row loop and traceback: one wavefront per window
 #include "poa_modes_out.inl"    // MSA columns and row text, base weights, coverage, graph and alignment output
 
-template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH, bool STRAND, bool BAND, bool LABELS>
+template <int NT, int CPL, int GM, bool MSA, bool WTS, bool GRAPH, bool STRAND, bool BAND, bool LABELS, bool PHASE>
 __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Shared& sh, int* s_wtot, uint32_t* s_scan) {
     const uint32_t t = threadIdx.x;
     const MSet S = a.sets[set];
     G g; uint32_t *path, *colref;
-    const uint64_t pools = carve_pools(slot, S.sum_len, S.nseq, S.lmax, &g, &path, &colref);
+    uint64_t pools = carve_pools(slot, S.sum_len, S.nseq, S.lmax, &g, &path, &colref);
+    const uint64_t phase_at = pools;   // phase instances: the phase pool lies behind the graph pools (the plan's slot_pools_bytes)
+    if constexpr (PHASE) pools += carve_phase(nullptr, S.sum_len, S.nseq, nullptr);
     if (pools > a.slot_bytes) { if (t == 0) a.status[set] = MS_GRAPH_OVERFLOW; return; }
     Cell<GM>* H = (Cell<GM>*)(slot + pools);
     const uint64_t hcap = (a.slot_bytes - pools) / sizeof(Cell<GM>);   // cells the slot holds
@@ -259,6 +272,11 @@ __device__ void run_set(const MArgs& a, const uint32_t set, uint8_t* slot, Share
         const uint64_t b0 = a.soff[S.seq_begin];
         if constexpr (LABELS) {
             static_assert(WTS && !GRAPH && !STRAND && !BAND, "the label instances are weighted ones, without graph output, strands and band");
+            if constexpr (PHASE) {   // (writes the labels label_views reads; the pool's pointers are made here, so that none of them lives through the DP)
+                PhasePool pp;
+                carve_phase(slot + phase_at, S.sum_len, S.nseq, &pp);
+                phase_reads<NT>(g, a, S, set, ncols, colr, pp, s_scan);
+            }
             label_views<NT>(g, a, S, set, V, E, colr, sh, s_scan);   // (reads base_col as node ids)
         }
         // (a graph instance keeps base_col as node ids: there the column travels with the node)
@@ -298,7 +316,37 @@ __global__ __launch_bounds__(NT) void k_poa_general(MArgs a) {
         const uint32_t q = sh.item;
         __syncthreads();
         if (q >= a.n_items) return;
-        run_set<NT, CPL, GM, MSA, WTS, GRAPH, STRAND, BAND, LABELS>(a, a.order[q], slot, sh, s_wtot, s_scan);
+        run_set<NT, CPL, GM, MSA, WTS, GRAPH, STRAND, BAND, LABELS, false>(a, a.order[q], slot, sh, s_wtot, s_scan);
+    }
+}
+
+// The waves per SIMD a phase instance is compiled for: its label neighbour's (DESIGN.md "Two-haplotype consensus", resources). Left to
+// itself the compiler gives the phase instances of 256 x 32 columns and of the small convex shapes a handful of registers more than 256,
+// which halves their occupancy. The rule is written for the shapes of HX_POA_INSTANCES_LINEAR / _AFFINE / _CONVEX (poa_modes_plan.h) as
+// they stand: 1 024 lanes are four waves per SIMD by themselves, the linear shapes of 16 columns per lane have three, every other shape
+// two. The assertions below fail when those lists change; the rule and the table in DESIGN.md are then to be made again from a compile
+// of the label instances with -Rpass-analysis=kernel-resource-usage.
+constexpr int waves_per_simd(int nt, int cpl, int gm) { return nt == 1024 ? 4 : gm == GM_LINEAR && cpl == 16 ? 3 : 2; }
+static_assert(INST_SHAPE[GM_LINEAR][0].nt == 64 && INST_SHAPE[GM_LINEAR][0].cpl == 16 && INST_SHAPE[GM_LINEAR][1].nt == 256 && INST_SHAPE[GM_LINEAR][1].cpl == 16 &&
+              INST_SHAPE[GM_LINEAR][2].nt == 256 && INST_SHAPE[GM_LINEAR][2].cpl == 32 && INST_SHAPE[GM_LINEAR][3].nt == 1024 && INST_SHAPE[GM_AFFINE][2].nt == 512 &&
+              INST_SHAPE[GM_AFFINE][3].nt == 1024 && INST_SHAPE[GM_CONVEX][1].nt == 128 && INST_SHAPE[GM_CONVEX][3].nt == 512 && N_INST == 4,
+              "waves_per_simd() was made for these instance shapes");
+
+// The phase instances (hx_poa_phased): k_poa_general's loop over run_set with LABELS and PHASE, as a kernel of their own, so that the
+// occupancy attribute stands on them alone and the declaration of k_poa_general stays as it was.
+template <int NT, int CPL, int GM>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(waves_per_simd(NT, CPL, GM)))) void k_poa_phase(MArgs a) {
+    __shared__ Shared sh;
+    __shared__ int s_wtot[(GM == GM_CONVEX ? 2 : 1) * (NT / 64)];
+    __shared__ uint32_t s_scan[NT / 64];
+    uint8_t* slot = a.ws + (size_t)blockIdx.x * a.slot_bytes;
+    for (;;) {
+        if (threadIdx.x == 0) sh.item = atomicAdd(a.counter, 1u);
+        __syncthreads();
+        const uint32_t q = sh.item;
+        __syncthreads();
+        if (q >= a.n_items) return;
+        run_set<NT, CPL, GM, true, true, false, false, false, true, true>(a, a.order[q], slot, sh, s_wtot, s_scan);
     }
 }
 
@@ -325,6 +373,10 @@ static_assert(MAX_LEN[GM_LINEAR] + 1 <= (BAND_SEQ_WORDS - 1) * 16, "the staged s
 #define HX_LABEL(GM, NT, CPL) (const void*)k_poa_general<NT, CPL, GM, true, true, false, false, false, true>
 const void* const kLabel[3][N_INST] = {{HX_POA_INSTANCES_LINEAR(HX_LABEL)}, {HX_POA_INSTANCES_AFFINE(HX_LABEL)}, {HX_POA_INSTANCES_CONVEX(HX_LABEL)}};
 #undef HX_LABEL
+// the phase instances (hx_poa_phased; DESIGN.md "Two-haplotype consensus"): the label instance of every shape with the phasing of the set's reads in front of its views
+#define HX_PHASE(GM, NT, CPL) (const void*)k_poa_phase<NT, CPL, GM>
+const void* const kPhase[3][N_INST] = {{HX_POA_INSTANCES_LINEAR(HX_PHASE)}, {HX_POA_INSTANCES_AFFINE(HX_PHASE)}, {HX_POA_INSTANCES_CONVEX(HX_PHASE)}};
+#undef HX_PHASE
 inline const void* fn(const Inst& inst, bool cols, bool weighted, bool graph, bool strand) { return inst.variant[strand ? 4 : graph ? 3 : weighted ? 2 : cols ? 1 : 0]; }
 
 template <class T> struct Buf {   // device buffer of one call
@@ -361,7 +413,8 @@ struct Run {
     uint64_t budget = 0;
     Buf<MSet> d_sets; Buf<uint8_t> d_codes; Buf<uint64_t> d_soff; Buf<uint32_t> d_order, d_counter, d_status, d_vseen, d_cns_len; Buf<unsigned long long> d_cells; Buf<char> d_cns;
     Buf<uint32_t> d_base_col, d_n_cols, d_cns_col;   // MSA and weighted calls only
-    Buf<uint8_t> d_labels;                           // labelled calls only: a label per sequence
+    Buf<uint8_t> d_labels;                           // labelled calls only: a label per sequence (phased calls: written by the kernel)
+    Buf<uint32_t> d_n_haps, d_rounds, d_n_sites, d_site_col, d_site_inf;   // phased calls only: what PhaseArgs points to
     Buf<uint32_t> d_band;                            // banded calls only: per set the half-width of its current attempt
     Buf<uint8_t> d_wts;                              // weighted calls with weights only: a byte per base (graph and strand calls: always, 1 without weights)
     // strand calls only: what StrandArgs points to
@@ -374,7 +427,7 @@ struct Run {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~Run() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
 
-    const void* fn_of(int k) const { return c.labels ? kLabel[c.gm][k] : fn(k == BAND_INST ? kBand[c.gm] : kInst[c.gm][k], c.cols, d_wts.p != nullptr, c.graph, c.strand); }
+    const void* fn_of(int k) const { return c.phase ? kPhase[c.gm][k] : c.labels ? kLabel[c.gm][k] : fn(k == BAND_INST ? kBand[c.gm] : kInst[c.gm][k], c.cols, d_wts.p != nullptr, c.graph, c.strand); }
     const uint8_t* codes_as_added() const { return c.strand ? d_codes_used.p : d_codes.p; }   // what the row, coverage and profile kernels read
 
     // runs f (0 = ok) between two events, waits for it, and adds the milliseconds it took on the device to *ms
@@ -418,7 +471,11 @@ struct Run {
             MCHK(hipMemcpyAsync(d_wts.p, a.weights, nb, hipMemcpyHostToDevice, s));
         }
         if ((c.graph || c.strand || c.labels) && !a.weights) { MCHK(d_wts.alloc(nb)); MCHK(d_wts.fill(1, nb, s)); }
-        if (c.labels) { MCHK(d_labels.alloc(nseq)); MCHK(hipMemcpyAsync(d_labels.p, a.labels, nseq, hipMemcpyHostToDevice, s)); }
+        if (c.labels && !c.phase) { MCHK(d_labels.alloc(nseq)); MCHK(hipMemcpyAsync(d_labels.p, a.labels, nseq, hipMemcpyHostToDevice, s)); }
+        if (c.phase) {   // (a set without a base runs nowhere: its sequences keep 255, its counts 0)
+            MCHK(d_labels.alloc(nseq)); MCHK(d_n_haps.alloc(ns)); MCHK(d_rounds.alloc(ns)); MCHK(d_n_sites.alloc(ns)); MCHK(d_site_col.alloc(nb)); MCHK(d_site_inf.alloc(nb));
+            MCHK(d_labels.fill(0xff, nseq, s)); MCHK(d_n_haps.fill(0, ns, s)); MCHK(d_rounds.fill(0, ns, s)); MCHK(d_n_sites.fill(0, ns, s));
+        }
         if (c.strand) {
             MCHK(d_codes_rc.alloc(nb)); MCHK(d_codes_used.alloc(nb)); MCHK(d_wts_used.alloc(nb));
             MCHK(d_reversed.alloc(nseq)); MCHK(d_score_fwd.alloc(nseq)); MCHK(d_score_rev.alloc(nseq)); MCHK(d_third.alloc(ns));
@@ -490,7 +547,8 @@ struct Run {
                     MArgs q{d_sets.p, d_order.p + pk.base, (uint32_t)pk.sets.size(), d_counter.p + k, d_codes.p, d_soff.p, (uint8_t*)ws.p, pk.slot,
                             a.match, a.mismatch, a.gap, a.type, d_cns.p, d_cns_len.p, d_status.p, d_vseen.p, d_cells.p, a.gap_extend,
                             d_base_col.p, d_n_cols.p, d_cns_col.p, d_wts.p, a.gap_open2, a.gap_extend2, go,
-                            StrandArgs{d_codes_rc.p, d_wts_rc.p ? d_wts_rc.p : d_wts.p, d_codes_used.p, d_wts_used.p, d_reversed.p, d_score_fwd.p, d_score_rev.p, d_third.p}, d_band.p, d_labels.p, c.nl};
+                            StrandArgs{d_codes_rc.p, d_wts_rc.p ? d_wts_rc.p : d_wts.p, d_codes_used.p, d_wts_used.p, d_reversed.p, d_score_fwd.p, d_score_rev.p, d_third.p}, d_band.p, d_labels.p, c.nl,
+                            PhaseArgs{d_labels.p, d_n_haps.p, d_rounds.p, d_n_sites.p, d_site_col.p, d_site_inf.p, a.phase_min_count, a.phase_min_pct}};
                     void* kargs[] = {&q};
                     MCHK(hipLaunchKernel(fn_of(k), dim3(pk.nslots), dim3((uint32_t)shape_of(c.gm, k).nt), kargs, 0, s));
                     o.launches++;
@@ -534,6 +592,7 @@ struct Run {
             MCHK(d_cns_col.download(col.data(), ncns));
             for (uint64_t j = 0; j < nlen; j++) o.cns_col.insert(o.cns_col.end(), col.begin() + c.cns_off[j], col.begin() + c.cns_off[j] + len[j]);
         }
+        if (c.phase && phase_out()) return -1;
         if (c.strand) {   // (a set that was rerun rewrote its own part)
             std::vector<uint32_t> third(ns);
             o.reversed.assign(nseq, 0); o.score_fwd.assign(nseq, 0); o.score_rev.assign(nseq, 0);
@@ -541,6 +600,31 @@ struct Run {
             if (nseq) { MCHK(d_reversed.download(o.reversed.data(), nseq)); MCHK(d_score_fwd.download(o.score_fwd.data(), nseq)); MCHK(d_score_rev.download(o.score_rev.data(), nseq)); }
             for (uint32_t i = 0; i < ns; i++) o.third_passes += third[i];
         }
+        return 0;
+    }
+
+    // ---- the haplotypes and the sites of a phased call (a set that was rerun rewrote its own part): the sites dense, set after set. The
+    // haplotypes are from here on the labels the plan of the coverage reads (c.lab)
+    int phase_out() {
+        const uint32_t ns = c.ns;
+        const uint64_t nseq = c.nseq, nb = c.nb;
+        std::vector<uint32_t> n_sites(ns), col(std::max<uint64_t>(1, nb)), inf(std::max<uint64_t>(1, nb));
+        o.hap.assign(std::max<uint64_t>(1, nseq), 255); o.n_haps.assign(ns, 1); o.phase_rounds.assign(ns, 0); o.site_off.assign((size_t)ns + 1, 0);
+        if (nseq) MCHK(d_labels.download(o.hap.data(), nseq));
+        o.hap.resize(nseq);
+        if (ns) { MCHK(d_n_haps.download(o.n_haps.data(), ns)); MCHK(d_rounds.download(o.phase_rounds.data(), ns)); MCHK(d_n_sites.download(n_sites.data(), ns)); }
+        if (nb) { MCHK(d_site_col.download(col.data(), nb)); MCHK(d_site_inf.download(inf.data(), nb)); }
+        for (uint32_t i = 0; i < ns; i++) {
+            if (!c.sets[i].sum_len) o.n_haps[i] = 1;   // (no base: one haplotype without a member)
+            if (n_sites[i] > c.sets[i].sum_len) { err = c.who + ": internal error (set " + std::to_string(i) + " reports " + std::to_string(n_sites[i]) + " sites on " + std::to_string(c.sets[i].sum_len) + " bases)"; return -1; }
+            const uint64_t b0 = a.seq_off[a.set_off[i]];
+            for (uint32_t j = 0; j < n_sites[i]; j++) {
+                o.site_col.push_back(col[b0 + j]); o.site_a1.push_back((uint8_t)(inf[b0 + j] & 15u)); o.site_a2.push_back((uint8_t)(inf[b0 + j] >> 4 & 15u));
+                o.site_phase.push_back((int8_t)((int)(inf[b0 + j] >> 8 & 3u) - 1));
+            }
+            o.site_off[i + 1] = o.site_col.size();
+        }
+        c.lab = o.hap.data();
         return 0;
     }
 

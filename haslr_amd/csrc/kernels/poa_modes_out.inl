@@ -1,6 +1,6 @@
 // poa_modes_out.inl - what the general POA path (kernels/poa_modes.hip) writes beside the consensus text: the columns of the multiple sequence
 // alignment and its row text, the base weights on the graph's edges, the coverage of the consensus bases, the graph and the alignments
-// themselves, and the per-label views of a set's graph with their consensus. Included inside that file's anonymous namespace, after MRow, GraphOutArgs and block_excl_sum.
+// themselves, the per-label views of a set's graph with their consensus, and the phasing of a set's reads into two haplotypes. Included inside that file's anonymous namespace, after MRow, GraphOutArgs and block_excl_sum.
 
 // ---- MSA output (DESIGN.md "General POA path", "MSA output") ----
 // The columns of spoa's generate_multiple_sequence_alignment on the final rank order (order_rows leaves aligned nodes contiguous): rank r
@@ -335,4 +335,225 @@ __device__ void label_views(G& g, const MArgs& a, const MSet& S, const uint32_t 
         }
         __syncthreads();   // the next label rewrites vw, the rows and the smallest id
     }
+}
+
+// ---- two-haplotype consensus (DESIGN.md "General POA path", "Two-haplotype consensus") ----
+constexpr uint32_t PHASE_ROUNDS = 8, HAP_NONE = 255;
+
+__device__ __forceinline__ int wave_sum(int v) {
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// All lanes, after the last sort and msa_columns, while base_col still holds the node of every base, and in front of label_views: the
+// haplotype of every sequence of the set (a.ph.hap: 0, 1, or 255 for none), the set's sites, rounds and verdict. The rules are DESIGN.md's,
+// held to tests/poa_phase_ref.cpp; the work is laid out so that nothing is sequences x columns:
+//   counts   one lane per base adds to its column's letter count; a sequence marks + 1 at its first column and - 1 behind its last, a block
+//            scan of the marks is the depth, and the gaps of a column are its depth less its letters
+//   sites    one lane per column tests the rule; a second block scan in the same pass numbers the sites; the seed is a 64-bit atomic
+//            maximum over (minor count, sites counted from the back)
+//   a base   then keeps one word: its site, its vote there (a1 + 1, a2 - 1, else 0) and the site's gap vote (a1 is the gap + 1, a2 - 1),
+//            packed as site << 4 | (vote + 1) << 2 | (gap vote + 1); NONE: the base stands in no site
+//   a round  with z = + 1 / - 1 / 0 for a sequence of haplotype 0 / 1 / none, a site's difference is the sum over the sequences that span
+//            it of z x (their vote, or the gap vote where they have no base): every base at a site adds z x (vote - gap vote), the span of
+//            every sequence marks + z / - z over the sites, and the scan of the marks times the gap vote is the rest. The sum of a sequence
+//            is the same the other way round: its bases add sign x (vote - gap vote), and the prefix of sign x gap vote over its sites is
+//            the rest. One wavefront per sequence, no barrier inside; the round's barriers stand in block-uniform code (the number of
+//            sites and the changed flag are the same value in every lane)
+// The pool: carve_phase (poa_modes_pools.inl); the few block-wide scalars (the seed's key, the changed flag, the members of the two
+// haplotypes, the first assigned sequence) are words of it, reached by atomics.
+template <int NT>
+__device__ void phase_reads(const G& g, const MArgs& a, const MSet& S, const uint32_t set, const uint32_t C, const uint32_t* colr, const PhasePool& P, uint32_t* s_scan) {
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    constexpr uint32_t NW = NT / 64;
+    const uint32_t n = S.nseq, T = (uint32_t)S.sum_len;
+    const uint64_t* soff = a.soff + S.seq_begin;
+    const uint64_t b0 = soff[0];
+    const uint32_t* node = a.base_col + b0;
+    const uint8_t* code = a.codes + b0;
+    uint8_t* hap = a.ph.hap + S.seq_begin;
+    // ---- the letter counts and the span marks (no run-time loop of this function is unrolled: twelve instances carry its code, and none of the loops is hot)
+#pragma unroll 1
+    for (uint32_t i = t; i < 4 * C; i += NT) P.cnt[i] = 0;
+#pragma unroll 1
+    for (uint32_t i = t; i <= C; i += NT) P.dep[i] = 0;
+    unsigned long long* key = (unsigned long long*)P.scal;
+    uint32_t *changed_at = P.scal + 2, *members = P.scal + 3, *first_at = P.scal + 5;
+    if (t == 0) *key = 0;
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t i = t; i < T; i += NT) {
+        const uint32_t c = colr[g.node2rank[node[i]]];
+        P.base[i] = c;
+        if (c < C) atomicAdd(&P.cnt[4 * c + code[i]], 1u);   // (c < C always: the guard keeps the add inside the array)
+    }
+#pragma unroll 1
+    for (uint32_t k = t; k < n; k += NT) {
+        const uint32_t b = (uint32_t)(soff[k] - b0), L = (uint32_t)(soff[k + 1] - soff[k]);
+        if (!L) continue;
+        const uint32_t f = min(colr[g.node2rank[node[b]]], C - 1), l = min(colr[g.node2rank[node[b + L - 1]]], C - 1);   // (both below C always)
+        P.lo[k] = f; P.hi[k] = l;
+        atomicAdd(&P.dep[f], 1u);
+        atomicAdd(&P.dep[l + 1], 0xffffffffu);
+    }
+    __syncthreads();
+    // ---- depth, the site rule, the sites numbered in column order, the seed
+    uint32_t carry_d = 0, Sn = 0;
+#pragma unroll 1
+    for (uint32_t cb = 0; cb < C; cb += NT) {
+        const uint32_t c = cb + t, mark = c < C ? P.dep[c] : 0u;
+        uint32_t tot;
+        const uint32_t d = carry_d + block_excl_sum<NT>(mark, s_scan, &tot) + mark;
+        carry_d += tot;
+        uint32_t site = 0, al = 0, n2 = 0;
+        if (c < C) {
+            uint32_t cn[5];
+            cn[4] = d;
+#pragma unroll
+            for (uint32_t q = 0; q < 4; q++) { cn[q] = P.cnt[4 * c + q]; cn[4] -= cn[q]; }
+            uint32_t a1 = 0, n1 = cn[0], a2 = 5;   // by count, falling, then by code, rising
+#pragma unroll
+            for (uint32_t q = 1; q < 5; q++) if (cn[q] > n1) { n1 = cn[q]; a1 = q; }
+#pragma unroll
+            for (uint32_t q = 0; q < 5; q++) if (q != a1 && (a2 == 5 || cn[q] > n2)) { n2 = cn[q]; a2 = q; }
+            site = n2 >= max(a.ph.min_count, (a.ph.min_pct * d + 99u) / 100u);
+            al = a1 | a2 << 4;
+        }
+        const uint32_t j = Sn + block_excl_sum<NT>(site, s_scan, &tot);
+        Sn += tot;
+        if (c < C) {
+            P.spre[c] = j;
+            if (site) { P.s_col[j] = c; P.s_al[j] = al; atomicMax(key, (unsigned long long)n2 << 32 | (0xffffffffu - j)); }
+        }
+    }
+    if (t == 0) P.spre[C] = Sn;
+    __syncthreads();
+    // ---- every base's word, every sequence's span in sites
+#pragma unroll 1
+    for (uint32_t i = t; i < T; i += NT) {
+        const uint32_t c = min(P.base[i], C - 1), j = P.spre[c];
+        uint32_t word = NONE;
+        if (P.spre[c + 1] != j) {
+            const uint32_t al = P.s_al[j], a1 = al & 15u, a2 = al >> 4, x = code[i];
+            word = j << 4 | (x == a1 ? 2u : x == a2 ? 0u : 1u) << 2 | (a1 == 4 ? 2u : a2 == 4 ? 0u : 1u);
+        }
+        P.base[i] = word;
+    }
+#pragma unroll 1
+    for (uint32_t k = t; k < n; k += NT) {
+        if (soff[k + 1] == soff[k]) continue;
+        const uint32_t f = P.lo[k], l = P.hi[k];
+        P.lo[k] = P.spre[f]; P.hi[k] = P.spre[l + 1];
+    }
+    __syncthreads();
+    // ---- the seed's haplotypes: one wavefront per sequence (every condition on k alone is the same in its 64 lanes)
+    const uint32_t jstar = 0xffffffffu - (uint32_t)*key;
+    const uint32_t al_star = Sn ? P.s_al[jstar] : 0u;
+#pragma unroll 1
+    for (uint32_t k = w; k < n; k += NW) {
+        const uint32_t b = (uint32_t)(soff[k] - b0), L = (uint32_t)(soff[k + 1] - soff[k]);
+        uint32_t h = HAP_NONE;
+        if (Sn && L && P.lo[k] <= jstar && jstar < P.hi[k]) {
+            uint32_t vote = 3;
+#pragma unroll 1
+            for (uint32_t i = lane; i < L; i += 64) { const uint32_t word = P.base[b + i]; if (word != NONE && word >> 4 == jstar) vote = word >> 2 & 3u; }
+            const unsigned long long has = __ballot(vote != 3);   // (at most one base of a sequence stands in a column)
+            vote = has ? (uint32_t)__shfl((int)vote, __builtin_ctzll(has)) : ((al_star & 15u) == 4 ? 2u : (al_star >> 4) == 4 ? 0u : 1u);
+            h = vote == 2 ? 0u : vote == 0 ? 1u : HAP_NONE;
+        }
+        if (lane == 0) hap[k] = (uint8_t)h;
+    }
+    __syncthreads();
+    // ---- the rounds
+    uint32_t rounds = 0;
+#pragma unroll 1
+    while (Sn && rounds < PHASE_ROUNDS) {
+#pragma unroll 1
+        for (uint32_t j = t; j <= Sn; j += NT) { P.s_d[j] = 0; P.s_mark[j] = 0; }
+        if (t == 0) *changed_at = 0;
+        __syncthreads();
+#pragma unroll 1
+        for (uint32_t k = w; k < n; k += NW) {
+            const uint32_t b = (uint32_t)(soff[k] - b0), L = (uint32_t)(soff[k + 1] - soff[k]), h = hap[k];
+            if (!L || h == HAP_NONE) continue;
+            const int z = h ? -1 : 1;
+            if (lane == 0 && P.lo[k] < P.hi[k]) { atomicAdd(&P.s_mark[P.lo[k]], z); atomicAdd(&P.s_mark[P.hi[k]], -z); }
+#pragma unroll 1
+            for (uint32_t i = lane; i < L; i += 64) {
+                const uint32_t word = P.base[b + i];
+                if (word == NONE) continue;
+                const int v = (int)(word >> 2 & 3u) - (int)(word & 3u);
+                if (v && (word >> 4) < Sn) atomicAdd(&P.s_d[word >> 4], z * v);   // (below Sn always)
+            }
+        }
+        __syncthreads();
+        int carry_z = 0, carry_g = 0;
+#pragma unroll 1
+        for (uint32_t jb = 0; jb < Sn; jb += NT) {
+            const uint32_t j = jb + t, mark = j < Sn ? (uint32_t)P.s_mark[j] : 0u;
+            uint32_t tot;
+            const int zs = carry_z + (int)(block_excl_sum<NT>(mark, s_scan, &tot) + mark);   // z over the sequences that span site j
+            carry_z += (int)tot;
+            int gv = 0, sg = 0;
+            if (j < Sn) {
+                const uint32_t al = P.s_al[j];
+                gv = (al & 15u) == 4 ? 1 : (al >> 4) == 4 ? -1 : 0;
+                const int D = P.s_d[j] + gv * zs;
+                sg = D > 0 ? 1 : D < 0 ? -1 : 0;
+                P.s_sign[j] = sg;
+            }
+            const int gp = carry_g + (int)block_excl_sum<NT>((uint32_t)(sg * gv), s_scan, &tot);
+            carry_g += (int)tot;
+            if (j < Sn) P.s_gp[j] = gp;
+        }
+        if (t == 0) P.s_gp[Sn] = carry_g;
+        __syncthreads();
+#pragma unroll 1
+        for (uint32_t k = w; k < n; k += NW) {
+            const uint32_t b = (uint32_t)(soff[k] - b0), L = (uint32_t)(soff[k + 1] - soff[k]);
+            if (!L) continue;
+            int sum = 0;
+#pragma unroll 1
+            for (uint32_t i = lane; i < L; i += 64) {
+                const uint32_t word = P.base[b + i];
+                if (word != NONE) sum += P.s_sign[word >> 4] * ((int)(word >> 2 & 3u) - (int)(word & 3u));
+            }
+            sum = wave_sum(sum) + P.s_gp[P.hi[k]] - P.s_gp[P.lo[k]];
+            const uint32_t h = hap[k], nh = sum > 0 ? 0u : sum < 0 ? 1u : h;
+            if (lane == 0 && nh != h) { hap[k] = (uint8_t)nh; *changed_at = 1; }
+        }
+        __syncthreads();
+        rounds++;
+        const uint32_t changed = *changed_at;
+        __syncthreads();   // (the next round clears the flag)
+        if (!changed) break;
+    }
+    // ---- the verdict, the renaming, the set's outputs
+    if (t == 0) { members[0] = 0; members[1] = 0; *first_at = NONE; }
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t k = t; k < n; k += NT) {
+        if (soff[k + 1] == soff[k]) continue;
+        const uint32_t h = hap[k];
+        if (h == HAP_NONE) continue;
+        atomicAdd(&members[h], 1u);
+        atomicMin(first_at, k);
+    }
+    __syncthreads();
+    const bool phased = Sn && members[0] >= a.ph.min_count && members[1] >= a.ph.min_count;
+    const bool flip = phased && hap[min(*first_at, n - 1)] == 1;   // (phased: both haplotypes have members, *first_at is the first of them)
+    __syncthreads();   // every lane has read that sequence's haplotype before any is renamed
+#pragma unroll 1
+    for (uint32_t k = t; k < n; k += NT) {
+        const uint32_t h = hap[k];
+        hap[k] = (uint8_t)(soff[k + 1] == soff[k] ? HAP_NONE : !phased ? 0u : h == HAP_NONE ? HAP_NONE : h ^ (uint32_t)flip);
+    }
+#pragma unroll 1
+    for (uint32_t j = t; j < Sn; j += NT) {   // (a set has no more sites than bases: its sites start at its first base's offset)
+        const int sg = !phased ? 0 : flip ? -P.s_sign[j] : P.s_sign[j];
+        a.ph.site_col[b0 + j] = P.s_col[j];
+        a.ph.site_inf[b0 + j] = P.s_al[j] | (uint32_t)(sg + 1) << 8;
+    }
+    if (t == 0) { a.ph.n_haps[set] = phased ? 2u : 1u; a.ph.rounds[set] = rounds; a.ph.n_sites[set] = Sn; }
+    __syncthreads();   // label_views reads the haplotypes as labels
 }

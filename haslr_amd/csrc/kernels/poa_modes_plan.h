@@ -58,6 +58,8 @@ struct ModesCall {
     bool band = false;                                       // hx_poa_banded: sets run inside an adaptive band as long as they do not miss it
     bool labels = false;                                     // hx_poa_labelled: one consensus per label and set over the set's one graph
     uint32_t nl = 1;                                         // consensus places per set: the call's n_labels, 1 without labels
+    bool phase = false;                                      // hx_poa_phased: a labelled call (labels is set, nl is 2) whose labels the device derives
+    const uint8_t* lab = nullptr;                            // labelled calls: the label of every sequence (the caller's; phased calls: what poa_modes_run downloaded, null until then)
     uint64_t nseq = 0, nb = 0;
     std::vector<MSet> sets;
     std::vector<uint64_t> cns_off;                           // ns x nl + 1: place g of set i is entry i x nl + g
@@ -83,6 +85,10 @@ struct ModesState {
 
 // the graph pools of a set in bytes: carve_pools (poa_modes_pools.inl) itself, asked without a slot
 uint64_t pools_bytes(const MSet& S);
+// the phase pool of a set in bytes (phased calls: behind the graph pools of the set's slot): carve_phase (poa_modes_pools.inl) itself
+uint64_t phase_pool_bytes(uint64_t sum_len, uint32_t nseq);
+// what a set's slot holds in front of H: the graph pools, and in a phased call the phase pool
+uint64_t slot_pools_bytes(const ModesCall& c, uint32_t set);
 // the first instance whose NT x CPL columns hold the set's longest sequence + 1
 int inst_of(const ModesCall& c, uint32_t set);
 // the slot of a round's plan a set runs in: BAND_INST while it has a half-width, else inst_of(c, set)

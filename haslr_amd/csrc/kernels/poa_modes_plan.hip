@@ -13,6 +13,8 @@ namespace {
 }  // namespace
 
 uint64_t pools_bytes(const MSet& S) { return carve_pools(nullptr, S.sum_len, S.nseq, S.lmax, nullptr, nullptr, nullptr); }
+uint64_t phase_pool_bytes(uint64_t sum_len, uint32_t nseq) { return carve_phase(nullptr, sum_len, nseq, nullptr); }
+uint64_t slot_pools_bytes(const ModesCall& c, uint32_t set) { return pools_bytes(c.sets[set]) + (c.phase ? phase_pool_bytes(c.sets[set].sum_len, c.sets[set].nseq) : 0); }
 
 int inst_of(const ModesCall& c, uint32_t set) {
     const InstShape* inst = INST_SHAPE[c.gm];
@@ -33,11 +35,16 @@ int describe(const PoaModesArgs& a, ModesCall& c, ModesState& st, std::string& e
     st = ModesState();
     c.a = &a; c.who = a.who; c.ns = a.n_sets; c.gm = a.gap_model;
     c.msa = a.msa != 0; c.wtd = a.weighted != 0; c.graph = a.graph != 0; c.strand = a.strand != 0;
-    c.labels = a.labels != nullptr; c.nl = c.labels ? a.n_labels : 1u;
+    c.phase = a.phase != 0;
+    if (c.phase && a.labels) { err = c.who + ": a phased call derives its labels itself and takes none"; return -1; }
+    c.labels = a.labels != nullptr || c.phase; c.nl = c.phase ? 2u : c.labels ? a.n_labels : 1u; c.lab = a.labels;
     c.cols = c.msa || c.wtd || c.graph || c.strand || c.labels;
     c.want_cov = (c.wtd || c.strand || c.labels) && (a.want_coverage || a.want_profile);
     c.band = a.band != 0;
     if (c.labels && (c.nl < 1 || c.nl > 16)) { err = c.who + ": n_labels must be 1..16, not " + std::to_string(c.nl); return -1; }
+    if (c.phase && (a.phase_min_count < 1 || a.phase_min_count > 255)) { err = c.who + ": min_count must be 1..255, not " + std::to_string(a.phase_min_count); return -1; }
+    if (c.phase && (a.phase_min_pct < 1 || a.phase_min_pct > 50)) { err = c.who + ": min_pct must be 1..50, not " + std::to_string(a.phase_min_pct); return -1; }
+    if (c.phase && (c.graph || c.strand || c.band)) { err = c.who + ": graph output, strand-ambiguous sets and banded alignment have no phasing"; return -1; }
     if (c.labels && (c.graph || c.strand || c.band)) { err = c.who + ": graph output, strand-ambiguous sets and banded alignment have no labels"; return -1; }
     if (c.band && a.band > MAX_BAND) { err = c.who + ": the band half-width must be 1.." + std::to_string(MAX_BAND) + ", not " + std::to_string(a.band); return -1; }
     if (c.band && (c.graph || c.strand)) { err = c.who + ": graph output and strand-ambiguous sets have no band"; return -1; }
@@ -126,8 +133,8 @@ int plan_round(const ModesCall& c, ModesState& st, const bool first, const uint6
     const uint64_t cell_bytes = CELL_BYTES[c.gm];
     // (a banded set: vest + 1 rows of B cells, and the rows' three word arrays)
     auto need = [&](uint32_t i) {
-        if (c.band && st.band[i]) return pools_bytes(sets[i]) + al256((st.vest[i] + 1) * (2 * (uint64_t)st.band[i] + 1) * cell_bytes + 12 * (st.vest[i] + 1));
-        return pools_bytes(sets[i]) + al256((st.vest[i] + 1) * (uint64_t)(sets[i].lmax + 1) * cell_bytes);
+        if (c.band && st.band[i]) return slot_pools_bytes(c, i) + al256((st.vest[i] + 1) * (2 * (uint64_t)st.band[i] + 1) * cell_bytes + 12 * (st.vest[i] + 1));
+        return slot_pools_bytes(c, i) + al256((st.vest[i] + 1) * (uint64_t)(sets[i].lmax + 1) * cell_bytes);
     };
     p = RoundPlan();
     for (uint32_t i : st.todo) p.inst[slot_of(c, st, i)].sets.push_back(i);
@@ -140,7 +147,7 @@ int plan_round(const ModesCall& c, ModesState& st, const bool first, const uint6
         for (uint32_t i : v) {
             const uint64_t nd = need(i);
             if (nd > sb) { sb = nd; big = i; }
-            pmax = std::max(pmax, pools_bytes(sets[i]));
+            pmax = std::max(pmax, slot_pools_bytes(c, i));
         }
         if (first && a.slot_kb_cap) sb = std::max(pmax, std::min<uint64_t>(sb, (uint64_t)a.slot_kb_cap << 10));   // (test switch: forces the overflow and rerun)
         sb = al256(sb);
@@ -222,7 +229,7 @@ int plan_coverage(const ModesCall& c, const std::vector<uint32_t>& ncols, const 
         for (uint64_t k = a.set_off[i]; k < a.set_off[i + 1]; k++) {
             const uint32_t L = (uint32_t)(a.seq_off[k + 1] - a.seq_off[k]);
             if (L < 2) continue;   // (spoa counts the sequence labels of a node's edges: a sequence of one base has none)
-            const uint32_t g = c.labels ? a.labels[k] : 0u;
+            const uint32_t g = c.labels ? c.lab[k] : 0u;
             if (g >= nl) continue;   // (a labelled call: the sequence has no label)
             p.seqs.add(CovRow{a.seq_off[k], 0, hoff + (uint64_t)g * ncols[i], L, ncols[i]}, L);
             hist_bases += L;

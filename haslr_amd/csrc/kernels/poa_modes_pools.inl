@@ -27,3 +27,26 @@ __host__ __device__ inline uint64_t carve_pools(uint8_t* base, uint64_t T, uint3
     if (g) { *g = t; *path = p; *colref = c; }
     return off;
 }
+
+// The phase pool of a set (phase instances only; phase_reads, poa_modes_out.inl), behind the graph pools of its slot: words, sized from the
+// set's bases T and sequences nseq alone. A set has at most T columns and at most as many sites as columns.
+//   cnt    4 per column   the letter counts of the column
+//   dep    1 per column   + 1: the span marks, then the depth
+//   spre   1 per column   + 1: the sites in front of the column
+//   base   1 per base     the column of the base, then its site, its vote and the site's gap vote, packed
+//   s_col, s_al, s_sign, s_d, s_mark, s_gp   6 per site, + 1 each: the site's column, alleles, sign, the round's difference, its span marks
+//          and the prefix of the gap votes
+//   lo, hi 2 per sequence: first its span in columns, then in sites
+//   scal   8 words: the block-wide scalars (the first two one 64-bit word)
+struct PhasePool { uint32_t *cnt, *dep, *spre, *base, *s_col, *s_al; int32_t *s_sign, *s_d, *s_mark, *s_gp; uint32_t *lo, *hi, *scal; };
+__host__ __device__ inline uint64_t carve_phase(uint8_t* base, uint64_t T, uint32_t nseq, PhasePool* pp) {
+    const uint64_t cc = T + 1;
+    uint64_t off = 0;
+    auto take = [&](uint64_t words) -> uint32_t* { uint32_t* p = base ? (uint32_t*)(base + off) : nullptr; off += al256(4 * words); return p; };
+    PhasePool t{};
+    t.cnt = take(4 * cc); t.dep = take(cc); t.spre = take(cc); t.base = take(cc);
+    t.s_col = take(cc); t.s_al = take(cc); t.s_sign = (int32_t*)take(cc); t.s_d = (int32_t*)take(cc); t.s_mark = (int32_t*)take(cc); t.s_gp = (int32_t*)take(cc);
+    t.lo = take((uint64_t)nseq + 1); t.hi = take((uint64_t)nseq + 1); t.scal = take(8);
+    if (pp) *pp = t;
+    return off;
+}

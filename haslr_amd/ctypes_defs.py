@@ -220,6 +220,15 @@ class LabelOut(C.Structure):
                 ("dp_cells", C.c_uint64), ("seq_bases", C.c_uint64), ("n_aligned", C.c_uint64), ("slot_reruns", C.c_uint32)]
 
 
+class PoaPhaseParams(C.Structure):
+    _fields_ = [("min_count", C.c_uint32), ("min_pct", C.c_uint32), ("want_msa", C.c_int32), ("include_consensus", C.c_int32), ("want_coverage", C.c_int32), ("want_profile", C.c_int32)]
+
+
+class PhaseOut(C.Structure):
+    _fields_ = LabelOut._fields_ + [("hap", C.POINTER(C.c_uint8)), ("n_haps", u32p), ("rounds", u32p), ("site_off", u64p), ("site_col", u32p),
+                                    ("site_a1", C.POINTER(C.c_uint8)), ("site_a2", C.POINTER(C.c_uint8)), ("site_phase", C.POINTER(C.c_int8))]
+
+
 def msa_to_lists(o):
     """(rows per set, consensus per set) of an MsaOut"""
     n = o.n_set

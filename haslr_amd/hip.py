@@ -16,7 +16,7 @@ _lib = None
 SYMBOLS = ["hx_last_error", "hx_device_count", "hx_ctx_create", "hx_ctx_destroy", "hx_upload", "hx_set_read_shard", "hx_set_prefiltered",
            "hx_chain_reads", "hx_edge_support", "hx_edge_coords", "hx_poa_batch", "hx_free_chain", "hx_free_edges",
            "hx_free_coords", "hx_free_cns", "hx_edge_emit", "hx_edge_records_bytes", "hx_edge_records_export",
-           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_poa_graph", "hx_free_graph", "hx_poa_strand", "hx_free_strand", "hx_poa_banded", "hx_free_band", "hx_poa_labelled", "hx_free_label", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
+           "hx_edge_records_import", "hx_poa_supports", "hx_poa_sequences", "hx_poa_sequences_mode", "hx_poa_sequences_affine", "hx_poa_msa", "hx_free_msa", "hx_poa_weighted", "hx_free_wcns", "hx_poa_sequences_convex", "hx_poa_msa_convex", "hx_poa_weighted_convex", "hx_poa_graph", "hx_free_graph", "hx_poa_strand", "hx_free_strand", "hx_poa_banded", "hx_free_band", "hx_poa_labelled", "hx_free_label", "hx_poa_phased", "hx_free_phase", "hx_timing_reset", "hx_timing_get", "hx_set_poa_block", "hx_backend_fill", "hx_poa_phase_cycles", "hx_set_poa_traceback", "hx_poa_workspace_bytes",
            "hx_set_option", "hx_get_option", "hx_option_names", "hx_poa_memory_stats", "hx_poa_release_workspace", "hx_poa_prune_stats", "hx_poa_retry_stats", "hx_group_set_timeout", "hx_group_inject_fault", "hx_poa_reserve", "hx_poa_host_times", "hx_poa_arena_stats", "hx_group_rccl_ranks",
            "hx_group_create", "hx_group_destroy", "hx_group_size", "hx_group_ctx", "hx_group_transport", "hx_edge_merge", "hx_group_backend_fill", "hx_group_exchange_stats"]
 
@@ -61,6 +61,8 @@ def lib():
         L.hx_free_band.argtypes = [C.c_void_p, C.POINTER(T.BandOut)]
         L.hx_poa_labelled.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.PoaLabelParams), C.POINTER(T.LabelOut)]
         L.hx_free_label.argtypes = [C.c_void_p, C.POINTER(T.LabelOut)]
+        L.hx_poa_phased.argtypes = [C.c_void_p, C.c_uint32, T.u64p, T.u64p, C.c_char_p, C.c_char_p, C.POINTER(T.PoaConvexParams), C.POINTER(T.PoaPhaseParams), C.POINTER(T.PhaseOut)]
+        L.hx_free_phase.argtypes = [C.c_void_p, C.POINTER(T.PhaseOut)]
         L.hx_free_chain.argtypes = [C.c_void_p, C.POINTER(T.ChainOut)]
         L.hx_free_edges.argtypes = [C.c_void_p, C.POINTER(T.EdgesOut)]
         L.hx_free_coords.argtypes = [C.c_void_p, C.POINTER(T.CoordsOut)]
@@ -208,6 +210,12 @@ BandRecord = namedtuple("BandRecord", "consensus band_used rows coverage profile
 # text, one row per given sequence and, with include_consensus, one more per label.
 LabelRecord = namedtuple("LabelRecord", "consensus columns coverage profile rows")
 NO_LABEL = 255
+# One set of HipContext.poa_phased (include/haslr_types.h, hx_phase_out). hap: per given sequence its haplotype, 0, 1 or 255 (none: an empty
+# sequence, or one that no site assigned); n_haps 2, or 1 where the set was left unphased (then every non-empty sequence is in haplotype
+# 0); rounds: the voting rounds run; sites: (column, a1, a2, phase) per heterozygous MSA column in column order, a1 / a2 the two most
+# frequent alleles (0..3 A C G T, 4 a gap), phase +1 where haplotype 0 carries a1, -1 where it carries a2, 0 undecided or unphased.
+# consensus, columns, coverage, profile and rows: LabelRecord's for the two haplotypes as labels.
+PhaseRecord = namedtuple("PhaseRecord", "hap n_haps rounds sites consensus columns coverage profile rows")
 
 
 def _out_edges_in_list_order(rec):
@@ -698,6 +706,55 @@ class HipContext:
             st = _counters(o, "slot_reruns")
         finally:
             lib().hx_free_label(self._h, C.byref(o))
+        return (res, st) if stats else res
+
+    def poa_phased(self, sets, type="nw", match=5, mismatch=-4, gap_open=-8, gap_extend=None, gap_open2=None, gap_extend2=None, weights=None, qualities=None,
+                   min_count=2, min_pct=25, msa=False, include_consensus=False, coverage=False, profile=False, stats=False):
+        """two-haplotype consensus with automatic read phasing (hx_poa_phased): the graph, the MSA columns and the weights of every set are
+        poa_weighted's; the heterozygous columns (sites: the second most frequent allele, a gap inside a read's span counting as one, is
+        seen min_count times and in min_pct per cent of the column's depth) split the reads into two haplotypes by a seed site and at most
+        eight voting rounds, and each haplotype gets poa_labelled's consensus for its reads as a label. A set without a site, or with a
+        haplotype of fewer than min_count reads, is left unphased: one haplotype, poa_weighted's consensus. min_count is 1..255, min_pct
+        1..50. A list with one PhaseRecord per set; msa, include_consensus, coverage, profile, the scores and weights / qualities as for
+        poa_labelled. With stats=True returns (records, counters): dp_cells, seq_bases, n_aligned and slot_reruns."""
+        import numpy as np
+        _check_type(type)
+        ge = gap_open if gap_extend is None else gap_extend
+        cp = _convex_params(type, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
+        if cp is None:   # one piece: a second one that is the first again never wins
+            cp = T.PoaConvexParams(match, mismatch, gap_open, ge, gap_open, ge, T.POA_TYPES[type])
+        if not 1 <= int(min_count) <= 255 or not 1 <= int(min_pct) <= 50:
+            raise ValueError("min_count is 1..255, min_pct 1..50")
+        wbytes = _weight_bytes(sets, weights, qualities)
+        pp = T.PoaPhaseParams(int(min_count), int(min_pct), int(bool(msa)), int(bool(msa and include_consensus)), int(bool(coverage)), int(bool(profile)))
+        o = T.PhaseOut()
+        n_sets, set_off, seq_off, bases = _flatten_sets(sets)
+        self._chk(lib().hx_poa_phased(self._h, n_sets, set_off, seq_off, bases, wbytes, C.byref(cp), C.byref(pp), C.byref(o)))
+        try:
+            off = T.arr(o.cns_off, n_sets * 2 + 1, np.uint64).astype(np.int64)
+            tot = int(off[-1])
+            raw = C.string_at(o.cns, tot).decode() if tot else ""
+            col = T.arr(o.cns_col, tot, np.uint32).tolist()
+            cov = T.arr(o.coverage, tot, np.uint32).tolist() if o.coverage else None
+            prof = T.arr(o.profile, 4 * tot, np.uint32).reshape(-1, 4).tolist() if o.profile else None
+            rows = T.msa_to_lists(o)[0] if msa else None
+            nseq = sum(len(st) for st in sets)
+            hap = T.arr(o.hap, nseq, np.uint8).tolist()
+            nh, rd = T.arr(o.n_haps, n_sets, np.uint32).tolist(), T.arr(o.rounds, n_sets, np.uint32).tolist()
+            soff = T.arr(o.site_off, n_sets + 1, np.uint64).astype(np.int64)
+            ns = int(soff[-1])
+            sites = list(zip(T.arr(o.site_col, ns, np.uint32).tolist(), T.arr(o.site_a1, ns, np.uint8).tolist(), T.arr(o.site_a2, ns, np.uint8).tolist(),
+                             T.arr(o.site_phase, ns, np.int8).tolist()))
+            res, k0 = [], 0
+            for i in range(n_sets):
+                cut = [(int(off[i * 2 + g]), int(off[i * 2 + g + 1])) for g in range(2)]
+                res.append(PhaseRecord(hap[k0:k0 + len(sets[i])], nh[i], rd[i], sites[int(soff[i]):int(soff[i + 1])],
+                                       [raw[a:b] for a, b in cut], [col[a:b] for a, b in cut], [cov[a:b] for a, b in cut] if coverage else None,
+                                       [prof[a:b] for a, b in cut] if profile else None, rows[i] if msa else None))
+                k0 += len(sets[i])
+            st = _counters(o, "slot_reruns")
+        finally:
+            lib().hx_free_phase(self._h, C.byref(o))
         return (res, st) if stats else res
 
     def poa_phase_cycles(self):

@@ -211,6 +211,21 @@ void hx_free_band(hx_ctx*, hx_band_out*);
  *                     rules to a CPU restatement. */
 int hx_poa_labelled(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const uint8_t* labels, const hx_poa_convex_params*, const hx_poa_label_params*, hx_label_out* out);
 void hx_free_label(hx_ctx*, hx_label_out*);
+/*   hx_poa_phased     two-haplotype consensus with automatic read phasing (DESIGN.md "General POA path", "Two-haplotype consensus"; the
+ *                     arrays: haslr_types.h, hx_phase_out): for reads without haplotags from a diploid sample, a two-copy repeat or a mixed
+ *                     amplicon. Alignment, graph, rank order, columns and weights are hx_poa_weighted's for the same sets. On the set's MSA
+ *                     columns the call finds the sites (the second most frequent allele - a letter, or a gap inside a read's span - is seen
+ *                     min_count times and in min_pct per cent of the column's depth), splits the reads at the site with the largest minor
+ *                     count, lets every read vote over all of its sites for at most 8 rounds, and gives every haplotype hx_poa_labelled's
+ *                     consensus, columns, coverage, profile and consensus row with its reads as a label. A set without a site, or with a
+ *                     haplotype of fewer than min_count reads, is left unphased: n_haps 1, haplotype 0 holds every read and its consensus is
+ *                     hx_poa_weighted's. All arithmetic is integer; base weights weigh the bundles, not the votes. One entry over the
+ *                     convex parameters, by hx_poa_graph's rules for the gap model; weights as for hx_poa_weighted, or NULL. The errors are
+ *                     hx_poa_graph's with this entry's name in front, and: min_count outside 1..255, min_pct outside 1..50 (each names the
+ *                     value). Options poa_modes_slot_kb and poa_workspace_gb act as on the other entries. No band, no strands, no graph
+ *                     output, two haplotypes at most. Not pinned against another program: the tests hold the rules to a CPU restatement. */
+int hx_poa_phased(hx_ctx*, uint32_t n_sets, const uint64_t* set_off, const uint64_t* seq_off, const char* bases, const uint8_t* weights, const hx_poa_convex_params*, const hx_poa_phase_params*, hx_phase_out* out);
+void hx_free_phase(hx_ctx*, hx_phase_out*);
 void hx_free_chain(hx_ctx*, hx_chain_out*);
 void hx_free_edges(hx_ctx*, hx_edges_out*);
 void hx_free_coords(hx_ctx*, hx_coords_out*);

@@ -338,6 +338,47 @@ typedef struct {
     uint32_t slot_reruns;
 } hx_label_out;
 
+/* hx_poa_phased: the two thresholds of the site rule, and what is wanted beside the consensus strings and their columns (hx_poa_strand_want's
+ * four switches). */
+typedef struct {
+    uint32_t min_count;        /* 1..255 (2 is a sound default): a column is a site if its second allele is seen at least this often ... */
+    uint32_t min_pct;          /* 1..50 (25 is a sound default): ... and in at least this share, in per cent rounded up, of the column's depth */
+    int32_t want_msa;          /* 0 / 1: the alignment text of every set */
+    int32_t include_consensus; /* 0 / 1: with want_msa, one consensus row per haplotype (two) behind the rows of every set */
+    int32_t want_coverage;     /* 0 / 1: the coverage of every consensus base within its haplotype */
+    int32_t want_profile;      /* 0 / 1: and the four letter counts of its column within its haplotype (the coverage is filled in as well) */
+} hx_poa_phase_params;
+
+/* hx_poa_phased: two-haplotype consensus with automatic read phasing (DESIGN.md "General POA path", "Two-haplotype consensus"). The first
+ * fields are hx_label_out's, at its offsets, for n_labels = 2 with the haplotypes as labels: the consensus of haplotype h of set i is entry
+ * 2 i + h. hap holds a byte per sequence of the call: 0, 1, or 255 (an empty sequence, or one that no site assigned). n_haps is 2, or 1
+ * where the set was left unphased: then every non-empty sequence is in haplotype 0 and haplotype 1's consensus is empty. rounds: the voting
+ * rounds run (0 without a site, at most 8). The sites of set i are entries site_off[i] .. site_off[i + 1], in column order: the MSA column,
+ * its two most frequent alleles (0..3 A C G T, 4 a gap inside a read's span) and the phase: +1 haplotype 0 carries a1, -1 it carries a2,
+ * 0 undecided or unphased. */
+typedef struct {
+    uint32_t n_set, n_labels;
+    uint64_t* cns_off;  /* n_set * 2 + 1 */
+    char* cns;
+    uint32_t* cns_col;  /* cns_off[n_set * 2] */
+    uint32_t* coverage; /* cns_off[n_set * 2], or NULL */
+    uint32_t* profile;  /* 4 * cns_off[n_set * 2], or NULL */
+    uint32_t* n_rows;   /* n_set, or NULL */
+    uint32_t* n_cols;   /* n_set, or NULL */
+    uint64_t* msa_off;  /* n_set+1, or NULL */
+    char* msa;          /* or NULL */
+    uint64_t dp_cells, seq_bases, n_aligned;
+    uint32_t slot_reruns;
+    uint8_t* hap;        /* one per sequence of the call */
+    uint32_t* n_haps;    /* n_set */
+    uint32_t* rounds;    /* n_set */
+    uint64_t* site_off;  /* n_set+1 */
+    uint32_t* site_col;  /* site_off[n_set] */
+    uint8_t* site_a1;    /* site_off[n_set] */
+    uint8_t* site_a2;    /* site_off[n_set] */
+    int8_t* site_phase;  /* site_off[n_set] */
+} hx_phase_out;
+
 #ifdef __cplusplus
 }
 #endif

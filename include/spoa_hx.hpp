@@ -563,6 +563,69 @@ inline std::vector<Labelled> labelled_batch(const std::vector<std::vector<std::s
     return labelled_batch(detail::pointers(sets), detail::pointers(weights), labels, n_labels, type, m, n, g, e, q, c, msa, include_consensus);
 }
 
+// two-haplotype consensus in ONE device call (hx_poa_phased): the graph of a set is built from all of its sequences as weighted_batch
+// builds it, the call itself splits the reads on the heterozygous MSA columns (min_count, min_pct: how often and in what share of a
+// column's depth the second allele must be seen) and every haplotype gets labelled_batch's consensus for its reads. Per set: the haplotype
+// of every read (0, 1, 255: none), n_haps (1: left unphased, everything in haplotype 0), the voting rounds, the sites, and per haplotype
+// what Labelled holds. weights as for weighted_batch, or empty: every weight is 1. (q, c) == (g, e) is one gap piece, and then e == g the
+// linear model.
+struct PhaseSite { std::uint32_t column; std::uint8_t a1, a2; std::int8_t phase; };   // alleles 0..3 A C G T, 4 a gap; phase +1: haplotype 0 carries a1
+struct Phased {
+    std::vector<std::uint8_t> hap;                      // one per sequence
+    std::uint32_t n_haps = 0, rounds = 0;
+    std::vector<PhaseSite> sites;
+    std::vector<std::string> consensus;                 // one per haplotype (two entries; the second empty in an unphased set)
+    std::vector<std::vector<std::uint32_t>> columns;    // one per haplotype: the column of every consensus base
+    std::vector<std::string> rows;                      // empty unless asked for
+};
+inline std::vector<Phased> phased_batch(const std::vector<const std::vector<std::string>*>& sets, const std::vector<const std::vector<std::vector<std::uint8_t>>*>& weights,
+                                        AlignmentType type, std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, std::int8_t q = -8, std::int8_t c = -8,
+                                        std::uint32_t min_count = 2, std::uint32_t min_pct = 25, bool msa = false, bool include_consensus = false) {
+    if (!weights.empty() && weights.size() != sets.size()) throw std::invalid_argument("spoa_hx: phased_batch needs one set of weights per set of sequences, or none");
+    const detail::Flat f(sets);
+    std::vector<std::uint8_t> w;
+    for (std::size_t i = 0; i < sets.size() && !weights.empty(); i++) {
+        const auto& st = *sets[i];
+        if (weights[i]->size() != st.size()) throw std::invalid_argument("spoa_hx: phased_batch: a set has another number of weight vectors than of sequences");
+        for (std::size_t k = 0; k < st.size(); k++) {
+            const auto& wk = (*weights[i])[k];
+            if (wk.size() != st[k].size()) throw std::invalid_argument("spoa_hx: phased_batch: a sequence has another number of weights than of bases");
+            w.insert(w.end(), wk.begin(), wk.end());
+        }
+    }
+    if (!weights.empty() && w.empty()) w.push_back(1);   // (no base at all: a pointer that is not null, nothing behind it is read)
+    const hx_poa_convex_params cp{m, n, g, e, q, c, static_cast<std::int32_t>(type)};
+    const hx_poa_phase_params pp{min_count, min_pct, msa ? 1 : 0, msa && include_consensus ? 1 : 0, 0, 0};
+    hx_phase_out out;
+    return detail::locked_call([&](hx_ctx* ctx) { return hx_poa_phased(ctx, f.n_sets(), f.set_off.data(), f.seq_off.data(), f.bases.c_str(), weights.empty() ? nullptr : w.data(), &cp, &pp, &out); },
+                               [&](hx_ctx* ctx) -> std::vector<Phased> {
+        std::vector<Phased> res(sets.size());
+        for (std::size_t i = 0; i < sets.size(); i++) {
+            Phased& d = res[i];
+            d.hap.assign(out.hap + f.set_off[i], out.hap + f.set_off[i + 1]);
+            d.n_haps = out.n_haps[i]; d.rounds = out.rounds[i];
+            for (std::uint64_t s = out.site_off[i]; s < out.site_off[i + 1]; s++) d.sites.push_back(PhaseSite{out.site_col[s], out.site_a1[s], out.site_a2[s], out.site_phase[s]});
+            for (std::uint32_t l = 0; l < 2; l++) {
+                const std::uint64_t a = out.cns_off[i * 2 + l], b = out.cns_off[i * 2 + l + 1];
+                d.consensus.emplace_back(out.cns + a, out.cns + b);
+                d.columns.emplace_back(out.cns_col + a, out.cns_col + b);
+            }
+            if (msa)
+                for (std::uint32_t r = 0; r < out.n_rows[i]; r++) {
+                    const char* p = out.msa + out.msa_off[i] + static_cast<std::uint64_t>(r) * out.n_cols[i];
+                    d.rows.emplace_back(p, p + out.n_cols[i]);
+                }
+        }
+        hx_free_phase(ctx, &out);
+        return res;
+    });
+}
+inline std::vector<Phased> phased_batch(const std::vector<std::vector<std::string>>& sets, const std::vector<std::vector<std::vector<std::uint8_t>>>& weights, AlignmentType type,
+                                        std::int8_t m = 5, std::int8_t n = -4, std::int8_t g = -8, std::int8_t e = -8, std::int8_t q = -8, std::int8_t c = -8,
+                                        std::uint32_t min_count = 2, std::uint32_t min_pct = 25, bool msa = false, bool include_consensus = false) {
+    return phased_batch(detail::pointers(sets), detail::pointers(weights), type, m, n, g, e, q, c, min_count, min_pct, msa, include_consensus);
+}
+
 // Graphviz text of a graph, after spoa's Graph::print_dot: per node `id [label = "id - LETTER"]`, filled for the nodes of the consensus;
 // per out-edge, in out-list order, `from -> to [label = "weight"]`; one dotted line without arrowhead per pair of aligned nodes (nodes that
 // share a column), from the smaller to the larger id

@@ -33,6 +33,10 @@ sets in the same process: kernel time by the same protocol, the workspace the ca
 after, the workspace released in between; the banded call also reports the plan's own figure), the share of sets that did not finish at
 W (band_used != W: they climbed to a wider band or to the full matrix), the reruns that cost, and the share of sets whose banded consensus
 is the full-matrix one. A package without the banded entry (--package-root of a parent checkout) gives the full-matrix figures alone.
+--phase is a mode of its own over the workload of --labels: hx_poa_phased beside hx_poa_labelled at n_labels = 2 with the true haplotypes
+as labels, on the same sets in the same session; the ratio of the kernel times is what the phasing costs, and the share of the reads that
+land on their true haplotype is reported as a measurement.
+
 --labels is another mode of its own: a two-haplotype workload (per set a template and a copy of it with SNPs and one indel, noisy reads of
 each) under kNW, affine scores, through hx_poa_labelled at n_labels = 1, 2 and 16 beside hx_poa_weighted on the same sets in the same
 build: kernel time of each and the ratio over the weighted call, which is what the label passes cost on top of the DP.
@@ -233,6 +237,59 @@ def labels_mode(a, hip):
             f.write(json.dumps(res) + "\n")
 
 
+def phase_mode(a, hip):
+    """the two-haplotype workload of --labels through hx_poa_phased and, on the same sets in the same session, through hx_poa_labelled
+    with n_labels = 2 and the true haplotypes as labels: the ratio of the kernel times is what the phasing costs"""
+    rng = np.random.default_rng(a.seed)
+    sets, haps = workload_haplotypes(rng, a.sets_a)
+    m, n, g, e = a.affine_scores
+    kw = dict(type="nw", match=m, mismatch=n, gap_open=g, gap_extend=e)
+    ctx = hip.HipContext(0)
+    res = {"tool": "poa_modes_bench", "mode": "phase", "seed": a.seed, "repeats": a.repeats, "sets": len(sets), "scores": [m, n, g, e],
+           "longest_sequence": max(len(q) for st in sets for q in st), "bases": sum(len(q) for st in sets for q in st)}
+
+    def one(fn):
+        ctx.timing_reset()
+        t0 = time.perf_counter()
+        fn()
+        return ctx.timing()["poa"]["ms"], (time.perf_counter() - t0) * 1e3
+
+    def stats_of(runs):
+        ms = [m for m, _ in runs]
+        out = {"kernel_ms_median": round(float(np.median(ms)), 2), "kernel_ms_min": round(min(ms), 2), "kernel_ms_max": round(max(ms), 2)}
+        out.update(wall_stats([w for _, w in runs]))
+        return out
+    # the first call of each is its warm-up (workspace, code objects); then the two calls take turns, so that neither has the later, warmer half of the session to itself
+    lrecs, lst = ctx.poa_labelled(sets, haps, 2, stats=True, **kw)
+    recs, st = ctx.poa_phased(sets, stats=True, **kw)
+    lruns, pruns = [], []
+    for _ in range(a.repeats):
+        lruns.append(one(lambda: ctx.poa_labelled(sets, haps, 2, **kw)))
+        pruns.append(one(lambda: ctx.poa_phased(sets, **kw)))
+    lab = stats_of(lruns)
+    lab["cells"] = int(lst["dp_cells"])
+    res["labelled_2"] = lab
+    note("phase", "labelled", lab["kernel_ms_median"], "ms")
+    r = stats_of(pruns)
+    r["over_labelled_by_turn"] = [round(p[0] / q[0], 4) for p, q in zip(pruns, lruns)]
+    same = sum(rec.hap in (hs, [1 - h for h in hs]) for rec, hs in zip(recs, haps))
+    reads = sum(len(hs) for hs in haps)
+    agree = sum(max(sum(x == y for x, y in zip(rec.hap, hs)), sum(x == 1 - y for x, y in zip(rec.hap, hs))) for rec, hs in zip(recs, haps))
+    r.update({"cells": int(st["dp_cells"]), "slot_reruns": int(st["slot_reruns"]), "over_labelled": round(r["kernel_ms_median"] / lab["kernel_ms_median"], 4),
+              "over_labelled_min": round(r["kernel_ms_min"] / lab["kernel_ms_max"], 4), "over_labelled_max": round(r["kernel_ms_max"] / lab["kernel_ms_min"], 4),
+              "ranges_overlap": bool(r["kernel_ms_min"] <= lab["kernel_ms_max"] and lab["kernel_ms_min"] <= r["kernel_ms_max"]),
+              "sets_phased": int(sum(rec.n_haps == 2 for rec in recs)), "sites": int(sum(len(rec.sites) for rec in recs)), "rounds_max": int(max(rec.rounds for rec in recs)),
+              "share_sets_with_the_true_haplotypes": round(same / len(sets), 4), "share_reads_on_their_true_haplotype": round(agree / reads, 4),
+              "share_sets_with_the_labelled_consensus": round(sum(rec.consensus in (lr.consensus, lr.consensus[::-1]) for rec, lr in zip(recs, lrecs)) / len(sets), 4)})
+    res["phased"] = r
+    note("phase", "phased", r["kernel_ms_median"], "ms")
+    ctx.close()
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sets-a", type=int, default=256)
@@ -247,6 +304,7 @@ def main():
     ap.add_argument("--package-root", default=ROOT, help="the tree whose built haslr_amd package runs (default: this one); parts it does not have are left out")
     ap.add_argument("--band", type=int, nargs="+", metavar="W", help="the band mode: workload (a) under kNW and kOV through hx_poa_banded at these half-widths, against the full-matrix general path")
     ap.add_argument("--labels", action="store_true", help="the label mode: the two-haplotype workload through hx_poa_labelled at n_labels = 1, 2 and 16, against hx_poa_weighted on the same sets")
+    ap.add_argument("--phase", action="store_true", help="the phase mode: the two-haplotype workload through hx_poa_phased, against hx_poa_labelled with n_labels = 2 and the true haplotypes on the same sets")
     ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.package_root))
@@ -255,6 +313,8 @@ def main():
         return band_mode(a, hip)
     if a.labels:
         return labels_mode(a, hip)
+    if a.phase:
+        return phase_mode(a, hip)
     import cvxlib
     import msalib
     import parlib
