@@ -1,8 +1,8 @@
 """ctypes loader for tests/poa_graph_ref.cpp, the CPU restatement of the graph and alignment output of the general POA path. It is compiled
 with g++ into a directory the caller gives (a pytest temporary directory, or one of tools/poa_modes_bench.py's own). Scores are always the
 six (match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2); the gap model follows from them by the C-ABI's rule (model_of). A
-result is a haslr_amd.hip.GraphRecord, the type HipContext.poa_graph returns, so that both sides compare field by field; checks() and
-rescore() state the properties such a record must have by itself, whoever made it."""
+result is a haslr_amd.hip.GraphRecord, the type HipContext.poa_graph returns, so that both sides compare field by field; checks(),
+rescore() and ends() state the properties such a record must have by itself, whoever made it."""
 import ctypes as C
 import os
 import subprocess
@@ -209,6 +209,47 @@ def rescore(rec, seqs, scores, type, before=None):
         if p:
             seen_v = max(seen_v, max(p))
             seen_e = max([seen_e] + [edge.get((p[i - 1], p[i]), -1) for i in range(1, len(p))])
+    return bad
+
+
+def ends(rec, seqs, type):
+    """where every alignment starts and ends in the graph as it was before the add (the union of the earlier paths), which rescore does not
+    look at. The rules are read off the DP's boundary, end and stop rules (DESIGN.md "General POA path"; dp_rows and the restatements):
+    row 0 is the predecessor of the rows without in-edges only, and the walk emits a pair per move.
+
+    kNW  the end cell is (a sink, L) and the walk stops at (0, 0) only. Row 0 is left to a source, by a diagonal or a vertical move, which
+         both carry the node: the first pair with a node holds a source, the last one the end cell's row, a sink. (rescore holds the
+         positions to 0 .. L - 1.)
+    kOV  the end cell (i, j), j >= 1, is in a sink's row or in column L; the walk stops in row 0 or in column 0.
+         Start: column 0 is entered by a diagonal or a horizontal move, which both carry position 0, and row 0 from a source: the
+         alignment holds position 0, or its first pair with a node holds a source.
+         End: horizontal moves leave the row, so the last pair with a node, if there is one, holds the end cell's row; vertical moves
+         leave the column, so the last position, if there is one, is j - 1. An alignment with both holds position L - 1 or ends in a
+         sink. One without a position (a walk straight up column j, as ["A", "C"] under a dear mismatch) records neither j nor anything
+         else of its end, and one without a node nothing of its row: of those only the start is checked.
+    kSW  may start and end anywhere.
+    Returns the list of what does NOT hold."""
+    bad = []
+    has_in, has_out = set(), set()   # the nodes with an edge into / out of them among the edges the earlier paths walk
+    for k, (q, sq) in enumerate(zip(seqs, rec.sequences)):
+        nodes = [n for n, _ in sq.alignment if n != -1]
+        pos = [p for _, p in sq.alignment if p != -1]
+        if sq.alignment and type == "nw":
+            if not nodes:
+                bad.append(f"alignment {k}: a global alignment holds no node")
+            else:
+                if nodes[0] in has_in:
+                    bad.append(f"alignment {k}: a global alignment starts at node {nodes[0]}, which is no source")
+                if nodes[-1] in has_out:
+                    bad.append(f"alignment {k}: a global alignment ends at node {nodes[-1]}, which is no sink")
+        elif sq.alignment and type == "ov":
+            if not (pos and pos[0] == 0) and not (nodes and nodes[0] not in has_in):
+                bad.append(f"alignment {k}: an overlap starts neither at position 0 nor at a source")
+            if nodes and pos and pos[-1] != len(q) - 1 and nodes[-1] in has_out:
+                bad.append(f"alignment {k}: an overlap ends neither at the last position nor at a sink")
+        p = [int(n) for n in sq.path]
+        has_out.update(p[:-1])
+        has_in.update(p[1:])
     return bad
 
 

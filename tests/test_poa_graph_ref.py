@@ -51,7 +51,7 @@ def failing(ref, msa, cvx, sets, mode, scores, weights=None):
     rows = pmap(lambda st: want_rows(msa, cvx, st, mode, scores), sets)
     out = []
     for k, (st, (rec, _, before)) in enumerate(zip(sets, res)):
-        bad = grflib.checks(rec, st, None if weights is None else weights[k]) + grflib.rescore(rec, st, scores, mode, before) + grflib.rescore(rec, st, scores, mode)
+        bad = grflib.checks(rec, st, None if weights is None else weights[k]) + grflib.rescore(rec, st, scores, mode, before) + grflib.rescore(rec, st, scores, mode) + grflib.ends(rec, st, mode)
         if grflib.rows_of(rec, st) != rows[k]:
             bad.append("the rows rebuilt from paths and columns are not the MSA restatement's")
         letters, ef, et, ew = ref.replay(st, rec)
